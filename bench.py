@@ -27,6 +27,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md: 8.0 TB/s; ~6.3 TB/s achievable)
+DUMP_LIMIT_BYTES = 64_000_000   # --dump-outputs: at most this much in all (64 MB)
+DUMP_SEED = 42                # ... and the sample of the groups it takes above that
 
 
 def kernel_sources_hash() -> str:
@@ -101,6 +103,30 @@ def parity_gate(table, w, plan, my_segments, executor):
                 int(tot.states[j][0]) & ((1 << (8 * sj.dtype.itemsize)) - 1), "totals disagree"
     return {"oracle_window_segments": win, "oracle_window_rows": win * win_rows, "oracle_groups": st.ngroups,
             "cross_path": "dense vs hash organisation, bit-exact over %d rows" % full.scanned_recs, "seconds": round(time.time() - t0, 2)}
+
+
+def dump_outputs(res, w, plan, out_dir: str) -> dict:
+    """--dump-outputs: what the timed path returned in its last step — the group keys, the metric states and (AVG) the hidden counts —
+    as <out_dir>/<name>.npy in float64. The groups are written sorted by their keys (the library's order depends on the table path),
+    so that two builds can be compared array for array. When the arrays exceed DUMP_LIMIT_BYTES, a fixed seeded sample of the sorted
+    groups is written instead, and group_index.npy holds the samples' positions in the sorted order."""
+    import numpy as np
+    arrays = [("key%d_%s" % (i, w.columns[g.col].name), k) for i, (g, k) in enumerate(zip(plan.groups, res.keys))]
+    arrays += [("state%d_%s" % (j, w.columns[m].name), s) for j, (m, s) in enumerate(zip(plan.metrics, res.states))]
+    if res.hidden_count is not None:
+        arrays.append(("hidden_count", res.hidden_count))
+    ng = len(arrays[0][1]) if arrays else 0
+    order = np.lexsort([k for k in reversed(res.keys)]) if res.keys else np.arange(ng)
+    keep = (DUMP_LIMIT_BYTES - 4096 * (len(arrays) + 1)) // (8 * (len(arrays) + 1))      # (+1: group_index; 4 KB per .npy header)
+    sampled = ng > keep
+    if sampled:
+        pos = np.sort(np.random.default_rng(DUMP_SEED).choice(ng, keep, replace=False))
+        order = order[pos]
+        arrays.append(("group_index", pos))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays:
+        np.save(os.path.join(out_dir, name + ".npy"), (a if name == "group_index" else a[order]).astype(np.float64))
+    return {"dir": out_dir, "arrays": [n for n, _ in arrays], "groups": ng, "written_groups": len(order), "sampled": sampled}
 
 
 def cpu_baseline(w, sample_segments: int):
@@ -247,7 +273,10 @@ def main():
     ap.add_argument("--no-reference-layout", action="store_true", help="skip the arena-only leg (profiling runs)")
     ap.add_argument("--no-unprepared", action="store_true", help="skip the unprepared-caller leg (a second table: profiling runs)")
     ap.add_argument("--rendezvous-only", action="store_true", help="launch the ranks, meet over gloo, print who came, stop (the launcher's own test: needs no GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the last step's result arrays to DIR/<name>.npy (float64, groups sorted by key, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         raise SystemExit(self_launch(args.gpus))       # a plain `python bench.py --gpus N`: become N ranks under torch.distributed.run
@@ -355,6 +384,9 @@ def main():
             kernel_ms.append(last.scan_kernel_ms)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # now: `last` aliases the staging buffer that the queries below write into
+        print("bench.py: --dump-outputs %s" % json.dumps(dump_outputs(last, w, plan, args.dump_outputs)), file=sys.stderr, flush=True)
 
     # The same query on the REFERENCE layout — the 4-byte column arenas only, no payload projection, no narrow predicate copies
     # (VH_PLAN_NO_PACK | VH_PLAN_NO_NARROW) — timed in the same run, after the headline loop: what the kernels do with the

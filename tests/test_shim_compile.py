@@ -4,7 +4,10 @@ reference's JIT-compiled function stands: extern "C" viya_query_agg with the exa
 (src/query/runner.h:33-35) and the generated per-table `Segment` class (src/codegen/db/store.cc:203-356). Here the text is
 checked with `g++ -std=c++17 -fsyntax-only` against the reference's REAL headers — db/table.h, db/dictionary.h, db/store.h,
 db/segment.h, query/output.h, query/stats.h — plus a forward declaration standing for <nlohmann/json_fwd.hpp> (the JSON
-submodule is not in the mount). Skipped where /root/reference does not exist (the GPU box)."""
+submodule is not in the mount). Where /root/reference does not exist (the GPU box, a clean checkout elsewhere) the tests hold the emitted
+text to what was compiled against those headers when tests/golden/shim_golden.json was recorded (oracle/make_shim_golden.py: every
+text by its sha256, the objects' symbol tables, the reference's declaration text), and run their assertions on the recorded data."""
+import hashlib
 import json
 import os
 import re
@@ -17,7 +20,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = "/root/reference/src"
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
-needs_ref = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is only present in the build container")
+HAVE_REF = os.path.isdir(REF)
+GOLDEN = os.path.join(ROOT, "tests", "golden", "shim_golden.json")
 
 TABLES = {
     "inapp": {"name": "events", "dimensions": [{"name": "country"}, {"name": "event_name", "cardinality": 200}, {"name": "install_time", "type": "time"},
@@ -52,14 +56,48 @@ def _syntax_check(text, tmp_path, name):
     assert r.returncode == 0, r.stderr[:4000]
 
 
-@needs_ref
+def _object_symbols(text, tmp_path, name, opt="-O2"):
+    """`g++ -c` of the text against the reference's headers; its symbol table (nm -C)."""
+    src = tmp_path / (name + ".cc")
+    obj = tmp_path / (name + ".o")
+    src.write_text(text)
+    r = subprocess.run(["g++", "-std=c++17", opt, "-fPIC", "-c", "-Wall", "-I" + REF, "-I" + os.path.join(ROOT, "include"),
+                        "-I" + os.path.join(ROOT, "tools", "shim_include"), str(src), "-o", str(obj)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[:4000]
+    return subprocess.run(["nm", "-C", str(obj)], capture_output=True, text=True, check=True).stdout
+
+
+def _golden():
+    return json.load(open(GOLDEN))
+
+
+def _pinned(key, text):
+    """The text is the one that compiled against the reference's headers when tests/golden/shim_golden.json was recorded."""
+    assert hashlib.sha256(text.encode()).hexdigest() == _golden()["tus"][key]["sha256"], \
+        "%s: not the text recorded in tests/golden/shim_golden.json (record it again with oracle/make_shim_golden.py where the reference tree exists)" % key
+
+
+def reference_declarations():
+    """From the reference's sources: the declaration texts of viya_query_agg that AggQueryGenerator emits (agg_query.cc:35-44) and the
+    parameter list of query::AggQueryFn (runner.h:33-35), whitespace removed."""
+    ref = open(os.path.join(REF, "codegen/query/agg_query.cc")).read()
+    pieces = re.findall(r'code << ((?:"(?:[^"\\]|\\.)*"\s*)+);', ref)
+    emitted = ["".join(re.findall(r'"((?:[^"\\]|\\.)*)"', p)).replace('\\"', '"').replace("\\n", "\n") for p in pieces]
+    sigs = [e for e in emitted if "viya_query_agg" in e]
+    runner = open(os.path.join(REF, "query/runner.h")).read()
+    m = re.search(r"using AggQueryFn = void \(\*\)\(([^;]*)\);", runner, re.S)
+    return sigs, [re.sub(r"\s+", "", x) for x in m.group(1).split(",")]
+
+
 @pytest.mark.parametrize("name", sorted(TABLES))
 def test_generated_shim_compiles_against_the_reference_headers(tmp_path, name):
     import gen_shim_tu
-    _syntax_check(gen_shim_tu.emit(TABLES[name], QUERIES[name]), tmp_path, name)
+    text = gen_shim_tu.emit(TABLES[name], QUERIES[name])
+    _pinned("syntax/" + name, text)
+    if HAVE_REF:
+        _syntax_check(text, tmp_path, name)
 
 
-@needs_ref
 @pytest.mark.parametrize("name", sorted(TABLES))
 def test_generated_shim_compiles_to_object_code(tmp_path, name):
     """One step past -fsyntax-only: `g++ -c` of the generated text against the reference's headers, so that the
@@ -68,13 +106,9 @@ def test_generated_shim_compiles_to_object_code(tmp_path, name):
     libviya_host.so (shim) and the reference's own libraries (db::Table, Dictionary, ...) provide. It has still never been LINKED behind
     QueryRunner::Visit: the reference cannot be built here (INTEGRATION.md says so)."""
     import gen_shim_tu
-    src = tmp_path / (name + ".cc")
-    obj = tmp_path / (name + ".o")
-    src.write_text(gen_shim_tu.emit(TABLES[name], QUERIES[name]))
-    r = subprocess.run(["g++", "-std=c++17", "-O2", "-fPIC", "-c", "-Wall", "-I" + REF, "-I" + os.path.join(ROOT, "include"),
-                        "-I" + os.path.join(ROOT, "tools", "shim_include"), str(src), "-o", str(obj)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[:4000]
-    syms = subprocess.run(["nm", "-C", str(obj)], capture_output=True, text=True, check=True).stdout
+    text = gen_shim_tu.emit(TABLES[name], QUERIES[name])
+    _pinned("object/" + name, text)
+    syms = _object_symbols(text, tmp_path, name) if HAVE_REF else _golden()["tus"]["object/" + name]["nm"]
     assert re.search(r"\bT viya_query_agg\b", syms), syms[:2000]
     undefined = [l.split(None, 1)[1] for l in syms.splitlines() if l.strip().startswith("U ")]
     assert any(u.startswith("viya::shim::Run(") for u in undefined) and any(u.startswith("viya::shim::Sync(") for u in undefined), undefined
@@ -87,23 +121,19 @@ def test_generated_shim_compiles_to_object_code(tmp_path, name):
         assert any("Roaring::toUint32Array" in u for u in undefined) and any("Roaring64Map::toUint64Array" in u for u in undefined), undefined
 
 
-@needs_ref
 def test_signature_is_the_one_the_reference_emits():
     """The declaration text of the swap point, character for character (modulo whitespace): agg_query.cc:35-44."""
     import gen_shim_tu
-    ref = open(os.path.join(REF, "codegen/query/agg_query.cc")).read()
-    pieces = re.findall(r'code << ((?:"(?:[^"\\]|\\.)*"\s*)+);', ref)
-    emitted = ["".join(re.findall(r'"((?:[^"\\]|\\.)*)"', p)).replace('\\"', '"').replace("\\n", "\n") for p in pieces]
-    sigs = [e for e in emitted if "viya_query_agg" in e]
+    g = _golden()
+    sigs, params = g["declarations"], g["agg_query_fn_params"]
+    if HAVE_REF:
+        assert reference_declarations() == (sigs, params), "tests/golden/shim_golden.json no longer says what the reference's sources say"
     assert len(sigs) == 2
     text = gen_shim_tu.emit(TABLES["inapp"], QUERIES["inapp"])
     norm = lambda s: re.sub(r"\s+", "", s)
     for s in sigs:
         assert norm(s) in norm(text), s
     # and the function type it is called through (runner.h:33-35) has the same parameter list
-    runner = open(os.path.join(REF, "query/runner.h")).read()
-    m = re.search(r"using AggQueryFn = void \(\*\)\(([^;]*)\);", runner, re.S)
-    params = [norm(x) for x in m.group(1).split(",")]
     assert params == ["db::Table&", "RowOutput&", "QueryStats&", "std::vector<db::AnyNum>", "size_t", "size_t", "std::vector<db::AnyNum>"]
 
 
@@ -120,43 +150,41 @@ def test_cxx_emitter_writes_what_the_python_generator_writes(name):
     assert hostdb.shim_text(None, None) == gen_shim_tu.upsert_hook()
 
 
-@needs_ref
+def upsert_hook_unit():
+    """The in-place branch of viya_upsert_do around the generated classes, with the hook line behind it (see the test below)."""
+    import gen_shim_tu
+    table = TABLES["user_events"]
+    text = gen_shim_tu.emit(table, QUERIES["user_events"])
+    classes = text[text.index("struct Tuple {"):text.index("static const char kTable[]")]       # Tuple / SegmentStats / Segment, as StoreDefs emits them
+    return ("#include <vector>\n#include <cstdint>\n#include <cstddef>\n#include <cfloat>\n#include <algorithm>\n#include <db/table.h>\n#include <db/store.h>\n#include <db/segment.h>\n"
+            "#include <util/bitset.h>\n#include <viya_shim.h>\nnamespace db = viya::db;\nnamespace util = viya::util;\n"
+            "struct LoaderContext { db::Table* table; };                                   // (input/loader: lctx->table)\n"
+            + classes +
+            "void viya_upsert_do_update_branch(LoaderContext* lctx, Tuple& upsert_tuple, size_t global_idx) {\n"
+            " auto* store = lctx->table->store();\n auto& segments = store->segments();\n"
+            " size_t segment_idx = global_idx / %d;\n size_t tuple_idx = global_idx %% %d;\n"
+            " (void)upsert_tuple; (void)static_cast<Segment*>(segments[segment_idx]);\n" % (1000000, 1000000)
+            + gen_shim_tu.upsert_hook() + "}\n")
+
+
 def test_upsert_hook_compiles_where_the_reference_would_emit_it(tmp_path):
     """UpsertGenerator writes the in-place branch of viya_upsert_do as text (src/codegen/db/upsert.cc:384-396):
     `static_cast<Segment*>(segments[segment_idx])->m.Update(upsert_tuple.m,tuple_idx);`. The hook line goes right behind it. Here that
     branch is rebuilt around the REAL db/table.h / db/store.h / db/segment.h — `lctx->table` is a db::Table*, `segments` the store's
     vector, the Segment class the generated one — and compiled to an object: the names the line uses exist there with these types, and
     the call resolves to viya::shim::Touch(const void*, unsigned, unsigned long, unsigned long)."""
-    import gen_shim_tu
-    table = TABLES["user_events"]
-    text = gen_shim_tu.emit(table, QUERIES["user_events"])
-    classes = text[text.index("struct Tuple {"):text.index("static const char kTable[]")]       # Tuple / SegmentStats / Segment, as StoreDefs emits them
-    src = tmp_path / "upsert_hook.cc"
-    src.write_text("#include <vector>\n#include <cstdint>\n#include <cstddef>\n#include <cfloat>\n#include <algorithm>\n#include <db/table.h>\n#include <db/store.h>\n#include <db/segment.h>\n"
-                   "#include <util/bitset.h>\n#include <viya_shim.h>\nnamespace db = viya::db;\nnamespace util = viya::util;\n"
-                   "struct LoaderContext { db::Table* table; };                                   // (input/loader: lctx->table)\n"
-                   + classes +
-                   "void viya_upsert_do_update_branch(LoaderContext* lctx, Tuple& upsert_tuple, size_t global_idx) {\n"
-                   " auto* store = lctx->table->store();\n auto& segments = store->segments();\n"
-                   " size_t segment_idx = global_idx / %d;\n size_t tuple_idx = global_idx %% %d;\n"
-                   " (void)upsert_tuple; (void)static_cast<Segment*>(segments[segment_idx]);\n" % (1000000, 1000000)
-                   + gen_shim_tu.upsert_hook() + "}\n")
-    obj = tmp_path / "upsert_hook.o"
-    r = subprocess.run(["g++", "-std=c++17", "-O1", "-fPIC", "-c", "-Wall", "-I" + REF, "-I" + os.path.join(ROOT, "include"),
-                        "-I" + os.path.join(ROOT, "tools", "shim_include"), str(src), "-o", str(obj)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[:4000]
-    syms = subprocess.run(["nm", "-C", str(obj)], capture_output=True, text=True, check=True).stdout
+    text = upsert_hook_unit()
+    _pinned("upsert_hook", text)
+    syms = _object_symbols(text, tmp_path, "upsert_hook", "-O1") if HAVE_REF else _golden()["tus"]["upsert_hook"]["nm"]
     assert "U viya::shim::Touch(void const*, unsigned int, unsigned long, unsigned long)" in syms, syms[:1500]
 
 
-@needs_ref
-def test_every_reference_test_table_gets_a_compilable_shim(tmp_path):
-    """The tables and aggregate queries of the reference's own known-answer tests (tests/golden/reference_cases.json), bitset tables
-    included (util/bitset.h is the reference's; CRoaring's two classes are declared — not defined — in tools/shim_include/)."""
+def reference_case_units():
+    """The generated text for the first 16 distinct (table, aggregate query) pairs of tests/golden/reference_cases.json."""
     import gen_shim_tu
     cases = json.load(open(os.path.join(ROOT, "tests", "golden", "reference_cases.json")))
     tables = cases["tables"] if isinstance(cases, dict) and "tables" in cases else {}
-    done = 0
+    units = []
     seen = set()
     for case in (cases["cases"] if isinstance(cases, dict) else cases):
         q = case.get("query") or {}
@@ -167,11 +195,22 @@ def test_every_reference_test_table_gets_a_compilable_shim(tmp_path):
         if key in seen:
             continue
         seen.add(key)
-        _syntax_check(gen_shim_tu.emit(t, q), tmp_path, "case%d" % done)
-        done += 1
-        if done >= 16:
+        units.append(gen_shim_tu.emit(t, q))
+        if len(units) >= 16:
             break
-    assert done >= 5, done
+    return units
+
+
+def test_every_reference_test_table_gets_a_compilable_shim(tmp_path):
+    """The tables and aggregate queries of the reference's own known-answer tests (tests/golden/reference_cases.json), bitset tables
+    included (util/bitset.h is the reference's; CRoaring's two classes are declared — not defined — in tools/shim_include/)."""
+    units = reference_case_units()
+    assert len(units) == len([k for k in _golden()["tus"] if k.startswith("case")])
+    for done, text in enumerate(units):
+        _pinned("case%d" % done, text)
+        if HAVE_REF:
+            _syntax_check(text, tmp_path, "case%d" % done)
+    assert len(units) >= 5, len(units)
 
 
 def test_shim_header_is_plain_cxx_without_reference_types():
