@@ -265,7 +265,10 @@ typedef struct vh_result_info {
                                 bit 11: predicate columns streamed as byte planes of a bit-packed predicate projection (vh_table_predpack; bit 4 is set too);
                                 bit 13: ... of its BIT-SLICED form (comparisons bit-serial on 32 rows per lane);
                                 bit 12: the payload was STREAMED — 4-byte bit-field records beside the predicate columns, a survivor's record queued in its
-                                        row's place — not gathered (bits 3 and 7 are set too) */
+                                        row's place — not gathered (bits 3 and 7 are set too);
+                                bit 14: DENSE_PART's one-word tuples were FOUR bytes (bit 10 is set too);
+                                bit 15: the projection's records are bit fields (bits 3 and 7 are set too);
+                                bits 16-18: log2 of the projection's record bytes, less one (4 bytes: 1 ... 64 bytes: 5; 0 when bit 3 is clear) */
   uint64_t returned_groups;  /* rows vh_result_copy delivers (= ngroups without HAVING) */
 } vh_result_info;
 

@@ -300,8 +300,8 @@ def test_four_byte_tuples_through_two_levels(monkeypatch):
 def test_four_byte_tuples(monkeypatch):
     """C3's gid (17 bits) and values (10 + 2 bits) fit 32 bits: DENSE_PART's tuple is four bytes — thirty-two to a 128-byte line through the ring
     writer, read back as 32-bit words by the compiled phase 2. Same groups as with the 8-byte tuple (VH_NO_TUPLE4) and as the oracle's, uniform and
-    Zipf-like keys, with every tuple through the overflow region too; a value that outgrows its recorded bits re-plans (VH_ERR_HP_WIDE) as with any
-    packed tuple."""
+    Zipf-like keys, with every tuple through the overflow region too. (A value that outgrows its recorded bits re-plans through VH_ERR_HP_WIDE:
+    tests/test_gpu_extremes.py::test_one_word_tuples_recover_from_a_wide_value.)"""
     if JIT_OFF:
         pytest.skip("packed tuples need the compiled kernels")
     for wl in ("C3", "C3z"):

@@ -237,6 +237,7 @@ struct QueryBuild {
   int hp_bpp = 1;
   uint32_t hp_chunk = 256;
   bool packed = false, packed_compressed = false;
+  bool packed_bits = false; uint32_t packed_rec = 0;     // ... the projection's records: bit fields, and their bytes (vh_result_info.reserved bits 15-18)
   int qpay = 0, qpay_slot = -1;                  // streamed payload (VhJitShape::qpay): the record's bytes, the slot the records come from
   std::vector<int> pp_cols;                      // the filter's columns (ascending) when every leaf reads a fixed-width column: what a predicate projection must hold
   int pp_boff[VJ_MAX_PRED] = {}, pp_bbits[VJ_MAX_PRED] = {}, pp_soff[VJ_MAX_PRED] = {}, pp_sbits[VJ_MAX_PRED] = {};      // predicate column k's bit field in the byte-plane / bit-sliced projection noted in jshape
@@ -919,6 +920,7 @@ int QueryBuild::choose_organisation() {
         const bool sgn = c.elem == VH_I8 || c.elem == VH_I16 || c.elem == VH_I32 || c.elem == VH_I64;
         if (sgn && (int64_t)(klo ^ (1ull << 63)) < 0) { fits = false; break; }      // negative values: the tuple's fields are unsigned
         nt_mb[j] = bits_of(sgn ? (khi ^ (1ull << 63)) : bits_of_order_key(c.elem, khi));
+        if (j == 0) if (const char* e = test_env("VH_TEST_TUPLE_BITS")) nt_mb[0] = std::max(1, nt_mb[0] - atoi(e));      // tests: the first metric's values do NOT fit -> VH_ERR_HP_WIDE -> no one-word tuples
         used += nt_mb[j];
       }
       narrow_tuples = fits && used <= 63;
@@ -1316,6 +1318,7 @@ int QueryBuild::choose_projection() {
       for (int j = 0; j < P.nmetric; ++j) if (metric_col[j] >= 0) P.m[j].set_slot((uint16_t)pslot(metric_col[j]));
       packed = true;
       packed_compressed = use->compressed;
+      packed_bits = use->bits; packed_rec = use->rec_bytes;
       if (qpay_want && use->bits && use->rec_bytes == 4) { qpay = 4; qpay_slot = pslot(gcols[0]); }      // (a bit-field record's members all start at the record: any member's slot is the record's)
     }
   }

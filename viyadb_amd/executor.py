@@ -89,6 +89,9 @@ class AggResult:
     sliced: bool = False           # ... of its bit-sliced form (comparisons bit-serial on 32 rows per lane)
     streamed_payload: bool = False  # ... and the payload records streamed beside them, a survivor's record queued in its row's place (no gathers)
     flags: int = 0                 # vh_result_info.reserved as it came
+    tuple4: bool = False           # DENSE_PART's one-word tuples were four bytes (gid and values in 32 bits)
+    pack_bits: bool = False        # the projection's records are bit fields
+    pack_rec_bytes: int = 0        # bytes of one projection record (0: no projection was read)
 
 
 
@@ -369,7 +372,9 @@ class DeviceTable:
                          float(info.total_ms), int(info.algorithmic_bytes), int(info.retries), bool(info.reserved & 1),
                          bool(info.reserved & 2), bool(info.reserved & 8), int(ng), (self.lib.vh_result_kernel(res) or b"").decode(),
                          bool(info.reserved & 16), bool(info.reserved & 32), bool(info.reserved & 64), bool(info.reserved & 128), bool(info.reserved & 256),
-                         bool(info.reserved & 2048), bool(info.reserved & 8192), bool(info.reserved & 4096), int(info.reserved))
+                         bool(info.reserved & 2048), bool(info.reserved & 8192), bool(info.reserved & 4096), int(info.reserved),
+                         bool(info.reserved & 16384), bool(info.reserved & 32768),
+                         (2 << ((info.reserved >> 16) & 7)) if info.reserved & 8 else 0)
 
     def query_agg(self, plan: AggPlan, copy: bool = True) -> AggResult:
         p, keep = self._build_plan(plan)
