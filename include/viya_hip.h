@@ -542,6 +542,12 @@ typedef struct vh_comm_info_t {
   char pci_bus_id[32];    /* "0000:c1:00.0" */
 } vh_comm_info_t;
 VH_API int vh_comm_info(vh_comm* c, vh_comm_info_t* out);
+/* ops.allgather_host of the communicator: every rank contributes `bytes` host bytes, recv = world x bytes, rank-major. A
+ * collective: every rank calls it, with the same `bytes`. For hosts that exchange small decisions over the same transport. */
+VH_API int vh_comm_allgather_host(vh_comm* c, const void* send, void* recv, uint64_t bytes);
+/* VH_COL_ROWID over a sharded table: positions are global — segment seg_base + s of a rank's snapshot segment s, seg_base being
+ * the number of snapshot segments (empty ones included) of the lower ranks — so they order as (rank, segment, row), the storage
+ * order of one table holding the ranks' contiguous blocks one after the other. */
 VH_API int vh_query_agg_sharded(vh_table* t, const vh_plan* plan, vh_comm* comm, int32_t root, vh_result** out);
 
 /* ---- the other two FilterBasedQuery kinds on the same scan ------------
@@ -576,6 +582,11 @@ typedef struct vh_rows_info {
   float kernel_ms, total_ms;
 } vh_rows_info;
 VH_API int vh_query_select(vh_table* t, const vh_select_plan* plan, vh_rows** out);
+/* select over a table sharded across GPUs (same communicator and collective rules as vh_query_agg_sharded: every rank calls it
+ * with the same plan): the rows one table holding all ranks' segments in rank order would return, through the same skip / limit
+ * window, delivered on `root`. scanned_recs, scanned_segments and passed_recs are global sums on every rank; nrows is the
+ * global count on root and 0 elsewhere. */
+VH_API int vh_query_select_sharded(vh_table* t, const vh_select_plan* plan, vh_comm* comm, int32_t root, vh_rows** out);
 VH_API int vh_rows_get_info(vh_rows* r, vh_rows_info* info);
 /* cols[c] = host array (pinned, owned by the vh_rows) of nrows elements of column c. */
 VH_API int vh_rows_view(vh_rows* r, const void** cols);

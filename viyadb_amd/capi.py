@@ -179,8 +179,10 @@ SYMBOLS = {
     "vh_comm_init_custom": (C.c_int, [C.POINTER(CommOps), C.c_int32, C.c_int32, C.POINTER(_VP)]),
     "vh_comm_destroy": (None, [_VP]),
     "vh_comm_info": (C.c_int, [_VP, C.POINTER(CommInfo)]),
+    "vh_comm_allgather_host": (C.c_int, [_VP, _VP, _VP, C.c_uint64]),
     "vh_query_agg_sharded": (C.c_int, [_VP, C.POINTER(Plan), _VP, C.c_int32, C.POINTER(_VP)]),
     "vh_query_select": (C.c_int, [_VP, C.POINTER(SelectPlan), C.POINTER(_VP)]),
+    "vh_query_select_sharded": (C.c_int, [_VP, C.POINTER(SelectPlan), _VP, C.c_int32, C.POINTER(_VP)]),
     "vh_rows_get_info": (C.c_int, [_VP, C.POINTER(RowsInfo)]),
     "vh_rows_view": (C.c_int, [_VP, C.POINTER(_VP)]),
     "vh_rows_free": (None, [_VP]),

@@ -77,6 +77,7 @@ struct vh_comm {
   struct BufShape { uint64_t count; int32_t elem, reduce; };
   struct Agreement {
     VhAgreed ag; uint64_t local_state;                         // local_state: plan_local_state() of THIS rank when the agreement was made
+    uint64_t seg_base = 0;                                     // snapshot segments of the lower ranks (from the summaries): where this rank's storage positions start
     // the partial table of a DENSE query planned from this agreement, as vh_result_device_buffers lists it — the same on every rank (same
     // plan, same agreed digit ranges), recorded when a query of this plan first went through on all ranks. Known: the query runs as ONE
     // stream-ordered sequence (scan, verdict and state arrays in one collective group, emission) with a single host wait at its end.
@@ -122,6 +123,8 @@ static uint64_t plan_local_state(const vh_plan* p, const vh_table* t) {
   mix(&ns, 8);
   if (p->seg_rows) mix(p->seg_rows, sizeof(uint64_t) * p->nseg);
   mix(&t->sync_epoch, 8);
+  const uint64_t tn = t->nseg;                       // (the segment count is what the next ranks' storage positions start from)
+  mix(&tn, 8);
   return h;
 }
 
@@ -257,6 +260,21 @@ extern "C" int vh_comm_info(vh_comm* c, vh_comm_info_t* out) {
   return VH_OK;
 }
 
+extern "C" int vh_comm_allgather_host(vh_comm* c, const void* send, void* recv, uint64_t bytes) {
+  if (!c || (!send && bytes) || (!recv && bytes)) return vh_fail(VH_E_INVALID, "null argument");
+  VH_ENTER();
+  if (int rc = c->ops.allgather_host(c->ops.ctx, send, recv, bytes)) return rc < 0 ? rc : vh_fail(VH_E_DEVICE, "host all-gather of %llu bytes failed (%d)", (unsigned long long)bytes, rc);
+  return VH_OK;
+}
+
+// what vh_query_select_sharded (vhh_select.h, earlier in this translation unit) uses of the communicator
+static void comm_shape(const vh_comm* c, int* rank, int* world) { *rank = c->rank; *world = c->world; }
+static std::mutex& comm_mutex(vh_comm* c) { return c->mu; }
+static int comm_alltoallv(vh_comm* c, int32_t ncols, const void* const* send, void* const* recv, const uint32_t* esize,
+                          const uint64_t* send_off, const uint64_t* recv_off, hipStream_t st) {
+  return c->ops.alltoallv_device(c->ops.ctx, ncols, send, recv, esize, send_off, recv_off, st);
+}
+
 // ------------------------------------------------------------------ plan agreement
 // Pure host arithmetic, also reachable from tests without a device (vh_plan_agree below is not part of the C ABI).
 static void merge_summaries(const VhSummary* all, int world, int ngroups, VhAgreed* ag, VhReplan* rp, bool* fatal) {
@@ -299,6 +317,33 @@ __global__ void sharded_flags_kernel(const unsigned long long* counters, unsigne
   flags[12] = (err & VH_ERR_HP_WIDE) ? 1 : 0;
   flags[13] = novoid;                              // this rank could not allocate the stand-in arrays of a void attempt: nobody records the dense shape
   for (int i = 14; i < VH_FLAG_WORDS; ++i) flags[i] = 0;
+}
+
+// Storage positions (VH_COL_ROWID, search's first occurrence) over a sharded table. A scan writes rank-local ones, segment << 32 | row;
+// in the global storage order (rank, local segment, row) of contiguous blocks a rank's segment s is segment seg_base + s, seg_base being
+// the number of snapshot segments of the lower ranks. The partial is rebased after the scan — the scan kernels, their compiled shapes and
+// cache keys stay those of a single table — before it is reduced (dense) or regrouped (hash). ~0ull, MIN's identity in an empty dense
+// slot, stays what it is.
+__global__ void rowid_rebase_kernel(unsigned long long* pos, uint64_t n, unsigned long long add) {
+  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
+  for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const unsigned long long v = pos[i];
+    if (v != ~0ull) pos[i] = v + add;
+  }
+}
+static int rebase_rowids(void* pos, uint64_t n, uint64_t seg_base, hipStream_t st) {
+  if (!seg_base || !n) return VH_OK;
+  const unsigned grid = (unsigned)std::min<uint64_t>((n + 255) / 256, (uint64_t)g_ctx.num_cu * 8);
+  hipLaunchKernelGGL(rowid_rebase_kernel, dim3(grid), dim3(256), 0, st, static_cast<unsigned long long*>(pos), n, (unsigned long long)(seg_base << 32));
+  HIP_TRY(hipGetLastError());
+  return VH_OK;
+}
+// the dense partial's ROWID state arrays (P.G slots each), after vh_result_device_buffers has merged any private copies into them
+static int rebase_dense_rowids(vh_result* r, uint64_t seg_base, hipStream_t st) {
+  for (int j = 0; j < r->plan.nmetric; ++j)
+    if (r->plan.m[j].slot() == VH_SLOT_ROWID)
+      if (int rc = rebase_rowids(r->plan.m[j].state, r->plan.G, seg_base, st)) return rc;
+  return VH_OK;
 }
 
 // vh_query_agg with the rows kept in device memory (they are exchanged or gathered next). Same re-plan loop.
@@ -367,7 +412,7 @@ static int agree_status(vh_comm* comm, int lrc, const char* what) {
 // 4b of the header comment: key-partitioned exchange of the partial groups (and of the distinct (group, id) pairs of every
 // bitset metric), merge by re-aggregation on the owner, gather on root. `r` is this rank's finalised partial result.
 static int sharded_exchange(vh_table* t, const vh_plan* plan, vh_comm* comm, int root, vh_result* r, const unsigned long long* gflags,
-                            vh_result** out) {
+                            uint64_t seg_base, vh_result** out) {
   const int W = comm->world, R = comm->rank;
   const VhPlanDev& P = r->plan;
   const int nk = P.ngroup, nm = (int)r->user_metric.size();
@@ -384,7 +429,9 @@ static int sharded_exchange(vh_table* t, const vh_plan* plan, vh_comm* comm, int
   char lerr[sizeof(g_err)] = "";
   auto keep = [&](int rc) { if (rc && !lrc) { lrc = rc; snprintf(lerr, sizeof(lerr), "%s", g_err); } return rc; };
   auto own_error = [&]() { return vh_fail(lrc, "%s", lerr); };
-  // ---- 1. regroup by owner, in HBM
+  // ---- 1. regroup by owner, in HBM (storage positions made global first)
+  for (int j = 0; j < nm && !lrc; ++j)
+    if (plan->metrics[j] == VH_COL_ROWID) keep(rebase_rowids(r->d_out_state[r->user_metric[j]], r->ngroups_host, seg_base, st));
   std::vector<uint64_t> goffs(W + 1, 0);
   std::vector<vh_device_buffer> gbufs(ncols);
   int32_t nb = 0;
@@ -421,7 +468,7 @@ static int sharded_exchange(vh_table* t, const vh_plan* plan, vh_comm* comm, int
   for (int i = 0; i < nk; ++i) cd[i] = vh_col_desc{VH_DIM_NUMERIC, (int32_t)P.g[i].type()};
   for (int j = 0; j < nm; ++j) {
     const int col = plan->metrics[j];
-    if (col == VH_COL_ROWID) { keep(vh_fail(VH_E_UNSUPPORTED, "search (VH_COL_ROWID) over a sharded table: storage positions are per rank")); cd[nk + j] = vh_col_desc{VH_METRIC_SUM, VH_U64}; continue; }
+    if (col == VH_COL_ROWID) { cd[nk + j] = vh_col_desc{VH_METRIC_MIN, VH_U64}; continue; }   // global storage positions: the first occurrence wins
     const VhColumn& c = t->cols[col];
     cd[nk + j] = c.kind == VH_METRIC_BITSET ? vh_col_desc{VH_METRIC_BITSET, c.elem} : vh_col_desc{merge_kind_of(c.kind), c.elem};
   }
@@ -583,6 +630,7 @@ static int fused_dense_step(vh_table* t, vh_comm* comm, int root, VhExec* x, vh_
     if (shape_ok && (size_t)nb != agr.dense.size()) shape_ok = false;
     for (int32_t b = 0; shape_ok && b < nb; ++b)
       shape_ok = bufs[b].count == agr.dense[b].count && bufs[b].elem == agr.dense[b].elem && bufs[b].reduce == agr.dense[b].reduce;
+    if (shape_ok && rebase_dense_rowids(r, agr.seg_base, st)) { shape_ok = false; if (!local_err[0]) snprintf(local_err, sizeof(g_err), "%s", g_err); }
   }
   int alloc_rc = VH_OK;
   if (!shape_ok) {
@@ -686,6 +734,7 @@ extern "C" int vh_query_agg_sharded(vh_table* t, const vh_plan* plan, vh_comm* c
       if (lrc && !local_err[0]) snprintf(local_err, sizeof(local_err), "%s", g_err);
       mine.cap_override = rp.cap_override; mine.part_override = rp.part_override;
       mine.force_hash = rp.force_hash; mine.no_part = rp.no_part; mine.fatal = lrc ? 1 : 0;
+      mine.nseg = plan->seg_rows ? plan->nseg : t->nseg;
       std::vector<VhSummary> all(W);
       if (int rc = comm->ops.allgather_host(comm->ops.ctx, &mine, all.data(), sizeof(VhSummary)))
         return rc < 0 ? rc : vh_fail(VH_E_DEVICE, "all-gather of the plan summaries failed (%d)", rc);
@@ -693,8 +742,11 @@ extern "C" int vh_query_agg_sharded(vh_table* t, const vh_plan* plan, vh_comm* c
       merge_summaries(all.data(), W, plan->ngroups, &ag, &rp, &fatal);
       if (fatal) { comm->agreed.clear(); return lrc ? vh_fail(lrc, "%s", local_err) : vh_fail(VH_E_INVALID, "another rank rejected the plan"); }
       if (comm->agreed.size() >= 64) comm->agreed.clear();
-      comm->agreed[sig] = vh_comm::Agreement{ag, plan_local_state(plan, t)};
+      vh_comm::Agreement& agr = comm->agreed[sig] = vh_comm::Agreement{ag, plan_local_state(plan, t)};
+      for (int p = 0; p < R; ++p) agr.seg_base += all[p].nseg;
     }
+    const auto agreed_now = comm->agreed.find(sig);
+    const uint64_t seg_base = agreed_now != comm->agreed.end() ? agreed_now->second.seg_base : 0;
 
     // ---- 2. scan this rank's shard with the agreed plan
     vh_result* r = nullptr;
@@ -771,7 +823,7 @@ extern "C" int vh_query_agg_sharded(vh_table* t, const vh_plan* plan, vh_comm* c
     r->info.retries = attempt;
     if (sparse) {
       vh_result* merged = nullptr;
-      int rc = sharded_exchange(t, plan, comm, root, r, f, &merged);   // the partial is dropped afterwards, its context returns to the pool through the guard
+      int rc = sharded_exchange(t, plan, comm, root, r, f, seg_base, &merged);   // the partial is dropped afterwards, its context returns to the pool through the guard
       if (rc) return rc;
       { std::lock_guard<std::mutex> lk(t->mu); t->groups_seen[r->group_sig] = r->info.ngroups; }
       *out = merged;
@@ -781,6 +833,7 @@ extern "C" int vh_query_agg_sharded(vh_table* t, const vh_plan* plan, vh_comm* c
     vh_device_buffer bufs[VH_MAX_METRIC + 1];
     int32_t nb = 0;
     if (int rc = vh_result_device_buffers(r, bufs, VH_MAX_METRIC + 1, &nb)) return rc;
+    if (int rc = rebase_dense_rowids(r, seg_base, st)) return rc;
     // (RCCL: the state arrays of one query go out as ONE group — one launch, one ring set-up — instead of one collective per array)
     const bool grouped = comm->nccl != nullptr && nb > 1;
     if (grouped) NCCL_TRY(g_rccl.GroupStart());

@@ -164,6 +164,7 @@ struct VhSummary {
   uint64_t rows_to_scan, probe_passed, probe_sampled;
   uint64_t cap_override, part_override;            // re-plan requests of the previous attempt (VhReplan)
   uint32_t force_hash, no_part, fatal, pad;
+  uint64_t nseg;                                   // snapshot segments of this rank (empty ones included): the base of the next ranks' storage positions
 };
 // ... and what every rank plans with instead of its own view, so that all of them build the same table organisation.
 struct VhAgreed {

@@ -1,4 +1,4 @@
-"""Multi-GPU glue for the aggregate path: one process per GPU, segments sharded as contiguous blocks.
+"""Multi-GPU glue for the aggregate, select and search paths: one process per GPU, segments sharded as contiguous blocks.
 
 Everything that matters happens behind the C boundary (include/viya_hip.h, vh_query_agg_sharded): plan agreement, the
 verdict all-reduce, the RCCL reduce of dense partial tables, the key-partitioned exchange + merge of sparse ones. This
@@ -226,3 +226,16 @@ def sharded_query(table, plan, comm: Comm, root: int = 0, copy: bool = True):
         return table._collect(res, plan, copy)
     finally:
         table.lib.vh_result_free(res)
+
+
+def sharded_select(table, filter, cols, comm: Comm, skip: int = 0, limit: int = 0, root: int = 0):
+    """DeviceTable.query_select over a table sharded across comm.world ranks (vh_query_select_sharded): the rows one table
+    holding every rank's segments in rank order would return, through the same skip / limit window, on `root`; the other
+    ranks get no rows. -> ([one numpy array per selected column], RowsInfo with global counters on every rank)."""
+    sp, keep = table._select_plan(filter, cols, skip, limit, None, 0)
+    rows = C.c_void_p()
+    rc = table.lib.vh_query_select_sharded(table.handle, C.byref(sp), comm.handle, int(root), C.byref(rows))
+    if rc != 0:
+        extra = "; transport: %s" % comm.transport.errors[-1] if comm.transport is not None and comm.transport.errors else ""
+        raise capi.VhError(rc, table.lib.vh_last_error().decode("utf-8", "replace") + extra)
+    return table._collect_rows(rows, cols)

@@ -389,6 +389,12 @@ class DeviceTable:
     def query_select(self, filter: Sequence, cols: Sequence[int], skip: int = 0, limit: int = 0,
                      seg_rows: Optional[Sequence[int]] = None, flags: int = 0):
         """-> ([one numpy array per selected column], RowsInfo)."""
+        sp, keep = self._select_plan(filter, cols, skip, limit, seg_rows, flags)
+        rows = C.c_void_p()
+        capi.check(self.lib.vh_query_select(self.handle, C.byref(sp), C.byref(rows)))
+        return self._collect_rows(rows, cols)
+
+    def _select_plan(self, filter, cols, skip, limit, seg_rows, flags):
         p, keep = self._build_plan(AggPlan(filter=filter, seg_rows=seg_rows, flags=flags))
         sp = capi.SelectPlan()
         sp.filter, sp.nfilter, sp.lits, sp.nlits = p.filter, p.nfilter, p.lits, p.nlits
@@ -396,8 +402,10 @@ class DeviceTable:
         ca = (C.c_int32 * max(1, len(cols)))(*[int(c) for c in cols])
         sp.cols, sp.ncols = ca, len(cols)
         sp.skip, sp.limit = int(skip), int(limit)
-        rows = C.c_void_p()
-        capi.check(self.lib.vh_query_select(self.handle, C.byref(sp), C.byref(rows)))
+        return sp, (p, keep, ca)
+
+    def _collect_rows(self, rows, cols):
+        """vh_rows -> ([one numpy array per selected column], RowsInfo); frees the rows."""
         try:
             info = capi.RowsInfo()
             capi.check(self.lib.vh_rows_get_info(rows, C.byref(info)))

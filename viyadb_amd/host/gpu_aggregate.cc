@@ -410,11 +410,22 @@ void PostAggregate(AggregateQuery& query, const Groups& groups, bool having_on_d
 }  // namespace detail
 
 // ------------------------------------------------------------------------------------------------
+namespace detail {
+int NodeRank(void* node_comm) {
+  if (!node_comm) return 0;
+  vh_comm_info_t ci;
+  vh_check(vh_comm_info(static_cast<vh_comm*>(node_comm), &ci));
+  return ci.rank;
+}
+}  // namespace detail
+
 // select: ScanVisitor::Visit(SelectQuery*) (src/codegen/query/scan.cc:75-166). The scan, the ordered
 // compaction and the skip/limit window (including the reference's "break leaves the tuple loop only"
 // rule) run on the GPU (vh_query_select); the rows come back as typed columns and are formatted here.
+// On a joined node (vh_query_select_sharded) the window is the one over all ranks' segments in rank order and the
+// rows arrive on rank 0, which formats and sends them; the other ranks send nothing.
 void GpuSelect(SelectQuery& query, RowOutput& output, QueryStats& stats, std::vector<db::AnyNum> fargs, size_t skip,
-               size_t limit) {
+               size_t limit, void* node_comm) {
   db::Table& table = query.table();
   typedef std::vector<std::string> Row;
   const size_t ncols = query.dimension_cols().size() + query.metric_cols().size();
@@ -453,7 +464,8 @@ void GpuSelect(SelectQuery& query, RowOutput& output, QueryStats& stats, std::ve
     plan.seg_rows = seg_rows.data(); plan.nseg = (uint32_t)seg_rows.size();
     plan.skip = skip; plan.limit = limit;
     vh_rows* rows = nullptr;
-    vh_check(vh_query_select(mir->handle, &plan, &rows));
+    if (node_comm) vh_check(vh_query_select_sharded(mir->handle, &plan, static_cast<vh_comm*>(node_comm), /*root*/0, &rows));
+    else vh_check(vh_query_select(mir->handle, &plan, &rows));
     std::unique_ptr<vh_rows, void (*)(vh_rows*)> guard(rows, vh_rows_free);
     vh_rows_info info;
     vh_check(vh_rows_get_info(rows, &info));
@@ -475,6 +487,7 @@ void GpuSelect(SelectQuery& query, RowOutput& output, QueryStats& stats, std::ve
   }
 
   output.Start();
+  if (detail::NodeRank(node_comm) != 0) { output.Flush(); return; }   // rank 0 answers for the node
   Row row(ncols);
   if (query.header()) {
     for (auto& dc : query.dimension_cols()) row[dc.index()] = dc.dim()->name();
@@ -530,12 +543,20 @@ void GpuSelect(SelectQuery& query, RowOutput& output, QueryStats& stats, std::ve
 // row's storage position (VH_COL_ROWID), groups taken in that order. The term match runs on the decoded values
 // here. Limit: the reference's `break` leaves the tuple loop only — the rest of THAT segment is not scanned (codes
 // first seen there are not inserted) and every later segment is scanned up to its first new matching value; that
-// tail is reproduced with one single-segment query per later segment.
+// tail is reproduced from one single-segment query per later segment.
+// On a joined node the first pass is vh_query_agg_sharded (global storage positions: rank, segment, row) and rank 0
+// decodes and matches. When the query has a limit, every rank learns from rank 0 whether and in which global segment it
+// was reached (one all-gather of 24 bytes per rank), runs the single-segment queries of its own later segments, and the
+// (global position, value) lists go to rank 0 (an all-gather of their lengths, then of the lists padded to the longest:
+// world x 16 bytes x the longest list, a list holding each later segment's distinct passing values), which applies the
+// rule over them in global segment order. The other ranks send no rows.
 void GpuSearch(SearchQuery& query, RowOutput& output, QueryStats& stats, std::vector<db::AnyNum> fargs,
-               const std::string& term, size_t limit) {
+               const std::string& term, size_t limit, void* node_comm) {
   db::Table& table = query.table();
   const db::Dimension* dim = query.dimension();
   const int es = dim->num_type().size();
+  vh_comm* comm = static_cast<vh_comm*>(node_comm);
+  const int rank = detail::NodeRank(node_comm);
   std::vector<std::string> values;
   std::set<uint64_t> codes;   // value bits (the reference's unordered_set<T>)
   auto decode = [&](uint64_t bits) -> std::string {
@@ -558,7 +579,8 @@ void GpuSearch(SearchQuery& query, RowOutput& output, QueryStats& stats, std::ve
     int32_t rowid = VH_COL_ROWID;
 
     // -> (first storage position, value bits) of every distinct value among the passing rows, in storage order
-    auto first_occurrences = [&](const std::vector<uint64_t>& rows, bool count_stats) {
+    // (over all ranks' rows, on rank 0, when `sharded`)
+    auto first_occurrences = [&](const std::vector<uint64_t>& rows, bool count_stats, bool sharded) {
       vh_plan plan;
       memset(&plan, 0, sizeof(plan));
       plan.filter = fb.nodes.data(); plan.nfilter = (int32_t)fb.nodes.size();
@@ -567,7 +589,8 @@ void GpuSearch(SearchQuery& query, RowOutput& output, QueryStats& stats, std::ve
       plan.metrics = &rowid; plan.nmetrics = 1;
       plan.seg_rows = rows.data(); plan.nseg = (uint32_t)rows.size();
       vh_result* res = nullptr;
-      vh_check(vh_query_agg(mir->handle, &plan, &res));
+      if (sharded) vh_check(vh_query_agg_sharded(mir->handle, &plan, comm, /*root*/0, &res));
+      else vh_check(vh_query_agg(mir->handle, &plan, &res));
       std::unique_ptr<vh_result, void (*)(vh_result*)> guard(res, vh_result_free);
       vh_result_info info;
       vh_check(vh_result_get_info(res, &info));
@@ -594,35 +617,92 @@ void GpuSearch(SearchQuery& query, RowOutput& output, QueryStats& stats, std::ve
       std::sort(out.begin(), out.end());
       return out;
     };
+    // the first passes of the segments after `hit` (`base`: this table's first segment in the global order), concatenated
+    auto later_segments = [&](uint64_t hit, uint64_t base) {
+      std::vector<std::pair<uint64_t, uint64_t>> tail;
+      for (uint64_t s = 0; s < seg_rows.size(); ++s) {
+        if (base + s <= hit || !seg_rows[s]) continue;
+        std::vector<uint64_t> only(seg_rows.size(), 0);
+        only[s] = seg_rows[s];
+        for (auto& pv : first_occurrences(only, false, false)) tail.push_back({((base + s) << 32) | (pv.first & 0xFFFFFFFFull), pv.second});
+      }
+      return tail;
+    };
 
     bool limit_hit = false;
     uint64_t hit_segment = 0;
-    for (auto& pv : first_occurrences(seg_rows, true)) {
-      codes.insert(pv.second);
-      const std::string check = decode(pv.second);
-      if (check.find(term) != std::string::npos) {
-        values.push_back(check);
-        if (limit > 0 && values.size() >= limit) { limit_hit = true; hit_segment = pv.first >> 32; break; }
-      }
-    }
-    if (limit_hit) {
-      for (uint64_t s = hit_segment + 1; s < seg_rows.size(); ++s) {
-        if (!seg_rows[s]) continue;
-        std::vector<uint64_t> only(seg_rows.size(), 0);
-        only[s] = seg_rows[s];
-        for (auto& pv : first_occurrences(only, false)) {
-          if (!codes.insert(pv.second).second) continue;
-          const std::string check = decode(pv.second);
-          if (check.find(term) != std::string::npos) { values.push_back(check); break; }   // size >= limit holds
+    std::string first_err;
+    try {
+      for (auto& pv : first_occurrences(seg_rows, true, comm != nullptr)) {
+        codes.insert(pv.second);
+        const std::string check = decode(pv.second);
+        if (check.find(term) != std::string::npos) {
+          values.push_back(check);
+          if (limit > 0 && values.size() >= limit) { limit_hit = true; hit_segment = pv.first >> 32; break; }
         }
+      }
+    } catch (const std::exception& e) {
+      if (!comm || limit == 0) throw;
+      first_err = e.what();      // (the peers are about to wait for rank 0's verdict: they hear of the failure there)
+    }
+    std::vector<std::pair<uint64_t, uint64_t>> tail;
+    if (comm && limit > 0) {
+      // rank 0's verdict + every rank's segment count, then every rank's later segments to rank 0
+      int32_t world = 1;
+      { vh_comm_info_t ci; vh_check(vh_comm_info(comm, &ci)); world = ci.nranks; }
+      uint64_t mine[3] = {first_err.empty() ? (limit_hit ? 1ull : 0ull) : 2ull, hit_segment, (uint64_t)seg_rows.size()};
+      std::vector<uint64_t> all((size_t)world * 3);
+      vh_check(vh_comm_allgather_host(comm, mine, all.data(), sizeof(mine)));
+      for (int p = 0; p < world; ++p)
+        if (all[(size_t)p * 3] == 2) throw std::runtime_error(p == rank ? first_err : "search failed on rank " + std::to_string(p));
+      limit_hit = all[0] == 1;
+      if (limit_hit) {
+        hit_segment = all[1];
+        uint64_t base = 0;
+        for (int p = 0; p < rank; ++p) base += all[(size_t)p * 3 + 2];
+        std::vector<std::pair<uint64_t, uint64_t>> my;
+        std::string err;
+        try { my = later_segments(hit_segment, base); } catch (const std::exception& e) { err = e.what(); }
+        uint64_t cnt[2] = {err.empty() ? 0ull : 1ull, (uint64_t)my.size()};
+        std::vector<uint64_t> cnts((size_t)world * 2);
+        vh_check(vh_comm_allgather_host(comm, cnt, cnts.data(), sizeof(cnt)));
+        uint64_t longest = 0;
+        for (int p = 0; p < world; ++p) {
+          if (cnts[(size_t)p * 2]) throw std::runtime_error(p == rank ? err : "search failed on rank " + std::to_string(p));
+          longest = std::max(longest, cnts[(size_t)p * 2 + 1]);
+        }
+        if (longest) {
+          std::vector<uint64_t> pad(longest * 2, 0), lists((size_t)world * longest * 2);
+          for (size_t i = 0; i < my.size(); ++i) { pad[i * 2] = my[i].first; pad[i * 2 + 1] = my[i].second; }
+          vh_check(vh_comm_allgather_host(comm, pad.data(), lists.data(), longest * 16));
+          for (int p = 0; p < world; ++p)                    // rank order, each rank in segment order: the global storage order
+            for (uint64_t i = 0; i < cnts[(size_t)p * 2 + 1]; ++i)
+              tail.push_back({lists[((size_t)p * longest + i) * 2], lists[((size_t)p * longest + i) * 2 + 1]});
+        }
+      }
+    } else if (limit_hit) {
+      tail = later_segments(hit_segment, 0);
+    }
+    if (rank == 0) {
+      // each later segment: new values go into `codes` up to its first new matching one (size >= limit holds)
+      for (size_t i = 0; i < tail.size();) {
+        const uint64_t seg = tail[i].first >> 32;
+        for (; i < tail.size() && (tail[i].first >> 32) == seg; ++i) {
+          if (!codes.insert(tail[i].second).second) continue;
+          const std::string check = decode(tail[i].second);
+          if (check.find(term) != std::string::npos) { values.push_back(check); break; }
+        }
+        while (i < tail.size() && (tail[i].first >> 32) == seg) ++i;
       }
     }
   }
   stats.aggregated_recs = codes.size();   // scan.cc:298
   output.Start();
-  if (query.header()) output.Send(std::vector<std::string>{dim->name()});
-  output.SendAsCol(values);
-  stats.output_recs = values.size();
+  if (rank == 0) {                         // rank 0 answers for the node
+    if (query.header()) output.Send(std::vector<std::string>{dim->name()});
+    output.SendAsCol(values);
+    stats.output_recs = values.size();
+  }
   output.Flush();
 }
 

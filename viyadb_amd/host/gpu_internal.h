@@ -134,6 +134,8 @@ void FetchGroups(vh_result* res, AggregateQuery& query, Groups& groups, QuerySta
 void AggregateOnMirror(AggregateQuery& query, vh_table* mirror, const std::vector<uint64_t>& seg_rows, bool having_on_device,
                        const std::vector<db::AnyNum>& fargs, const std::vector<db::AnyNum>& hargs, size_t skip, size_t limit,
                        int64_t now, Groups& groups, QueryStats& stats, void* node_comm = nullptr);
+// this process's rank on a joined node (vh_comm_info), 0 without one
+int NodeRank(void* node_comm);
 // PostAggVisitor + SortVisitor (post_agg.cc:26-147, sort.cc:24-75) over fetched groups.
 void PostAggregate(AggregateQuery& query, const Groups& groups, bool having_on_device, const std::vector<db::AnyNum>& hargs,
                    size_t skip, size_t limit, RowOutput& output, QueryStats& stats);

@@ -199,7 +199,7 @@ query::QueryStats Database::Query(const util::Config& conf, query::RowOutput& ou
     query::QueryStats stats;
     std::vector<AnyNum> fargs = query::PackFilterArgs(*table, q.filter());
     stats.compile_time = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    query::GpuSelect(q, output, stats, fargs, q.skip(), q.limit());
+    query::GpuSelect(q, output, stats, fargs, q.skip(), q.limit(), comm_);
     stats.whole_time = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return stats;
   }
@@ -208,7 +208,7 @@ query::QueryStats Database::Query(const util::Config& conf, query::RowOutput& ou
     query::QueryStats stats;
     std::vector<AnyNum> fargs = query::PackFilterArgs(*table, q.filter());
     stats.compile_time = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    query::GpuSearch(q, output, stats, fargs, q.term(), q.limit());
+    query::GpuSearch(q, output, stats, fargs, q.term(), q.limit(), comm_);
     stats.whole_time = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return stats;
   }

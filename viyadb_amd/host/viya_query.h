@@ -198,10 +198,11 @@ void GpuAggregate(AggregateQuery& query, RowOutput& output, QueryStats& stats, s
                   size_t skip, size_t limit, std::vector<db::AnyNum> hargs, int64_t now, void* node_comm = nullptr);
 
 // ... and where viya_query_select / viya_query_search stood (src/query/runner.h:29-31,37-39): same arguments.
+// node_comm: as GpuAggregate's — over all ranks of a joined node, rows on rank 0.
 void GpuSelect(SelectQuery& query, RowOutput& output, QueryStats& stats, std::vector<db::AnyNum> fargs, size_t skip,
-               size_t limit);
+               size_t limit, void* node_comm = nullptr);
 void GpuSearch(SearchQuery& query, RowOutput& output, QueryStats& stats, std::vector<db::AnyNum> fargs,
-               const std::string& term, size_t limit);
+               const std::string& term, size_t limit, void* node_comm = nullptr);
 
 }  // namespace query
 
@@ -215,9 +216,10 @@ public:
   Table* GetTable(const std::string& name);
   query::QueryStats Query(const util::Config& query_conf, query::RowOutput& output, int64_t now = -1);
   // One node, one process per GPU, every process holding ITS segments of the tables (same descriptors and the same
-  // dictionary codes everywhere): after JoinNode, aggregate queries run over all ranks' rows — the same Query() on every
-  // rank, rows delivered on rank 0 (vh_query_agg_sharded; replaces the HTTP + TSV merge of src/cluster/query/agg_runner.cc:83-140
-  // inside a node). `comm` is a vh_comm* (include/viya_hip.h: vh_comm_init / vh_comm_init_custom), owned by the caller.
+  // dictionary codes everywhere): after JoinNode, aggregate, select and search queries run over all ranks' rows — the same
+  // Query() on every rank, rows delivered on rank 0, the other ranks sending none (vh_query_agg_sharded / vh_query_select_sharded;
+  // replaces the HTTP + TSV merge of src/cluster/query/agg_runner.cc:83-140 and the search runner inside a node). The global
+  // storage order is rank, then segment: ranks hold contiguous blocks of the table's segments in rank order. `comm` is a vh_comm* (include/viya_hip.h: vh_comm_init / vh_comm_init_custom), owned by the caller.
   void JoinNode(void* comm) { comm_ = comm; }
   void* node_comm() const { return comm_; }
   void Load(const std::string& table, const std::vector<std::vector<std::string>>& rows, int64_t now = -1);
