@@ -12,6 +12,11 @@ configuration the metric (rows/s + achieved HBM GB/s) is quoted on.  N>1 runs co
 "C4": the SAME 1 B rows sharded as contiguous blocks of segments across the ranks (strong
 scaling: total work fixed), with an RCCL reduce of the per-GPU partial aggregates.
 
+A plain run does what the headline needs and nothing else: it generates and prepares the table, runs the warm-up steps, times the
+steps, writes --dump-outputs if asked and prints the line (roofline included: it is computed from the timed steps and the committed
+PMC summaries, no run of its own). --full adds everything else the benchmark measures or checks, as it always has: the parity gate
+before the warm-up, and at N=1 after the timed steps the reference-layout leg, the unprepared-caller leg and both CPU baselines.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -261,17 +266,19 @@ def main():
     ap.add_argument("--workload", default="C3")
     ap.add_argument("--segments", type=int, default=0, help="total segments (default: 1000 for C3, 100 for C2, 10 for C1)")
     ap.add_argument("--segment-rows", type=int, default=1_000_000)
-    ap.add_argument("--cpu-segments", type=int, default=100, help="CPU baseline sample: this many segments of the same workload")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--cpu-parallel", action="store_true", help="(default at N=1 now) also time the courtesy all-cores CPU baseline (adds ~20 s)")
-    ap.add_argument("--no-cpu-parallel", action="store_true", help="skip the courtesy all-cores CPU baseline")
+    ap.add_argument("--full", action="store_true", help="also run what the headline does not need: the parity gate, and at N=1 the reference-layout "
+                                                         "and unprepared-caller legs and both CPU baselines (each --no-* below leaves one out again)")
+    ap.add_argument("--cpu-segments", type=int, default=100, help="CPU baseline sample (--full): this many segments of the same workload")
+    ap.add_argument("--no-cpu", action="store_true", help="skip both CPU baselines of --full")
+    ap.add_argument("--cpu-parallel", action="store_true", help="(default of --full at N=1) also time the courtesy all-cores CPU baseline (adds ~20 s)")
+    ap.add_argument("--no-cpu-parallel", action="store_true", help="skip the courtesy all-cores CPU baseline of --full")
     ap.add_argument("--flags", type=int, default=0)
     ap.add_argument("--no-pack", action="store_true", help="ablation: no payload projection (survivors gather from the column arenas)")
-    ap.add_argument("--no-check", action="store_true", help="skip the parity gate (profiling runs)")
+    ap.add_argument("--no-check", action="store_true", help="skip the parity gate of --full (profiling runs)")
     ap.add_argument("--no-predpack", action="store_true", help="ablation: narrow copies of the predicate columns (round 4's layout) instead of the bit-packed predicate projection")
     ap.add_argument("--no-warm", action="store_true", help="no vh_table_prepare: the first queries pay the first-use costs")
-    ap.add_argument("--no-reference-layout", action="store_true", help="skip the arena-only leg (profiling runs)")
-    ap.add_argument("--no-unprepared", action="store_true", help="skip the unprepared-caller leg (a second table: profiling runs)")
+    ap.add_argument("--no-reference-layout", action="store_true", help="skip the arena-only leg of --full (profiling runs)")
+    ap.add_argument("--no-unprepared", action="store_true", help="skip the unprepared-caller leg of --full (a second table: profiling runs)")
     ap.add_argument("--rendezvous-only", action="store_true", help="launch the ranks, meet over gloo, print who came, stop (the launcher's own test: needs no GPU)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the last step's result arrays to DIR/<name>.npy (float64, groups sorted by key, at most 64 MB)")
     args = ap.parse_args()
@@ -357,7 +364,7 @@ def main():
     t_pack = time.time() - t_pack
 
     checked = None
-    if not args.no_check:
+    if args.full and not args.no_check:
         checked = parity_gate(table, w, plan, my_segments, executor)   # every rank checks its own shard; raises on any difference
 
     def step():
@@ -392,7 +399,7 @@ def main():
     # (VH_PLAN_NO_PACK | VH_PLAN_NO_NARROW) — timed in the same run, after the headline loop: what the kernels do with the
     # bytes the reference's Segment holds, so that rounds stay comparable whatever the derived layouts buy.
     ref_layout = None
-    if world == 1 and not args.no_pack and not args.no_reference_layout:
+    if args.full and world == 1 and not args.no_pack and not args.no_reference_layout:
         rplan = executor.AggPlan(filter=plan.filter, groups=plan.groups, metrics=plan.metrics, groups_hint=plan.groups_hint,
                                  flags=args.flags | capi.PLAN_NO_PACK | capi.PLAN_NO_NARROW)
         table.prepare(rplan)
@@ -414,7 +421,7 @@ def main():
     # reference's layout, and the library builds the derived layouts unasked once the shape has been seen VH_AUTO_PACK / VH_AUTO_NARROW (3) times:
     # what every one of those queries costs is in the line, next to what the prepared table's cost.
     unprepared = None
-    if world == 1 and not args.no_pack and not args.no_unprepared and not args.no_warm:
+    if args.full and world == 1 and not args.no_pack and not args.no_unprepared and not args.no_warm:
         try:
             t2 = synth.create_device_table(w, my_segments, w.segment_rows, row_base=seg_lo * w.segment_rows)
             torch.cuda.synchronize()
@@ -470,6 +477,7 @@ def main():
             "scaling": "strong",
             "degraded": bool(degraded),       # true = N > 1 but the data plane was NOT RCCL over distinct GPUs (see "rccl")
             "rccl": rccl_info,
+            "full": bool(args.full),          # false = the headline alone: no parity gate, no reference_layout / unprepared / CPU legs
             "parity_checked": bool(checked), "parity": checked,
             "vs_baseline": None, "dtype": "u32 predicates (compared as bit fields of a packed word / u8 / u16 where such a copy exists) / int64 + u32 integer sums", "data": "synthetic",
             "config": {"workload": "%s: %s" % (w.name if world == 1 else w.name + " sharded (C4)", w.description),
@@ -531,7 +539,7 @@ def main():
                 "roofline": {"achieved": rcred / (rkms * 1e-3) / 1e9, "frac": rcred / (rkms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": rtraffic, "traffic_write": rwrite,
                              "traffic_source": rsrc, "traffic_refused": rwhy,
                              "bref_over_t_GBs": rl.algorithmic_bytes / (rkms * 1e-3) / 1e9}}
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             twin_state = None
             try:
                 # (sparse groups: the twin's unordered_map grows with the sample — C5's 5 segments are ~4.5 M groups, ~10-20 s of CPU for the 8 runs)

@@ -328,14 +328,14 @@ def test_cxx_database_queries_all_ranks_rows(tmp_path):
 
 
 def test_bench_from_a_plain_shell_two_ranks_one_gpu():
-    """`python bench.py --gpus 2 …` with nothing in the environment: the launcher re-executes itself under
+    """`python bench.py --gpus 2 --full …` with nothing in the environment: the launcher re-executes itself under
     torch.distributed.run; with one GPU here the two ranks share it over the callback transport, and the line must SAY so —
-    "rccl".transport = "gloo-fallback", "degraded" true — with the parity gate run on both shards."""
+    "rccl".transport = "gloo-fallback", "degraded" true — with the parity gate (a --full leg) run on both shards."""
     import json
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["VH_BENCH_BACKEND"] = "gloo"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--segments", "4", "--segment-rows", "20000",
-                        "--steps", "3", "--warmup", "1"], env=env, capture_output=True, text=True, timeout=900)
+                        "--steps", "3", "--warmup", "1", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
