@@ -147,13 +147,15 @@ def test_projection_follows_segment_syncs():
         dt.close()
 
 
-def test_derived_layouts_moved_to_other_memory():
+def test_derived_layouts_moved_to_other_memory(monkeypatch):
     """vh_table_relocate (what vh_table_prepare does per candidate place): projections and predicate planes copied to fresh allocations, pointers
-    swapped — the same groups before and after, for each kind and both, a sync after the move still lands in the moved layouts, and a prepare
-    (whose placement moves them again where the scan is long enough) changes nothing either."""
+    swapped — the same groups before and after, for each kind and both, a sync after the move still lands in the moved layouts (segment 1 is
+    written again with OTHER rows: a layout that missed it would answer the old data), and a prepare whose placement is forced to try three
+    places (VH_TEST_PLACE_CANDIDATES: the table is far below the scan time placement otherwise waits for) changes nothing either."""
     from viyadb_amd import synth
     from viyadb_amd.executor import AggPlan
     from tests.parity import build_oracle_table
+    from tests.conftest import JIT_OFF          # (predicate planes are read by the compiled kernels alone)
     w = synth.c3(segment_rows=250_000)
     dt = synth.create_device_table(w, 4, 249_991)
     try:
@@ -162,16 +164,29 @@ def test_derived_layouts_moved_to_other_memory():
         dt.pack(dt.gather_columns(plan)); dt.predpack(dt.filter_columns(plan))
         r = dt.query_agg(plan)
         compare(r, want, "before the move")
-        assert r.packed and r.predpack
+        assert r.packed and (r.predpack or JIT_OFF)
         for which in (1, 2, 0, 2, 1):
             dt.relocate(which)
             r = dt.query_agg(plan)
             compare(r, want, f"after relocate({which})")
-            assert r.packed and r.predpack
-        dt.generate(1, 1, 249_991, 249_991, [c.gen for c in w.columns], 42)      # (segment 1 written again with the same rows: the journalled ranges are re-derived into the MOVED layouts)
-        compare(dt.query_agg(plan), want, "after a sync behind the move")
+            assert r.packed and (r.predpack or JIT_OFF)
+        # segment 1 written again with other rows (a seed that differs in a HIGH bit: one differing in low bits only permutes the same rows):
+        # the journalled ranges are re-derived into the MOVED layouts
+        seed2 = 42 ^ (1 << 40)
+        dt.generate(1, 1, 249_991, 249_991, [c.gen for c in w.columns], seed2)
+        tab = build_oracle_table(w, 4, 249_991)
+        tab.segments[1] = build_oracle_table(w, 1, 249_991, row_base=249_991, seed=seed2).segments[0]
+        want2 = vo.scan_aggregate(vo.parse_query(tab, w.query), now=getattr(w, "now", NOW))
+        assert want2.passed_recs != want.passed_recs
+        r = dt.query_agg(plan)
+        compare(r, want2, "after a sync behind the move")
+        assert r.packed and (r.predpack or JIT_OFF)
+        monkeypatch.setenv("VH_TEST_PLACE_CANDIDATES", "3")
+        monkeypatch.setenv("VH_TEST_PLACE_VERDICT", "alternate")       # (kept, given back, kept: both ways of settling a candidate)
         dt.warm(plan)
-        compare(dt.query_agg(plan), want, "after vh_table_prepare")
+        r = dt.query_agg(plan)
+        compare(r, want2, "after vh_table_prepare")
+        assert r.packed and (r.predpack or JIT_OFF)
     finally:
         dt.close()
 

@@ -270,7 +270,13 @@ CONCURRENT_DRIVER = textwrap.dedent(r"""
         --n;
       }
     }
-    static void one_query(int tid, int qid, std::string& log) {
+    static size_t rows_now() {                    // rows the table holds now, over every segment
+      size_t r = 0;
+      const uint32_t n = nseg.load();
+      for (uint32_t i = 0; i < n; ++i) r += segs[i]->size.load(std::memory_order_acquire);
+      return r;
+    }
+    static size_t one_query(int tid, int qid, std::string& log) {      // -> rows of the size() snapshot the call took
       const uint64_t v0 = version.load();
       viya::shim::Session* s = viya::shim::Open(&table_identity, kTable, kQuery[qid]);
       const uint32_t n = nseg.load();
@@ -311,12 +317,15 @@ CONCURRENT_DRIVER = textwrap.dedent(r"""
       log += head;
       for (size_t z : sizes) log += " " + std::to_string(z);
       log += "\n" + rows.text + "end\n";
+      size_t total = 0;
+      for (size_t z : sizes) total += z;
+      return total;
     }
     int main() {
       for (int i = 0; i < 6; ++i) { segs[i] = new Seg(); nseg.store(i + 1); append(i < 5 ? CAP : 1500); }
       std::string warm;
       one_query(-1, 0, warm); one_query(-1, 1, warm);        // everything that exists so far is mirrored before the writer starts
-      std::atomic<bool> stop{false};
+      std::atomic<bool> stop{false}, writer_done{false};
       struct Op { uint32_t seg, row; uint32_t id; };
       std::vector<Op> ops;
       std::thread writer([&] {
@@ -336,10 +345,25 @@ CONCURRENT_DRIVER = textwrap.dedent(r"""
           version.fetch_add(1);
           std::this_thread::sleep_for(std::chrono::microseconds(300));
         }
+        writer_done.store(true);
       });
       std::vector<std::thread> readers;
       std::vector<std::string> logs(4);
-      for (int t = 0; t < 4; ++t) readers.emplace_back([&, t] { for (int it = 0; it < 12; ++it) one_query(t, (t + it) % 2, logs[t]); });
+      // every call of a reader takes a snapshot of its own: one that saw no append since its previous call waits for the next (the writer
+      // sleeps 300 us per round, and a quick reader would otherwise take the same size() snapshot several times over), then starts at a
+      // point of the writer's round of its own (started right behind an append, a call would end before the writer's next update)
+      for (int t = 0; t < 4; ++t) readers.emplace_back([&, t] {
+        size_t seen = 0;
+        uint32_t phase = 2654435761u * (uint32_t)(t + 1);
+        for (int it = 0; it < 12; ++it) {
+          if (it && rows_now() <= seen) {
+            while (rows_now() <= seen && !writer_done.load()) std::this_thread::sleep_for(std::chrono::microseconds(20));
+            phase = phase * 1664525u + 1013904223u;
+            std::this_thread::sleep_for(std::chrono::microseconds((phase >> 8) % 300));
+          }
+          seen = one_query(t, (t + it) % 2, logs[t]);
+        }
+      });
       for (auto& r : readers) r.join();
       stop.store(true);
       writer.join();

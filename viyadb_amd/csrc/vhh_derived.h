@@ -256,6 +256,7 @@ static int table_pack_locked(vh_table* t, const int32_t* cols, int32_t ncols, bo
     pk->cols = ord; pk->off = off; pk->width = width; pk->rec_bytes = rec; pk->automatic = automatic; pk->compressed = compress;
     if (bits) { pk->bits = true; pk->bitoff = bitoff; pk->bitw = bitw; pk->rec_bytes = rec = rec_bits; for (auto& o : pk->off) o = 0; }
     pk->stride = (t->segment_rows + 255) / 256 * 256 * (uint64_t)rec;
+    pk->serial = ++t->layout_serial;
     VhPack* raw = pk.get();
     t->packs.push_back(std::move(pk));
     const int rc = pack_refresh(t, raw, 0, t->nseg);
@@ -470,6 +471,7 @@ static int table_predpack_locked(vh_table* t, const std::vector<int>& cols, bool
     if (pp->bytes_per_row() >= plain) return VH_OK;
   }
   pp->automatic = automatic;
+  pp->serial = ++t->layout_serial;
   VhPredPack* raw = pp.get();
   t->predpacks.push_back(std::move(pp));
   const int rc = predpack_refresh(t, raw);
@@ -525,7 +527,9 @@ extern "C" int vh_table_pack(vh_table* t, const int32_t* cols, int32_t ncols) { 
 // 2 MB-aligned virtual addresses, so it is nothing a process can compute). What a process can do is try: derived_move copies every layout `which`
 // names (1: projections, 2: predicate planes) to FRESH allocations while the old ones are still held — so that the new ones are other pages —
 // and swaps the pointers (kernels take addresses as arguments); the caller measures and keeps or gives back (vh_table_prepare, vh_table_relocate).
-struct VhMoved { int kind; void* owner; int plane; char* old_ptr; char* new_ptr; size_t bytes; };      // kind 1: VhPack* owner, 2: VhPredPack* owner
+struct VhMoved {       // kind 1: a projection's records, 2: plane `plane` of a predicate projection; `serial` and `applied_epoch` of the layout at the move
+  int kind; uint64_t serial, applied_epoch; int plane; char* old_ptr; char* new_ptr; size_t bytes;
+};
 static size_t derived_bytes(const vh_table* t, uint32_t which) {
   size_t b = 0;
   if (which & 1u) for (auto& pk : t->packs) if (pk->base) b += (size_t)pk->cap_seg * pk->stride + 256;
@@ -535,33 +539,41 @@ static size_t derived_bytes(const vh_table* t, uint32_t which) {
 static int derived_move(vh_table* t, uint32_t which, std::vector<VhMoved>* moved) {      // (t->mu held)
   table_quiesce(t);
   HIP_TRY(hipStreamSynchronize(g_ctx.stream)); derived_waited(t);
-  auto move = [&](int kind, void* owner, int plane, char*& base, size_t bytes, const char* what) -> int {
+  auto move = [&](int kind, uint64_t serial, uint64_t applied_epoch, int plane, char*& base, size_t bytes, const char* what) -> int {
     char* nb = nullptr;
     if (hipMalloc(&nb, bytes) != hipSuccess) { (void)hipGetLastError(); return VH_E_NOMEM; }
     trace_alloc(what, nb, bytes);
     if (hipMemcpyAsync(nb, base, bytes, hipMemcpyDeviceToDevice, g_ctx.stream) != hipSuccess) { (void)hipFree(nb); return vh_fail(VH_E_DEVICE, "moving a derived layout"); }
-    moved->push_back(VhMoved{kind, owner, plane, base, nb, bytes});
+    moved->push_back(VhMoved{kind, serial, applied_epoch, plane, base, nb, bytes});
     base = nb;
     return VH_OK;
   };
   int rc = VH_OK;
-  if (which & 1u) for (auto& pk : t->packs) if (pk->base && !rc) rc = move(1, pk.get(), 0, pk->base, (size_t)pk->cap_seg * pk->stride + 256, "projection");
-  if (which & 2u) for (auto& pp : t->predpacks) for (int q = 0; q < pp->nplanes && !rc; ++q) if (pp->pbase[q]) rc = move(2, pp.get(), q, pp->pbase[q], (size_t)pp->cap_seg * pp->pstride[q] + 256, "predicate plane");
+  if (which & 1u) for (auto& pk : t->packs) if (pk->base && !rc) rc = move(1, pk->serial, pk->applied_epoch, 0, pk->base, (size_t)pk->cap_seg * pk->stride + 256, "projection");
+  if (which & 2u) for (auto& pp : t->predpacks) for (int q = 0; q < pp->nplanes && !rc; ++q) if (pp->pbase[q]) rc = move(2, pp->serial, pp->applied_epoch, q, pp->pbase[q], (size_t)pp->cap_seg * pp->pstride[q] + 256, "predicate plane");
   HIP_TRY(hipStreamSynchronize(g_ctx.stream));
   return rc == VH_E_NOMEM ? VH_OK : rc;          // (out of memory: what could be moved was moved)
 }
 // The buffers a move left behind (keep = true), or the ones it made after the layouts were pointed back at the old ones (keep = false), into
 // `out` — still allocated: whoever tries several places frees them all at the end, so that no candidate lands on a place already tried.
+// The caller dropped t->mu between the move and this call (vh_table_prepare measures with queries of its own), so the layout may have changed:
+// - it is found by its serial, not by its address: a projection dropped and rebuilt meanwhile (a synced value outgrew it) can come back at the
+//   same host address AND be given the device address just freed — its new widths would then be paired with the old buffer;
+// - it must still hold new_ptr: another prepare or relocate may have moved it on (then new_ptr is that one's old buffer, settled by that one);
+// - it goes back to old_ptr only if nothing was refreshed since the move: a sync that landed meanwhile was re-derived into new_ptr alone, and
+//   the old buffer would be stale under an applied_epoch that says current. Then the new buffer stays, whatever the verdict.
+// Exactly one of the two buffers is ours to free: new_ptr where the layout goes back, old_ptr otherwise — where the layout was dropped, grew
+// or moved on, whoever replaced new_ptr owns it (and freed it, or will settle it).
 static void derived_settle(vh_table* t, std::vector<VhMoved>& moved, bool keep, std::vector<char*>* out) {      // (t->mu held)
   table_quiesce(t);
   (void)hipStreamSynchronize(g_ctx.stream);
   for (const VhMoved& m : moved) {
-    char** slot = nullptr;      // the layout may be gone by now (a sync voided it): then both buffers are somebody else's or nobody's — only ours is freed
-    if (m.kind == 1) { for (auto& pk : t->packs) if (pk.get() == m.owner && pk->base == m.new_ptr) slot = &pk->base; }
-    else { for (auto& pp : t->predpacks) if (pp.get() == m.owner && pp->pbase[m.plane] == m.new_ptr) slot = &pp->pbase[m.plane]; }
-    if (!slot) { out->push_back(m.old_ptr); continue; }      // (the layout was dropped or moved again with new_ptr freed by its owner: the old buffer is ours to free)
-    if (keep) out->push_back(m.old_ptr);
-    else { *slot = m.old_ptr; out->push_back(m.new_ptr); }
+    char** slot = nullptr;
+    uint64_t applied = 0;
+    if (m.kind == 1) { for (auto& pk : t->packs) if (pk->serial == m.serial && pk->base == m.new_ptr) { slot = &pk->base; applied = pk->applied_epoch; } }
+    else { for (auto& pp : t->predpacks) if (pp->serial == m.serial && pp->pbase[m.plane] == m.new_ptr) { slot = &pp->pbase[m.plane]; applied = pp->applied_epoch; } }
+    if (slot && !keep && applied == m.applied_epoch) { *slot = m.old_ptr; out->push_back(m.new_ptr); }
+    else out->push_back(m.old_ptr);
   }
   moved.clear();
 }

@@ -532,7 +532,17 @@ static bool placing_now() { return g_placing; }
 static int place_layouts(vh_table* t, const vh_plan* plan, vh_result_info* info_out, double budget_ms) {
   const auto t_begin = std::chrono::steady_clock::now();
   struct Guard { Guard() { g_placing = true; } ~Guard() { g_placing = false; } } guard;
-  const int cand = knobs().prepare_place;
+  // test hooks (test_env): VH_TEST_PLACE_CANDIDATES=n tries exactly n places whatever the scan takes and however long they take (the free-memory
+  // guard stays); VH_TEST_PLACE_VERDICT=keep|reject|alternate decides each candidate instead of its timing (noise on a small table);
+  // VH_TEST_PLACE_WAIT_SYNC=1 holds every candidate, after its move and before its measuring queries, until a sync of another thread has landed
+  // (outside t->mu): each window between derived_move and derived_settle then sees one — or the prepare fails, so no test passes without the race
+  const char* env_cand = test_env("VH_TEST_PLACE_CANDIDATES");
+  const char* env_verdict = test_env("VH_TEST_PLACE_VERDICT");
+  const bool wait_sync = test_env("VH_TEST_PLACE_WAIT_SYNC") != nullptr;
+  const bool forced = env_cand != nullptr;
+  const int cand = forced ? std::max(0, atoi(env_cand)) : knobs().prepare_place;
+  const int verdict = !env_verdict ? -1 : !strcmp(env_verdict, "keep") ? 1 : !strcmp(env_verdict, "reject") ? 0 : !strcmp(env_verdict, "alternate") ? 2 : -1;
+  if (env_verdict && verdict < 0) return vh_fail(VH_E_INVALID, "VH_TEST_PLACE_VERDICT=%s: keep, reject or alternate", env_verdict);
   auto measure = [&](float* ms) -> int {
     *ms = 1e30f;
     for (int i = 0; i < 3; ++i) {
@@ -548,17 +558,19 @@ static int place_layouts(vh_table* t, const vh_plan* plan, vh_result_info* info_
     float best = 0;
     if (int rc = measure(&best)) return rc;
     std::vector<char*> held;
-    for (int k = 0; k < cand && best >= 0.3f; ++k) {
+    for (int k = 0; k < cand && (forced || best >= 0.3f); ++k) {
       // (a fresh allocation of a few GB takes the driver 2 ms or 400, depending on what the memory was last used for: the candidates stop when the
       // budget is spent — a second inside vh_table_prepare, 0.3 s inside a query that places layouts nobody prepared)
-      if (std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count() > budget_ms) break;
+      if (!forced && std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count() > budget_ms) break;
       std::vector<VhMoved> moved;
       // (both layouts, then the planes alone, then the projections alone, and again: what decides is how the two lie to each other as much as
       // where either lies; a spacer of 1-3 GB in front, because neighbouring allocations tend to behave alike)
       const uint32_t which = k % 3 == 0 ? 3u : k % 3 == 1 ? 2u : 1u;
       const auto tk0 = std::chrono::steady_clock::now();
+      uint64_t moved_epoch = 0;
       {
         std::lock_guard<std::mutex> lk(t->mu);
+        moved_epoch = t->sync_epoch;
         size_t free_b = 0, total_b = 0;
         const size_t spacer = (size_t)(1 + k % 3) << 30;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < derived_bytes(t, which) + spacer + total_b / 4) break;
@@ -568,11 +580,23 @@ static int place_layouts(vh_table* t, const vh_plan* plan, vh_result_info* info_
       }
       if (knobs().times) fprintf(stderr, "vh prepare: candidate %d: spacer + allocations + copies in %.1f ms\n", k, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tk0).count());
       if (moved.empty()) break;
+      if (wait_sync) {
+        const auto tw0 = std::chrono::steady_clock::now();
+        for (;;) {
+          { std::lock_guard<std::mutex> lk(t->mu); if (t->sync_epoch > moved_epoch) break; }
+          if (std::chrono::steady_clock::now() - tw0 > std::chrono::seconds(10)) {
+            { std::lock_guard<std::mutex> lk(t->mu); derived_settle(t, moved, false, &held); }
+            for (char* p : held) (void)hipFree(p);
+            return vh_fail(VH_E_INVALID, "vh_table_prepare: VH_TEST_PLACE_WAIT_SYNC: no sync landed within 10 s of candidate %d's move", k);
+          }
+          std::this_thread::sleep_for(std::chrono::microseconds(200));
+        }
+      }
       float ms = 0;
       const auto tm0 = std::chrono::steady_clock::now();
       const int mrc = measure(&ms);
       if (knobs().times) fprintf(stderr, "vh prepare: candidate %d: three queries in %.1f ms\n", k, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tm0).count());
-      const bool keep = !mrc && ms < best * 0.985f;
+      const bool keep = !mrc && (verdict < 0 ? ms < best * 0.985f : verdict == 2 ? k % 2 == 0 : verdict == 1);
       if (knobs().times) fprintf(stderr, "vh prepare: %s at another place: %.4f ms against %.4f ms (%s)\n", which == 3u ? "projections and predicate planes" : which == 2u ? "predicate planes" : "projections", ms, best, keep ? "kept" : "given back");
       { std::lock_guard<std::mutex> lk(t->mu); derived_settle(t, moved, keep, &held); }
       if (mrc) { for (char* p : held) (void)hipFree(p); return mrc; }

@@ -54,6 +54,7 @@ struct VhPack {
   char* base = nullptr; uint64_t stride = 0; uint32_t cap_seg = 0;
   std::vector<uint64_t> seg_mod;    // value of vh_table::seg_mod[s] the segment was packed at (0: never)
   uint64_t applied_epoch = 0;       // every change of the table's journal up to this epoch is in the records
+  uint64_t serial = 0;              // vh_table::layout_serial when it was built: which projection this is (derived_settle; addresses get reused)
   bool automatic = false;
   int col_index(int col) const { for (size_t i = 0; i < cols.size(); ++i) if (cols[i] == col) return (int)i; return -1; }
 };
@@ -78,6 +79,7 @@ struct VhPredPack {
   char* pbase[4] = {}; uint64_t pstride[4] = {};
   uint32_t cap_seg = 0;
   std::vector<uint64_t> seg_mod; uint64_t applied_epoch = 0;
+  uint64_t serial = 0;               // vh_table::layout_serial when it was built (derived_settle)
   bool automatic = false;
   // BIT-SLICED form: one plane per BIT of the word, one bit per row (32 rows = one 4-byte word of a plane); pbase[0] is the whole arena,
   // pstride[0] the bytes between segments, `pitch` the bytes between planes inside a segment; `bits` planes.
@@ -117,6 +119,7 @@ struct vh_table {
   std::vector<std::unique_ptr<VhPack>> packs;
   std::vector<std::unique_ptr<VhNarrow>> narrows;
   std::vector<std::unique_ptr<VhPredPack>> predpacks;
+  uint64_t layout_serial = 0;                             // the last serial given to a projection or predicate projection built
   std::map<std::string, uint32_t> ppred_seen;             // predicate column set -> compiled-kernel queries that filtered on it (automatic predicate projections)
   std::map<int, uint32_t> pred_seen;                     // column -> queries that filtered on it (automatic narrow copies)
   std::vector<uint64_t> seg_mod;                          // sync_epoch of the last change to a segment's columns
@@ -263,7 +266,9 @@ static void table_quiesce(vh_table* t) {
 static void table_note_change(vh_table* t, uint32_t seg, uint64_t first, uint64_t last, bool new_epoch = true) {
   if (new_epoch) ++t->sync_epoch;
   t->seg_mod[seg] = t->sync_epoch;
-  if (t->journal.size() >= (1u << 18)) {          // keep the newer half; layouts older than the floor fall back to whole segments
+  const char* cap_env = test_env("VH_TEST_JOURNAL_CAP");       // (tests: a few hundred small syncs push a layout behind the floor)
+  const size_t cap = cap_env && atoi(cap_env) >= 2 ? (size_t)atoi(cap_env) : (1u << 18);
+  if (t->journal.size() >= cap) {                 // keep the newer half; layouts older than the floor fall back to whole segments
     const size_t drop = t->journal.size() / 2;
     t->journal_floor = t->journal[drop - 1].epoch;
     t->journal.erase(t->journal.begin(), t->journal.begin() + (long)drop);

@@ -28,6 +28,7 @@
 #include <mutex>
 #include <set>
 #include <string>
+#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -65,7 +66,9 @@ static std::mutex g_mu;
 // one. They exist for measurements and tests: defaults are what every reported number was taken with (DESIGN.md "Knobs"). The
 // VH_TEST_* / VH_POISON / VH_PART_TABLE_KB / VH_NO_HP_PACK / VH_NO_OFF32 hooks are the exception — tests switch them between two
 // queries of one process — and go through test_env(): one gate (VH_TEST_HOOKS, read once; tests/conftest.py sets it) in front of them, so
-// that a serving process never walks its environment on the query path.
+// that a serving process never walks its environment on the query path. Among them: VH_TEST_PLACE_CANDIDATES / VH_TEST_PLACE_VERDICT /
+// VH_TEST_PLACE_WAIT_SYNC make vh_table_prepare's placement of the derived layouts deterministic (vhh_finalize.h, place_layouts), and
+// VH_TEST_JOURNAL_CAP replaces the 2^18 entries at which the table's journal drops its older half (vhh_table.h, table_note_change).
 static const char* test_env(const char* name) {
   static const bool hooks = getenv("VH_TEST_HOOKS") != nullptr;
   return hooks ? getenv(name) : nullptr;
