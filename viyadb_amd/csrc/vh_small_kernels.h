@@ -2,6 +2,7 @@
 // segment stats, bandwidth probe. Included by viya_hip.hip only (non-template __global__ symbols).
 #pragma once
 #include "vh_kernels.h"
+#include "vh_topk_key.h"
 
 // ----------------------------------------------------------- table finalisation
 // Combine the per-XCD private copies of a dense table into copy 0 (they were only ever
@@ -289,50 +290,10 @@ __device__ __forceinline__ void vh_store_sized(void* base, uint32_t esize, uint6
 }
 
 // ------------------------------------------------- device top-N over emitted groups
-// `sort` + `limit` on a numeric column: instead of shipping every group to the host to be formatted and string-
-// sorted (src/codegen/query/post_agg.cc:50-147, sort.cc:24-75 — what dominates at ~10 M groups), the device keeps
-// a SUPERSET of the rows the reference would return: every group whose primary sort key is at least the K-th
-// best (K = skip + limit), ties and a rounding slack included. The host then runs the reference's exact string
-// comparators on those few rows. Keys only have to be MONOTONE in the reference's order, not exact:
-//   INTEGER columns compare as strings by (length, lexicographic) (src/util/string.h:28-49): ascending order is
-//     0..9, -1..-9, 10..99, -10..-99, ...  ->  key = class(digits, sign) : |v|
-//   FLOAT columns compare stod("%.15g" / "%g" text): numeric order up to the rounding of the formatter, which the
-//     slack covers.
-enum { VH_TOPK_INT = 0, VH_TOPK_FLOAT = 1 };
+// What the key and the slack must guarantee, and why they do: vh_topk_key.h (plain C++, also compiled and checked on the host).
+static_assert(VHK_U8 == VH_U8 && VHK_U16 == VH_U16 && VHK_U32 == VH_U32 && VHK_U64 == VH_U64 && VHK_I8 == VH_I8 && VHK_I16 == VH_I16 &&
+              VHK_I32 == VH_I32 && VHK_I64 == VH_I64 && VHK_F32 == VH_F32 && VHK_F64 == VH_F64, "vh_topk_key.h restates enum vh_elem");
 struct VhTopkState { unsigned long long k_remaining, prefix, out_count, pad; unsigned long long hist[256]; };
-
-__device__ __forceinline__ uint64_t vh_topk_key(int cls, int elem, uint64_t bits) {
-  if (cls == VH_TOPK_FLOAT) {
-    if (elem == VH_F32) {
-      uint32_t b = (uint32_t)bits;
-      if (b == 0x80000000u) b = 0;                                  // "-0" and "0" compare equal through stod
-      b = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-      return (uint64_t)b << 32;
-    }
-    uint64_t b = bits;
-    if (b == 0x8000000000000000ull) b = 0;
-    return (b & 0x8000000000000000ull) ? ~b : (b | 0x8000000000000000ull);
-  }
-  bool neg = false;
-  uint64_t mag = bits;
-  switch (elem) {
-    case VH_I8: { const int64_t v = (int8_t)bits; neg = v < 0; mag = neg ? (uint64_t)(-v) : (uint64_t)v; } break;
-    case VH_I16: { const int64_t v = (int16_t)bits; neg = v < 0; mag = neg ? (uint64_t)(-v) : (uint64_t)v; } break;
-    case VH_I32: { const int64_t v = (int32_t)bits; neg = v < 0; mag = neg ? (uint64_t)(-v) : (uint64_t)v; } break;
-    case VH_I64: { const int64_t v = (int64_t)bits; neg = v < 0; mag = neg ? 0ull - (uint64_t)v : (uint64_t)v; } break;
-    case VH_U8: mag = bits & 0xFFull; break;
-    case VH_U16: mag = bits & 0xFFFFull; break;
-    case VH_U32: mag = bits & 0xFFFFFFFFull; break;
-    default: break;
-  }
-  int nd = 1;                                                        // decimal digits of |v|
-  uint64_t base = 1;                                                 // 10^(nd-1)
-  while (nd < 20 && mag / 10 >= base) { base *= 10; ++nd; }
-  const uint64_t cls_rank = neg ? 2ull * nd + 1 : 2ull * nd;       // string length, '-' sorts before digits
-  // 58 bits for the magnitude: exact up to 17 digits; the 18..20-digit classes keep (|v| - 10^(nd-1)) >> 6,
-  // still monotone inside the class (the low bits only merge near-ties, which a superset tolerates)
-  return (cls_rank << 58) | (nd <= 17 ? mag : (mag - base) >> 6);
-}
 
 __global__ __launch_bounds__(256) void topk_keys_kernel(const void* src, int elem, uint32_t esize, int cls, int desc,
                                                         const unsigned long long* n_ptr, uint64_t* keys) {

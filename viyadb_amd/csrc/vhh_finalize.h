@@ -145,8 +145,8 @@ static int result_finalize(vh_result* r, int* retry, const vh_plan* plan) {
     }
     VhTopkCompact C{};
     C.ncols = P.ngroup + P.nmetric;
-    // formatter rounding ("%.15g" / "%g") can make nearby values compare equal in the reference: keep a margin
-    C.slack = r->topk_cls == VH_TOPK_FLOAT ? (r->topk_elem == VH_F32 ? (256ull << 32) : 64ull) : 0ull;
+    // formatter rounding ("%.15g" / "%g") makes nearby values compare equal in the reference: the margin that covers it (vh_topk_key.h)
+    C.slack = vh_topk_slack(r->topk_cls, r->topk_elem);
     for (int i = 0; i < P.ngroup; ++i) { C.src[i] = r->d_out_key[i]; C.dst[i] = r->d_out_key2[i]; C.esize[i] = (uint32_t)vh_elem_size(P.g[i].type()); }
     for (int j = 0; j < P.nmetric; ++j) {
       C.src[P.ngroup + j] = r->d_out_state[j]; C.dst[P.ngroup + j] = r->d_out_state2[j];
