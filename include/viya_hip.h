@@ -268,7 +268,9 @@ typedef struct vh_result_info {
                                         row's place — not gathered (bits 3 and 7 are set too);
                                 bit 14: DENSE_PART's one-word tuples were FOUR bytes (bit 10 is set too);
                                 bit 15: the projection's records are bit fields (bits 3 and 7 are set too);
-                                bits 16-18: log2 of the projection's record bytes, less one (4 bytes: 1 ... 64 bytes: 5; 0 when bit 3 is clear) */
+                                bits 16-18: log2 of the projection's record bytes, less one (4 bytes: 1 ... 64 bytes: 5; 0 when bit 3 is clear);
+                                bit 19: (VH_BUILD_BACKGROUND tables) a kernel compile or a layout build for this query's shape is queued or running:
+                                        this query ran on what existed (the pre-built kernels, the arenas, layouts already there) */
   uint64_t returned_groups;  /* rows vh_result_copy delivers (= ngroups without HAVING) */
 } vh_result_info;
 
@@ -607,6 +609,41 @@ VH_API int vh_table_prepare(vh_table* t, const vh_plan* plan, vh_result_info* in
 /* The derived layouts moved to fresh device memory (which: 1 projections, 2 predicate planes, 0 = both) — same contents, other pages; what
  * vh_table_prepare does per candidate place, for callers that measure by themselves. */
 VH_API int vh_table_relocate(vh_table* t, uint32_t which);
+
+/* ---- where the one-time work runs ------------------------------------------
+ * VH_BUILD_INLINE (default; VH_BUILD=inline): the first queries of a shape compile its scan kernel and build the layouts the library
+ * decides on (VH_AUTO_PACK / VH_AUTO_NARROW) themselves, under the table lock. VH_BUILD_BACKGROUND (VH_BUILD=background makes it the default
+ * of new tables): a query never compiles and never builds a layout — it answers from what exists, sets vh_result_info.reserved bit 19 and
+ * queues the work; one worker thread per process compiles the kernel and builds the layouts beside the running queries and syncs, and they
+ * are taken into use once complete and current. Explicit calls (vh_table_pack*, _predpack*, _narrow, _prepare, _relocate, VH_PLAN_FORCE_PACK)
+ * stay synchronous; vh_table_prepare first waits for the table's jobs. vh_query_agg_sharded / vh_query_select_sharded treat every table as
+ * inline (the ranks must agree on organisation and buffer list). */
+enum vh_build_mode { VH_BUILD_INLINE = 0, VH_BUILD_BACKGROUND = 1 };
+typedef struct vh_build_info {
+  uint64_t jobs_queued;       /* waiting for the worker now                                             */
+  uint64_t jobs_running;      /* 0 or 1                                                                 */
+  uint64_t jobs_done;         /* since the table was created ...                                        */
+  uint64_t jobs_failed;       /* ... a compile or a build kernel that FAILED (the compile's text is reported by the next query) */
+  uint64_t jobs_cancelled;    /* ... dropped by vh_table_unpack                                         */
+  uint64_t kernels_compiled;  /* hipRTC compiles the worker ran for this table                          */
+  uint64_t kernels_cached;    /* kernels the worker loaded from the disk cache                          */
+  uint64_t layouts_built;     /* projections, predicate projections and narrow copies it published      */
+  uint64_t inline_builds;     /* compiles and automatic layout builds that ran on a caller's thread under the table lock: inside queries, vh_table_prepare's included */
+  double compile_ms;          /* the worker's compiles, summed (the reference's QueryStats::compile_time) */
+  double layout_ms;           /* the worker's layout builds, summed                                     */
+  double lock_ms;             /* of those: time the worker held the table lock (allocate + enqueue, publish) */
+  uint64_t jobs_declined;     /* layout jobs that came to nothing without an error: nothing to gain, no room under the free-memory guard,
+                                 a build a synced value made void (it is asked for again when queries keep wanting it)    */
+  uint64_t layout_restarts;   /* times a layout job started over: the arenas moved, the journal dropped past its epoch, a compressed
+                                 projection whose field a synced value outgrew during the build                          */
+  uint64_t warm_queries;      /* the worker's own queries (the asking plans run once more after the layouts were published, rows discarded,
+                                 so that the kernel for the new shape is queued at once) ...                             */
+  double warm_ms;             /* ... and their wall time, summed                                                         */
+} vh_build_info;
+VH_API int vh_table_set_build_mode(vh_table* t, int32_t mode);
+/* Returns when no job of this table is queued or running (VH_E_RANGE after timeout_ms; 0 = no limit); *out (may be NULL) as vh_table_build_info. */
+VH_API int vh_table_build_wait(vh_table* t, uint32_t timeout_ms, vh_build_info* out);
+VH_API int vh_table_build_info(vh_table* t, vh_build_info* out);
 VH_API int vh_result_get_info(vh_result* r, vh_result_info* info);
 /* Symbol(s) of the scan kernel(s) this query launched, spelled as rocprofv3 prints them ("scan_agg_fast_kernel<4, 256, 4, 3> +
  * part_agg_kernel<1024>"): what a profile of the same command must show. Valid until vh_result_free. */

@@ -26,7 +26,8 @@ enum { VDB_OK = 0, VDB_E_INVALID_ARGUMENT = 1, /* std::invalid_argument in the r
 typedef struct vdb_stats {          /* query::QueryStats (src/query/stats.h:35-58) + GPU extras */
   uint64_t scanned_segments, scanned_recs, aggregated_recs, output_recs, passed_recs;
   double compile_time, whole_time, scan_kernel_ms, device_total_ms;
-  int32_t path, reserved;
+  int32_t path, build_pending;      /* build_pending: background builds are on and a compile / layout build for this query's shape is queued or running */
+  double compile_ms;                /* the build worker's compiles for the query's table so far (0 with inline builds) */
 } vdb_stats;
 
 VDB_API int vdb_open(const char* config_json, int device, vdb** out);        /* db::Database(config) */
@@ -37,6 +38,9 @@ VDB_API int vdb_create_table(vdb* db, const char* table_json);              /* D
  * vh_comm_init / vh_comm_init_custom (include/viya_hip.h) and stays the caller's; NULL leaves the node. Dictionary codes of
  * string dimensions must agree between the ranks (one ingest order, or numeric / time dimensions). */
 VDB_API int vdb_join_node(vdb* db, void* vh_comm_handle);
+/* Database::SetBackgroundBuilds: kernels compiled and automatic layouts built beside the queries (on != 0) instead of inside the first
+ * queries of a shape (0, the default) — include/viya_hip.h, vh_table_set_build_mode. Applies to existing and future tables. */
+VDB_API int vdb_set_background_builds(vdb* db, int on);
 /* input::SimpleLoader::Load: rows in the facade's row encoding; now < 0 = wall clock
  * (the reference's VIYA_TEST_ROLLUP_TS test hook, src/codegen/db/rollup.cc:47-49) */
 VDB_API int vdb_load(vdb* db, const char* table, const char* rows, size_t rows_len, int64_t now);

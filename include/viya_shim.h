@@ -50,6 +50,10 @@ struct Stats {
   uint32_t device_flags, retries;
   double scan_kernel_ms;
   double sync_ms;            /* host time Run spent bringing the mirror up to date (assembling and enqueueing the batch; 0.00x when nothing changed) */
+  /* background builds (VH_BUILD=background): a compile or layout build for this query's shape is queued or running, so it ran on what existed;
+   * the build worker's compiles for the table so far, in ms (vh_build_info.compile_ms) */
+  uint32_t build_pending, reserved_;
+  double compile_ms;
 };
 typedef void (*SendFn)(void* ctx, const std::vector<std::string>& row);
 

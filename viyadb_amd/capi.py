@@ -132,6 +132,19 @@ class CommOps(C.Structure):
 
 COMM_ID_BYTES = 128
 
+BUILD_INLINE, BUILD_BACKGROUND = 0, 1
+INFO_BUILD_PENDING = 1 << 19      # vh_result_info.reserved bit 19
+
+
+class BuildInfo(C.Structure):
+    """vh_build_info: what the background build worker did for one table."""
+    _fields_ = [("jobs_queued", C.c_uint64), ("jobs_running", C.c_uint64), ("jobs_done", C.c_uint64),
+                ("jobs_failed", C.c_uint64), ("jobs_cancelled", C.c_uint64), ("kernels_compiled", C.c_uint64),
+                ("kernels_cached", C.c_uint64), ("layouts_built", C.c_uint64), ("inline_builds", C.c_uint64),
+                ("compile_ms", C.c_double), ("layout_ms", C.c_double), ("lock_ms", C.c_double),
+                ("jobs_declined", C.c_uint64), ("layout_restarts", C.c_uint64), ("warm_queries", C.c_uint64), ("warm_ms", C.c_double)]
+
+
 
 class VhError(RuntimeError):
     def __init__(self, code, msg):
@@ -188,6 +201,9 @@ SYMBOLS = {
     "vh_rows_free": (None, [_VP]),
     "vh_result_get_info": (C.c_int, [_VP, C.POINTER(ResultInfo)]),
     "vh_table_prepare": (C.c_int, [_VP, C.POINTER(Plan), C.POINTER(ResultInfo)]),
+    "vh_table_set_build_mode": (C.c_int, [_VP, C.c_int32]),
+    "vh_table_build_wait": (C.c_int, [_VP, C.c_uint32, C.POINTER(BuildInfo)]),
+    "vh_table_build_info": (C.c_int, [_VP, C.POINTER(BuildInfo)]),
     "vh_result_kernel": (C.c_char_p, [_VP]),
     "vh_result_state_elem": (C.c_int, [_VP, C.c_int32]),
     "vh_result_copy": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(C.c_uint64)]),

@@ -85,6 +85,8 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name);
 // The kernel for this shape: memory cache -> disk cache -> hipRTC. nullptr + *err on failure (the caller falls back to the
 // pre-built interpreting kernels). Thread-safe; a shape is compiled once.
 VhJitKernel* vh_jit_get(const VhJitShape& s, std::string* err);
+// What the memory cache holds for this shape, without compiling: 1 and *k (ready), -1 and *err (the compile failed), 0 (never asked for, or being compiled now).
+int vh_jit_peek(const VhJitShape& s, VhJitKernel** k, std::string* err);
 int vh_jit_occupancy(VhJitKernel* k, int block, size_t lds);
 hipError_t vh_jit_launch(VhJitKernel* k, const VhPlanDev& P, int grid, int block, size_t lds, hipStream_t s);
 hipError_t vh_jit_launch_hpagg(VhJitKernel* k, const VhPlanDev& P, const void* d_hpargs, int blocks_per_partition, int a_first, int grid, size_t lds, hipStream_t s);

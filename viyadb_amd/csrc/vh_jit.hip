@@ -655,6 +655,22 @@ VhJitKernel* vh_jit_get(const VhJitShape& s, std::string* err) {
   return e->k.get();
 }
 
+int vh_jit_peek(const VhJitShape& s, VhJitKernel** k, std::string* err) {
+  *k = nullptr;
+  std::shared_ptr<Entry> e;
+  {
+    std::lock_guard<std::mutex> lk(g_jit_mu);
+    auto it = g_jit.find(s.key());
+    if (it == g_jit.end()) return 0;
+    e = it->second;
+  }
+  std::unique_lock<std::mutex> lk(e->mu, std::try_to_lock);      // (held: somebody compiles the shape right now)
+  if (!lk.owns_lock() || !e->done) return 0;
+  if (!e->k) { if (err) *err = e->err; return -1; }
+  *k = e->k.get();
+  return 1;
+}
+
 int vh_jit_occupancy(VhJitKernel* k, int block, size_t lds) {
   int n = 0;
   if (lds > 64 * 1024 && lds > k->scan_lds_set) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k->fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); k->scan_lds_set = lds; }

@@ -707,6 +707,7 @@ static int fused_dense_step(vh_table* t, vh_comm* comm, int root, VhExec* x, vh_
 extern "C" int vh_query_agg_sharded(vh_table* t, const vh_plan* plan, vh_comm* comm, int32_t root, vh_result** out) {
   if (!t || !plan || !comm || !out) return vh_fail(VH_E_INVALID, "null argument");
   if (root >= comm->world || root < -1) return vh_fail(VH_E_INVALID, "root %d of %d ranks", root, comm->world);
+  struct InlineBuilds { bool was = g_build_inline; InlineBuilds() { g_build_inline = true; } ~InlineBuilds() { g_build_inline = was; } } inline_builds;      // (the ranks must agree on organisation and buffer list: no rank-local "not ready yet", vhh_build.h)
   if (comm->world == 1 && !test_env("VH_TEST_SHARDED_WORLD1")) return vh_query_agg(t, plan, out);   // (the test knob sends one rank through the whole protocol: RCCL with a single GPU)
   VH_ENTER();
   std::lock_guard<std::mutex> comm_lk(comm->mu);

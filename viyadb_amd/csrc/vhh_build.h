@@ -1,0 +1,444 @@
+// vhh_build.h — host side of libviya_hip, part of viya_hip.hip's translation unit (included there, in order; not a stand-alone header):
+// the background build mode (vh_table_set_build_mode, VH_BUILD=background): kernel compiles and automatic layout builds off the query path.
+//
+// ONE worker thread per process, started by the first job, bound to the library's device, with a stream of its own; joined when the library
+// is unloaded (g_build's destructor). No child processes. A query of a background table never compiles and never builds: where the inline
+// mode would, it asks for a job here (build_request_*, t->mu held) and goes on with what exists; vh_result_info.reserved bit 19 says so.
+// Jobs are keyed — kernel: VhJitShape::key(); layout: kind, form, column set — so a shape asked for a hundred times is built once.
+//
+// KERNELS. The job is vh_jit_get on the worker (disk cache or hipRTC; the code object is loaded and published under the JIT cache's own
+// locks). Queries look the shape up with vh_jit_peek: absent or being compiled = pending (planned for the pre-built kernels exactly like
+// "no kernel for this shape", but nothing is remembered or logged and VH_PLAN_FORCE_JIT is no error); a compile that failed is found there
+// by the next query and reported as in the inline mode.
+//
+// LAYOUTS (payload projections, predicate projections, narrow copies) are built beside queries and syncs in three steps:
+//   (a) under t->mu: the free-memory guard (evaluated NOW, not when the job was queued), the layout's description from the recorded stats,
+//       its buffers, the journal epoch E and the arena generation it builds against, and the build kernels ENQUEUED on the worker's stream
+//       (behind an event on the library's stream: every sync up to E has landed when they start);
+//   (b) t->mu released: the kernels run; the worker waits for its stream;
+//   (c) under t->mu: publish — applied_epoch = E, per-segment stamps as of (a), linked into t->packs / t->predpacks / t->narrows.
+// The journalled refresh every derived layout has (derived_jobs) then re-derives what was synced after E before the first query reads the
+// layout; a row a sync rewrote while (b) read it lies in such a range by construction.
+//   * What keeps the arenas in place during (b): table_grow — the only code that replaces them — calls build_arenas_moving first, which waits
+//     (t->mu held by the sync, not needed by step (b)) until the worker's stream is idle, and bumps vh_table::arena_gen; step (c) sees the
+//     generation moved and the job starts over against the new arenas. A layout is never published at another capacity than the table's.
+//   * A value that outgrows its field during (b): the projection kernels' own check (their overflow word, a private one of the worker) voids
+//     the build at (c) — a compressed projection starts over at the widths the stats say now; what was synced after the rows were read is
+//     caught by the first refresh (VH_PACK_STALE) or by the stats check of predpack_usable / narrow_usable, as for any layout. Never silently.
+//   * The journal dropped its older half past E (VH_TEST_JOURNAL_CAP): the job starts over.
+// After the last waiting layout job of a table the worker runs the plans that asked for them once more (build_warm: a query whose rows are
+// discarded, counted towards nothing), so that the kernel for the shape the NEW layouts give is queued at once and not by the next caller.
+//
+// LIFETIMES. vh_table_destroy and vh_table_unpack drop the table's queued jobs and wait for the running one (build_cancel_table, before they
+// take t->mu); a job only ever creates layouts, it holds no pointer to an existing one. vh_table_prepare waits for the table's jobs, then
+// goes on as in the inline mode (g_preparing). vh_query_agg_sharded / vh_query_select_sharded treat every table as inline: the ranks must agree
+// on organisation and buffer list, and a rank-local "not ready yet" is out of scope.
+//
+// The worker's own queries (build_warm) are whole scans through the pre-built kernels, one per distinct asking plan (at most 64 remembered),
+// counted in vh_build_info.warm_queries / warm_ms. Planning alone would do if the planner could stop before the launch for an aggregate;
+// its plan_only mode stops before the organisation is chosen, which is what the kernel's shape depends on.
+//
+// SHUTDOWN. The library has no shutdown entry point: the worker is stopped and joined by g_build's destructor, a static of this translation
+// unit declared after g_ctx and so destroyed before it. The JIT cache's statics live in another translation unit, whose destruction order
+// against this one is not specified: a process that exits in the middle of a background compile is the one case this leaves open. A worker that is
+// idle (the normal case at exit) leaves at once; one inside a compile or a kernel wait is waited for. Its stream, event, overflow word and
+// pinned job list are left to the process's end on purpose: releasing them from a static destructor would call into a HIP runtime that may
+// already be tearing down.
+//
+// Test hooks (test_env): VH_TEST_BUILD_HOLD=start — the worker accepts jobs but starts none while the variable reads so; =publish — a layout
+// job waits between (b) and (c). Both polled (g_build_hold, refreshed from the environment on the calling threads only), ended by a cancel or the library's unloading.
+#include <atomic>
+#include <deque>
+#include <functional>
+
+static thread_local int g_build_quiet = 0;        // this thread's queries count towards no automatic layout and queue none (a pending query's second plan, the worker's own queries)
+static thread_local bool g_build_inline = false;  // this thread's queries treat every table as inline (sharded queries)
+static bool build_background(const vh_table* t) { return t->build_mode == VH_BUILD_BACKGROUND && !g_preparing && !g_build_inline; }
+
+struct VhPlanCopy {        // a plan that outlives its caller's arrays (segment snapshot dropped: the rows of the last sync)
+  vh_plan p{};
+  std::vector<vh_filter_node> filter, having;
+  std::vector<vh_anynum> lits;
+  std::vector<vh_group_col> groups;
+  std::vector<int32_t> metrics;
+  std::string sig;
+  explicit VhPlanCopy(const vh_plan& s) : p(s) {
+    if (s.filter && s.nfilter > 0) filter.assign(s.filter, s.filter + s.nfilter);
+    if (s.having && s.nhaving > 0) having.assign(s.having, s.having + s.nhaving);
+    if (s.lits && s.nlits > 0) lits.assign(s.lits, s.lits + s.nlits);
+    if (s.groups && s.ngroups > 0) groups.assign(s.groups, s.groups + s.ngroups);
+    if (s.metrics && s.nmetrics > 0) metrics.assign(s.metrics, s.metrics + s.nmetrics);
+    p.filter = filter.empty() ? nullptr : filter.data(); p.having = having.empty() ? nullptr : having.data();
+    p.lits = lits.empty() ? nullptr : lits.data(); p.groups = groups.empty() ? nullptr : groups.data(); p.metrics = metrics.empty() ? nullptr : metrics.data();
+    p.seg_rows = nullptr; p.nseg = 0;
+    auto put = [&](const void* b, size_t n) { sig.append(static_cast<const char*>(b), n); sig.push_back('|'); };
+    put(filter.data(), filter.size() * sizeof(vh_filter_node)); put(having.data(), having.size() * sizeof(vh_filter_node));
+    put(lits.data(), lits.size() * sizeof(vh_anynum)); put(groups.data(), groups.size() * sizeof(vh_group_col)); put(metrics.data(), metrics.size() * 4);
+    put(&p.flags, 4); put(&p.groups_hint, 8); put(&p.top_col, 4); put(&p.top_desc, 4); put(&p.top_k, 8);
+  }
+};
+
+enum { VB_KERNEL = 0, VB_PACK = 1, VB_PREDPACK = 2, VB_NARROW = 3 };
+struct VhBuildJob {
+  vh_table* t = nullptr;
+  int kind = VB_KERNEL;
+  std::string key;
+  VhJitShape shape;                    // VB_KERNEL
+  std::vector<int> cols;               // layouts: the column set (VB_NARROW: one column)
+  bool form = false, automatic = true; // VB_PACK: compressed records; VB_PREDPACK: bit-sliced planes
+  std::string seen;                    // the sightings counter that asked (reset when the job comes to nothing)
+  std::atomic<bool> cancel{false};
+};
+struct VhBuild {
+  std::mutex mu;                       // taken AFTER t->mu where both are held; never held while t->mu is taken
+  std::condition_variable cv;
+  std::deque<std::shared_ptr<VhBuildJob>> queue;
+  std::shared_ptr<VhBuildJob> running;
+  bool reading = false;                // the running job's kernels may be reading the table's arenas (step (b))
+  std::map<vh_table*, vh_build_info> info;
+  std::map<vh_table*, std::vector<std::shared_ptr<VhPlanCopy>>> warm;      // plans whose queries asked for the layouts now being built
+  std::thread worker;
+  bool started = false, stop = false;
+  hipStream_t stream = nullptr; hipEvent_t ev = nullptr; unsigned int* d_flag = nullptr;
+  VhJob* h_jobs = nullptr; size_t h_jobs_bytes = 0;
+  ~VhBuild() {
+    { std::lock_guard<std::mutex> lk(mu); stop = true; }
+    cv.notify_all();
+    if (worker.joinable()) worker.join();
+  }
+};
+static VhBuild g_build;
+// VH_TEST_BUILD_HOLD as the worker sees it: 0 none, 1 start, 2 publish. The environment is read on the CALLING threads only — whenever a job is
+// queued and on entry to vh_table_build_info / vh_table_build_wait / vh_table_set_build_mode — never on the worker, which polls this word: a
+// getenv there would race with the setenv of the test's own threads.
+static std::atomic<int> g_build_hold{0};
+static void build_hold_refresh() {
+  const char* e = test_env("VH_TEST_BUILD_HOLD");
+  g_build_hold.store(!e ? 0 : !strcmp(e, "start") ? 1 : !strcmp(e, "publish") ? 2 : 0);
+}
+static void build_worker_main();
+
+// (t->mu held) Queue a job unless one with this key waits or runs for the table. true: there is such a job now.
+static bool build_queue(vh_table* t, int kind, const std::string& key, const std::function<void(VhBuildJob&)>& fill, const vh_plan* plan) {
+  build_hold_refresh();
+  std::lock_guard<std::mutex> lk(g_build.mu);
+  if (g_build.stop) return false;
+  bool have = g_build.running && g_build.running->t == t && g_build.running->key == key && !g_build.running->cancel;
+  for (auto& q : g_build.queue) have |= q->t == t && q->key == key;
+  if (!have) {
+    auto j = std::make_shared<VhBuildJob>();
+    j->t = t; j->kind = kind; j->key = key;
+    fill(*j);
+    g_build.queue.push_back(j);
+    ++g_build.info[t].jobs_queued;
+    if (kind != VB_KERNEL && plan) {
+      auto pc = std::make_shared<VhPlanCopy>(*plan);
+      auto& w = g_build.warm[t];
+      bool known = false;
+      for (auto& o : w) known |= o->sig == pc->sig;
+      if (!known && w.size() < 64) w.push_back(pc);
+    }
+    if (!g_build.started) { g_build.started = true; g_build.worker = std::thread(build_worker_main); }
+    g_build.cv.notify_all();
+  }
+  return true;
+}
+static bool build_request_kernel(vh_table* t, const VhJitShape& s) {
+  return build_queue(t, VB_KERNEL, "k:" + s.key(), [&](VhBuildJob& j) { j.shape = s; }, nullptr);
+}
+// `plan`: the aggregate plan that asked (nullptr: none to run again afterwards)
+static bool build_request_layout(vh_table* t, int kind, const std::vector<int>& cols, bool form, bool automatic, const std::string& seen, const vh_plan* plan) {
+  std::string key = kind == VB_PACK ? "p:" : kind == VB_PREDPACK ? "q:" : "n:";
+  key += form ? "1:" : "0:";
+  std::vector<int> sorted_cols = cols;
+  std::sort(sorted_cols.begin(), sorted_cols.end());
+  for (int c : sorted_cols) { key += std::to_string(c); key.push_back(','); }
+  auto no = t->build_nothing.find(key);
+  if (no != t->build_nothing.end()) { if (no->second == t->sync_epoch) return false; t->build_nothing.erase(no); }      // (judged "nothing to gain" at this very state of the table)
+  return build_queue(t, kind, key, [&](VhBuildJob& j) { j.cols = cols; j.form = form; j.automatic = automatic; j.seen = seen; }, plan);
+}
+
+static void build_arenas_moving(vh_table* t) {
+  std::unique_lock<std::mutex> lk(g_build.mu);
+  g_build.cv.wait(lk, [&] { return !(g_build.running && g_build.running->t == t && g_build.reading); });
+}
+static bool build_busy_locked(const vh_table* t) {
+  if (g_build.running && g_build.running->t == t) return true;
+  for (auto& q : g_build.queue) if (q->t == t) return true;
+  return false;
+}
+static void build_cancel_table(vh_table* t, bool forget) {
+  std::unique_lock<std::mutex> lk(g_build.mu);
+  if (!g_build.started) return;
+  for (auto it = g_build.queue.begin(); it != g_build.queue.end();) {
+    if ((*it)->t != t) { ++it; continue; }
+    auto f = g_build.info.find(t);
+    if (f != g_build.info.end()) { --f->second.jobs_queued; ++f->second.jobs_cancelled; }
+    it = g_build.queue.erase(it);
+  }
+  g_build.warm.erase(t);
+  if (g_build.running && g_build.running->t == t) g_build.running->cancel = true;
+  g_build.cv.notify_all();
+  g_build.cv.wait(lk, [&] { return !(g_build.running && g_build.running->t == t); });
+  if (forget) g_build.info.erase(t);
+}
+static void build_info_locked(vh_table* t, vh_build_info* out) {      // (g_build.mu held)
+  auto f = g_build.info.find(t);
+  *out = f != g_build.info.end() ? f->second : vh_build_info{};
+}
+static int build_wait(vh_table* t, uint32_t timeout_ms, vh_build_info* out) {
+  bool idle = true;
+  {
+    std::unique_lock<std::mutex> lk(g_build.mu);
+    auto done = [&] { return !build_busy_locked(t); };
+    if (timeout_ms) idle = g_build.cv.wait_for(lk, std::chrono::milliseconds(timeout_ms), done);
+    else g_build.cv.wait(lk, done);
+    if (out) build_info_locked(t, out);
+  }
+  if (out) { std::lock_guard<std::mutex> lk(t->mu); out->inline_builds = t->inline_builds; }
+  return idle ? VH_OK : vh_fail(VH_E_RANGE, "vh_table_build_wait: jobs of this table still queued or running after %u ms", timeout_ms);
+}
+
+extern "C" int vh_table_set_build_mode(vh_table* t, int32_t mode) {
+  if (!g_ctx.inited) return vh_fail(VH_E_INVALID, "vh_init has not been called");
+  if (!t || (mode != VH_BUILD_INLINE && mode != VH_BUILD_BACKGROUND)) return vh_fail(VH_E_INVALID, "vh_table_set_build_mode: bad argument");
+  build_hold_refresh();
+  std::lock_guard<std::mutex> lk(t->mu);
+  t->build_mode = mode;
+  return VH_OK;
+}
+extern "C" int vh_table_build_wait(vh_table* t, uint32_t timeout_ms, vh_build_info* out) {
+  if (!g_ctx.inited) return vh_fail(VH_E_INVALID, "vh_init has not been called");
+  if (!t) return vh_fail(VH_E_INVALID, "null table");
+  build_hold_refresh();
+  return build_wait(t, timeout_ms, out);
+}
+extern "C" int vh_table_build_info(vh_table* t, vh_build_info* out) {
+  if (!g_ctx.inited) return vh_fail(VH_E_INVALID, "vh_init has not been called");
+  if (!t || !out) return vh_fail(VH_E_INVALID, "null argument");
+  build_hold_refresh();
+  { std::lock_guard<std::mutex> lk(g_build.mu); build_info_locked(t, out); }
+  std::lock_guard<std::mutex> lk(t->mu);
+  out->inline_builds = t->inline_builds;
+  return VH_OK;
+}
+
+// ------------------------------------------------------------------ the worker
+static void build_count(vh_table* t, const std::function<void(vh_build_info&)>& f) {
+  std::lock_guard<std::mutex> lk(g_build.mu);
+  auto it = g_build.info.find(t);
+  if (it != g_build.info.end()) f(it->second);
+}
+static bool build_hold(const char* at) { return g_build_hold.load() == (!strcmp(at, "start") ? 1 : 2); }
+static double build_ms_since(std::chrono::steady_clock::time_point t0) {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// 0: done, 1: failed, 2: cancelled, 3: declined (nothing to gain, no room under the free-memory guard, a build that was void)
+static int build_run_kernel(VhBuildJob* j) {
+  VhJitKernel* k = nullptr;
+  std::string err;
+  if (vh_jit_peek(j->shape, &k, &err) != 0) return k ? 0 : 1;      // (somebody — vh_table_prepare, an inline table — was faster)
+  const auto t0 = std::chrono::steady_clock::now();
+  k = vh_jit_get(j->shape, &err);
+  const double ms = build_ms_since(t0);
+  build_count(j->t, [&](vh_build_info& i) {
+    if (!k) return;
+    if (k->compile_ms > 0) ++i.kernels_compiled; else ++i.kernels_cached;
+    i.compile_ms += ms;
+  });
+  if (knobs().times) fprintf(stderr, "vh build: kernel %s in %.1f ms on the worker\n", k ? k->name.c_str() : "(failed)", ms);
+  return k ? 0 : 1;
+}
+
+static int build_run_layout(VhBuildJob* j) {
+  vh_table* t = j->t;
+  auto nothing = [&](bool judged) {        // (t->mu held) the job comes to nothing: the sightings start again; `judged`: not before the table changes
+    if (j->kind == VB_PACK) t->gather_seen[j->seen] = 0;
+    else if (j->kind == VB_PREDPACK) t->ppred_seen[j->seen] = 0;
+    else t->pred_seen[j->cols[0]] = 0;
+    if (judged) t->build_nothing[j->key] = t->sync_epoch;
+    return 3;
+  };
+  std::vector<int> sorted_cols = j->cols;
+  std::sort(sorted_cols.begin(), sorted_cols.end());
+  auto exists = [&] {                      // (t->mu held) an explicit call built the same meanwhile
+    if (j->kind == VB_PACK) { for (auto& pk : t->packs) { std::vector<int> have = pk->cols; std::sort(have.begin(), have.end()); if (have == sorted_cols && pk->compressed == j->form) return true; } }
+    else if (j->kind == VB_PREDPACK) { for (auto& pp : t->predpacks) if (pp->cols == sorted_cols && pp->sliced == j->form) return true; }
+    else { for (auto& nw : t->narrows) if (nw->col == j->cols[0]) return true; }
+    return false;
+  };
+  const auto t_begin = std::chrono::steady_clock::now();
+  double lock_ms = 0;
+  for (int attempt = 0; attempt < 4; ++attempt) {
+    std::unique_ptr<VhPack> pk; std::unique_ptr<VhPredPack> pp; std::unique_ptr<VhNarrow> nw;
+    std::vector<char*> bufs;
+    size_t bytes = 0;
+    uint64_t E = 0, gen = 0;
+    uint32_t nseg_a = 0;
+    std::vector<uint64_t> mod_a;
+    size_t njobs = 0;
+    hipError_t he = hipSuccess;
+    auto drop = [&] { for (char* b : bufs) if (b) (void)hipFree(b); bufs.clear(); };
+    // ---- (a)
+    {
+      const auto a0 = std::chrono::steady_clock::now();
+      std::lock_guard<std::mutex> lk(t->mu);
+      struct Timer { double& acc; std::chrono::steady_clock::time_point t0; ~Timer() { acc += build_ms_since(t0); } } timer{lock_ms, a0};
+      if (j->cancel) return 2;
+      if (sync_resolve(t)) return 1;
+      if (exists()) return 0;
+      if (j->kind == VB_PACK) {
+        if (pack_describe(t, j->cols, j->automatic, j->form, &pk)) return nothing(true);
+        pk->cap_seg = t->cap_seg;
+        bufs.push_back(nullptr); bytes = (size_t)t->cap_seg * pk->stride + 256;
+      } else if (j->kind == VB_PREDPACK) {
+        if (predpack_describe(t, sorted_cols, j->automatic, j->form, &pp) || !pp) return nothing(true);
+        pp->cap_seg = t->cap_seg;
+        for (int q = 0; q < pp->nplanes; ++q) { bufs.push_back(nullptr); bytes += (size_t)t->cap_seg * pp->pstride[q] + 256; }
+      } else {
+        const int w = narrow_width_for(t, j->cols[0], t->nseg);
+        if (!w) return nothing(true);
+        nw.reset(new VhNarrow());
+        nw->col = j->cols[0]; nw->width = w; nw->automatic = j->automatic; nw->stride = t->padded_rows * (uint64_t)w; nw->cap_seg = t->cap_seg;
+        bufs.push_back(nullptr); bytes = (size_t)t->cap_seg * nw->stride + 256;
+      }
+      size_t free_b = 0, total_b = 0;      // room: a quarter of the device stays free, and a projection does not outgrow the table
+      if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b <= bytes + total_b / 4 || (j->kind == VB_PACK && bytes > t->device_bytes + 256)) return nothing(false);
+      for (size_t q = 0; q < bufs.size(); ++q) {
+        const size_t b = pk ? bytes : nw ? bytes : (size_t)t->cap_seg * pp->pstride[q] + 256;
+        if (hipMalloc(&bufs[q], b) != hipSuccess) { (void)hipGetLastError(); drop(); return nothing(false); }
+        trace_alloc("background layout", bufs[q], b);
+      }
+      if (pk) pk->base = bufs[0];
+      if (nw) nw->base = bufs[0];
+      if (pp) for (int q = 0; q < pp->nplanes; ++q) pp->pbase[q] = bufs[q];
+      E = t->sync_epoch; gen = t->arena_gen; nseg_a = t->nseg; mod_a = t->seg_mod;
+      std::vector<VhJob> jobs;
+      derived_jobs(t, 0, std::vector<uint64_t>(t->cap_seg, 0), pk ? (t->segment_rows + 255) / 256 * 256 : t->padded_rows, &jobs);
+      njobs = jobs.size();
+      if (njobs) {
+        if (njobs * sizeof(VhJob) > g_build.h_jobs_bytes) {
+          if (g_build.h_jobs) (void)hipHostFree(g_build.h_jobs);
+          g_build.h_jobs = nullptr; g_build.h_jobs_bytes = 0;
+          const size_t nb = std::max<size_t>(njobs * sizeof(VhJob) * 2, 1u << 16);
+          if (hipHostMalloc((void**)&g_build.h_jobs, nb, hipHostMallocCoherent) != hipSuccess) { (void)hipGetLastError(); drop(); return 1; }
+          g_build.h_jobs_bytes = nb;
+        }
+        memcpy(g_build.h_jobs, jobs.data(), njobs * sizeof(VhJob));
+        he = hipEventRecord(g_build.ev, g_ctx.stream);                       // every sync up to E has landed before the build kernels read
+        if (he == hipSuccess) he = hipStreamWaitEvent(g_build.stream, g_build.ev, 0);
+        if (he == hipSuccess && pk) he = hipMemsetAsync(g_build.d_flag, 0, 256, g_build.stream);
+        if (he == hipSuccess) {
+          if (pk) pack_launch(t, pk.get(), g_build.h_jobs, njobs, g_build.d_flag, g_build.stream);
+          else if (pp) predpack_launch(t, pp.get(), g_build.h_jobs, njobs, g_build.stream);
+          else narrow_launch(t, nw.get(), g_build.h_jobs, njobs, g_build.stream);
+          he = hipGetLastError();
+        }
+        std::lock_guard<std::mutex> bl(g_build.mu);
+        g_build.reading = true;
+      }
+    }
+    // ---- (b): the kernels run beside queries and syncs; nobody waits for this thread
+    unsigned int ovf = 0;
+    if (njobs) {
+      if (he == hipSuccess && pk) he = hipMemcpyAsync(&ovf, g_build.d_flag, sizeof(ovf), hipMemcpyDeviceToHost, g_build.stream);
+      const hipError_t se = hipStreamSynchronize(g_build.stream);
+      if (he == hipSuccess) he = se;
+      { std::lock_guard<std::mutex> bl(g_build.mu); g_build.reading = false; }
+      g_build.cv.notify_all();
+    }
+    while (build_hold("publish") && !j->cancel) {
+      { std::lock_guard<std::mutex> bl(g_build.mu); if (g_build.stop) break; }
+      std::this_thread::sleep_for(std::chrono::milliseconds(1));
+    }
+    // ---- (c)
+    {
+      const auto c0 = std::chrono::steady_clock::now();
+      std::unique_lock<std::mutex> lk(t->mu);
+      struct Timer { double& acc; std::chrono::steady_clock::time_point t0; ~Timer() { acc += build_ms_since(t0); } } timer{lock_ms, c0};
+      const bool moved = t->arena_gen != gen || t->cap_seg != (pk ? pk->cap_seg : pp ? pp->cap_seg : nw->cap_seg) || (E && E < t->journal_floor);
+      const bool again = !j->cancel && he == hipSuccess && (moved || (ovf && pk && pk->compressed));
+      if (j->cancel || he != hipSuccess || moved || ovf || exists()) {
+        lk.unlock();
+        drop();
+        if (j->cancel) return 2;
+        if (again) { build_count(t, [](vh_build_info& i) { ++i.layout_restarts; }); continue; }
+        if (he != hipSuccess || ovf) { std::lock_guard<std::mutex> l2(t->mu); (void)nothing(false); return he != hipSuccess ? 1 : 3; }
+        return 0;
+      }
+      std::vector<uint64_t> stamps(t->cap_seg, 0);
+      for (uint32_t s = 0; s < nseg_a && s < stamps.size(); ++s) stamps[s] = mod_a[s];
+      if (pk) { pk->seg_mod = stamps; pk->applied_epoch = E; pk->serial = ++t->layout_serial; t->packs.push_back(std::move(pk)); }
+      else if (pp) { pp->seg_mod = stamps; pp->applied_epoch = E; pp->serial = ++t->layout_serial; t->predpacks.push_back(std::move(pp)); }
+      else { nw->seg_mod = stamps; nw->applied_epoch = E; t->narrows.push_back(std::move(nw)); }
+      t->device_bytes += bytes;
+    }
+    const double ms = build_ms_since(t_begin);
+    build_count(t, [&](vh_build_info& i) { ++i.layouts_built; i.layout_ms += ms; i.lock_ms += lock_ms; });
+    if (knobs().times) fprintf(stderr, "vh build: layout %s in %.1f ms on the worker, the table lock held for %.3f ms of them (allocate + enqueue, publish)\n", j->key.c_str(), ms, lock_ms);
+    return 0;
+  }
+  std::lock_guard<std::mutex> lk(t->mu);
+  return nothing(false);
+}
+
+// The plan of a query that asked for layouts, once more, now that they exist: its kernel's shape has changed with them.
+static void build_warm(vh_table* t, const VhPlanCopy* pc) {
+  const auto t0 = std::chrono::steady_clock::now();
+  ++g_build_quiet;
+  vh_result* r = nullptr;
+  if (vh_query_agg(t, &pc->p, &r) == VH_OK) vh_result_free(r);
+  --g_build_quiet;
+  const double ms = build_ms_since(t0);
+  build_count(t, [&](vh_build_info& i) { ++i.warm_queries; i.warm_ms += ms; });
+}
+
+static void build_worker_main() {
+  (void)hipSetDevice(g_ctx.device);
+  (void)hipStreamCreateWithFlags(&g_build.stream, hipStreamNonBlocking);
+  (void)hipEventCreateWithFlags(&g_build.ev, hipEventDisableTiming);
+  (void)hipMalloc((void**)&g_build.d_flag, 256);
+  for (;;) {
+    std::shared_ptr<VhBuildJob> j;
+    {
+      std::unique_lock<std::mutex> lk(g_build.mu);
+      for (;;) {
+        if (g_build.stop) return;
+        const bool held = build_hold("start");
+        if (!held && !g_build.queue.empty()) break;
+        if (held) g_build.cv.wait_for(lk, std::chrono::milliseconds(2));
+        else g_build.cv.wait(lk);
+      }
+      auto it = g_build.queue.begin();      // layouts first: the kernel worth compiling is the one for the shape they give
+      for (auto q = g_build.queue.begin(); q != g_build.queue.end(); ++q) if ((*q)->kind != VB_KERNEL) { it = q; break; }
+      j = *it;
+      g_build.queue.erase(it);
+      g_build.running = j;
+      auto f = g_build.info.find(j->t);
+      if (f != g_build.info.end()) { --f->second.jobs_queued; ++f->second.jobs_running; }
+    }
+    const bool usable = g_build.stream && g_build.ev && g_build.d_flag;
+    int outcome = j->kind == VB_KERNEL ? build_run_kernel(j.get()) : usable ? build_run_layout(j.get()) : 1;
+    if (j->kind != VB_KERNEL && !j->cancel) {
+      std::vector<std::shared_ptr<VhPlanCopy>> plans;
+      {
+        std::lock_guard<std::mutex> lk(g_build.mu);
+        bool more = false;
+        for (auto& q : g_build.queue) more |= q->t == j->t && q->kind != VB_KERNEL;
+        auto w = g_build.warm.find(j->t);
+        if (!more && w != g_build.warm.end()) { plans.swap(w->second); g_build.warm.erase(w); }
+      }
+      for (auto& pc : plans) if (!j->cancel) build_warm(j->t, pc.get());
+    }
+    if (j->cancel) outcome = 2;
+    {
+      std::lock_guard<std::mutex> lk(g_build.mu);
+      auto f = g_build.info.find(j->t);
+      if (f != g_build.info.end()) { --f->second.jobs_running; ++(outcome == 0 ? f->second.jobs_done : outcome == 1 ? f->second.jobs_failed : outcome == 3 ? f->second.jobs_declined : f->second.jobs_cancelled); }
+      g_build.running.reset();
+      g_build.reading = false;
+    }
+    g_build.cv.notify_all();
+  }
+}

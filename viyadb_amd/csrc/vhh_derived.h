@@ -74,6 +74,30 @@ static int derived_waited(vh_table* t) {         // the host waited for g_ctx.st
   return VH_OK;
 }
 
+// One launch of the projection's build kernel over a list of jobs (pinned memory), on `st`; `flag`: the "a value outgrew its stored width" word.
+static void pack_launch(const vh_table* t, const VhPack* pk, const VhJob* d_jobs, size_t njobs, unsigned int* flag, hipStream_t st) {
+  if (pk->bits) {
+    VhPackBitsArgs B{};
+    B.ncols = (int32_t)pk->cols.size(); B.rec_bytes = pk->rec_bytes;
+    for (size_t c = 0; c < pk->cols.size(); ++c) {
+      const VhColumn& col = t->cols[pk->cols[c]];
+      B.src[c] = col.base; B.src_stride[c] = col.stride; B.esize[c] = (uint32_t)col.esize; B.bitoff[c] = pk->bitoff[c]; B.bitw[c] = pk->bitw[c];
+    }
+    B.overflow = flag; B.dst = pk->base; B.dst_stride = pk->stride; B.jobs = d_jobs;
+    hipLaunchKernelGGL(pack_bits_kernel, dim3((unsigned)njobs), dim3(256), 0, st, B);
+  } else {
+    VhPackArgs A{};
+    A.ncols = (int32_t)pk->cols.size(); A.rec_bytes = pk->rec_bytes;
+    for (size_t c = 0; c < pk->cols.size(); ++c) {
+      const VhColumn& col = t->cols[pk->cols[c]];
+      A.src[c] = col.base; A.src_stride[c] = col.stride; A.esize[c] = (uint32_t)col.esize; A.off[c] = pk->off[c];
+      A.wbytes[c] = pk->width[c];
+      if (col.elem == VH_I8 || col.elem == VH_I16 || col.elem == VH_I32 || col.elem == VH_I64) A.sgn_mask |= 1u << c;
+    }
+    A.overflow = flag; A.dst = pk->base; A.dst_stride = pk->stride; A.jobs = d_jobs;
+    hipLaunchKernelGGL(pack_kernel, dim3((unsigned)njobs), dim3(256), 256 * pk->rec_bytes, st, A);
+  }
+}
 // Bring the projection up to date with the arenas: re-pack what changed since it was last packed (derived_jobs) in ONE launch.
 static int pack_refresh(vh_table* t, VhPack* pk, uint32_t first, uint32_t n) {
   (void)first; (void)n;
@@ -102,27 +126,7 @@ static int pack_refresh(vh_table* t, VhPack* pk, uint32_t first, uint32_t n) {
     const VhJob* d_jobs = nullptr;
     if (int rc = derived_upload(t, jobs, &d_jobs)) return rc;
     if (!t->d_packflag) { HIP_TRY(hipMalloc((void**)&t->d_packflag, 256)); HIP_TRY(hipMemsetAsync(t->d_packflag, 0, 256, g_ctx.stream)); }
-    if (pk->bits) {
-      VhPackBitsArgs B{};
-      B.ncols = (int32_t)pk->cols.size(); B.rec_bytes = pk->rec_bytes;
-      for (size_t c = 0; c < pk->cols.size(); ++c) {
-        const VhColumn& col = t->cols[pk->cols[c]];
-        B.src[c] = col.base; B.src_stride[c] = col.stride; B.esize[c] = (uint32_t)col.esize; B.bitoff[c] = pk->bitoff[c]; B.bitw[c] = pk->bitw[c];
-      }
-      B.overflow = t->d_packflag; B.dst = pk->base; B.dst_stride = pk->stride; B.jobs = d_jobs;
-      hipLaunchKernelGGL(pack_bits_kernel, dim3((unsigned)jobs.size()), dim3(256), 0, g_ctx.stream, B);
-    } else {
-      VhPackArgs A{};
-      A.ncols = (int32_t)pk->cols.size(); A.rec_bytes = pk->rec_bytes;
-      for (size_t c = 0; c < pk->cols.size(); ++c) {
-        const VhColumn& col = t->cols[pk->cols[c]];
-        A.src[c] = col.base; A.src_stride[c] = col.stride; A.esize[c] = (uint32_t)col.esize; A.off[c] = pk->off[c];
-        A.wbytes[c] = pk->width[c];
-        if (col.elem == VH_I8 || col.elem == VH_I16 || col.elem == VH_I32 || col.elem == VH_I64) A.sgn_mask |= 1u << c;
-      }
-      A.overflow = t->d_packflag; A.dst = pk->base; A.dst_stride = pk->stride; A.jobs = d_jobs;
-      hipLaunchKernelGGL(pack_kernel, dim3((unsigned)jobs.size()), dim3(256), 256 * pk->rec_bytes, g_ctx.stream, A);
-    }
+    pack_launch(t, pk, d_jobs, jobs.size(), t->d_packflag, g_ctx.stream);
     HIP_TRY(hipGetLastError());
     if (pk->compressed) {                               // did every value survive its stored width? (the one host wait of a refresh)
       unsigned int ovf = 0;
@@ -197,6 +201,51 @@ static int column_stored_width(vh_table* t, int col, int* width_out) {
   return VH_OK;
 }
 
+// The record layout of a projection of `order` (distinct columns): widths (compressed: what the recorded values need), offsets, bit fields.
+static int pack_describe(vh_table* t, const std::vector<int>& order, bool automatic, bool compress, std::unique_ptr<VhPack>* out) {
+  std::map<int, int> wof;
+  for (int c : order) {
+    int w = (int)t->cols[c].esize;
+    if (compress) if (int rc = column_stored_width(t, c, &w)) return rc;
+    wof[c] = w;
+  }
+  std::vector<int> ord = order;
+  std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return wof[a] > wof[b]; });   // widest first: every field naturally aligned
+  uint32_t bytes = 0;
+  std::vector<uint32_t> off;
+  std::vector<uint8_t> width;
+  for (int c : ord) { off.push_back(bytes); width.push_back((uint8_t)wof[c]); bytes += (uint32_t)wof[c]; }
+  if (bytes > 64) return vh_fail(VH_E_UNSUPPORTED, "vh_table_pack: %u payload bytes per row (max 64)", bytes);
+  uint32_t rec = 8;
+  while (rec < bytes) rec <<= 1;
+  // bit fields instead of bytes when every column is a non-negative integer (by its recorded min / max) and the word comes out smaller
+  std::vector<uint8_t> bitoff, bitw;
+  bool bits = compress && !test_env("VH_NO_PACK_BITS") && t->nseg > 0;
+  uint32_t used = 0;
+  for (int c : ord) {
+    if (!bits) break;
+    const VhColumn& col = t->cols[c];
+    if (col.elem == VH_F32 || col.elem == VH_F64 || (size_t)c >= t->stats.size() || t->stats[c].size() < t->nseg) { bits = false; break; }
+    uint64_t lo = ~0ull, hi = 0;
+    for (uint32_t sg = 0; sg < t->nseg; ++sg) { const VhSegStat& st = t->stats[c][sg]; if (st.lo > st.hi) continue; lo = std::min(lo, st.lo); hi = std::max(hi, st.hi); }
+    if (lo > hi) lo = hi = order_key_of_bits(col.elem, 0);
+    const bool sgn = col.elem == VH_I8 || col.elem == VH_I16 || col.elem == VH_I32 || col.elem == VH_I64;
+    if (sgn && (int64_t)(lo ^ (1ull << 63)) < 0) { bits = false; break; }
+    const uint64_t vmax = sgn ? (hi ^ (1ull << 63)) : bits_of_order_key(col.elem, hi);
+    int b = 1; while (b < 64 && (vmax >> b)) ++b;
+    bitoff.push_back((uint8_t)used); bitw.push_back((uint8_t)b); used += (uint32_t)b;
+    if (used > 64) { bits = false; break; }
+  }
+  const uint32_t rec_bits = used <= 32 ? 4u : 8u;
+  if (bits && rec_bits >= rec) bits = false;
+  std::unique_ptr<VhPack>& pk = *out;
+  pk.reset(new VhPack());
+  pk->cols = ord; pk->off = off; pk->width = width; pk->rec_bytes = rec; pk->automatic = automatic; pk->compressed = compress;
+  if (bits) { pk->bits = true; pk->bitoff = bitoff; pk->bitw = bitw; pk->rec_bytes = rec = rec_bits; for (auto& o : pk->off) o = 0; }
+  pk->stride = (t->segment_rows + 255) / 256 * 256 * (uint64_t)rec;
+  return VH_OK;
+}
+
 static int table_pack_locked(vh_table* t, const int32_t* cols, int32_t ncols, bool automatic, VhPack** out, bool compress) {
   if (!cols || ncols <= 0 || ncols > VH_PACK_MAX_COLS) return vh_fail(VH_E_INVALID, "vh_table_pack: 1..%d columns", VH_PACK_MAX_COLS);
   std::vector<int> order;
@@ -217,45 +266,8 @@ static int table_pack_locked(vh_table* t, const int32_t* cols, int32_t ncols, bo
     return rc;
   }
   for (int attempt = 0; attempt < 2; ++attempt) {
-    std::map<int, int> wof;
-    for (int c : order) {
-      int w = (int)t->cols[c].esize;
-      if (compress) if (int rc = column_stored_width(t, c, &w)) return rc;
-      wof[c] = w;
-    }
-    std::vector<int> ord = order;
-    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return wof[a] > wof[b]; });   // widest first: every field naturally aligned
-    uint32_t bytes = 0;
-    std::vector<uint32_t> off;
-    std::vector<uint8_t> width;
-    for (int c : ord) { off.push_back(bytes); width.push_back((uint8_t)wof[c]); bytes += (uint32_t)wof[c]; }
-    if (bytes > 64) return vh_fail(VH_E_UNSUPPORTED, "vh_table_pack: %u payload bytes per row (max 64)", bytes);
-    uint32_t rec = 8;
-    while (rec < bytes) rec <<= 1;
-    // bit fields instead of bytes when every column is a non-negative integer (by its recorded min / max) and the word comes out smaller
-    std::vector<uint8_t> bitoff, bitw;
-    bool bits = compress && !test_env("VH_NO_PACK_BITS") && t->nseg > 0;
-    uint32_t used = 0;
-    for (int c : ord) {
-      if (!bits) break;
-      const VhColumn& col = t->cols[c];
-      if (col.elem == VH_F32 || col.elem == VH_F64 || (size_t)c >= t->stats.size() || t->stats[c].size() < t->nseg) { bits = false; break; }
-      uint64_t lo = ~0ull, hi = 0;
-      for (uint32_t sg = 0; sg < t->nseg; ++sg) { const VhSegStat& st = t->stats[c][sg]; if (st.lo > st.hi) continue; lo = std::min(lo, st.lo); hi = std::max(hi, st.hi); }
-      if (lo > hi) lo = hi = order_key_of_bits(col.elem, 0);
-      const bool sgn = col.elem == VH_I8 || col.elem == VH_I16 || col.elem == VH_I32 || col.elem == VH_I64;
-      if (sgn && (int64_t)(lo ^ (1ull << 63)) < 0) { bits = false; break; }
-      const uint64_t vmax = sgn ? (hi ^ (1ull << 63)) : bits_of_order_key(col.elem, hi);
-      int b = 1; while (b < 64 && (vmax >> b)) ++b;
-      bitoff.push_back((uint8_t)used); bitw.push_back((uint8_t)b); used += (uint32_t)b;
-      if (used > 64) { bits = false; break; }
-    }
-    const uint32_t rec_bits = used <= 32 ? 4u : 8u;
-    if (bits && rec_bits >= rec) bits = false;
-    std::unique_ptr<VhPack> pk(new VhPack());
-    pk->cols = ord; pk->off = off; pk->width = width; pk->rec_bytes = rec; pk->automatic = automatic; pk->compressed = compress;
-    if (bits) { pk->bits = true; pk->bitoff = bitoff; pk->bitw = bitw; pk->rec_bytes = rec = rec_bits; for (auto& o : pk->off) o = 0; }
-    pk->stride = (t->segment_rows + 255) / 256 * 256 * (uint64_t)rec;
+    std::unique_ptr<VhPack> pk;
+    if (int drc = pack_describe(t, order, automatic, compress, &pk)) return drc;
     pk->serial = ++t->layout_serial;
     VhPack* raw = pk.get();
     t->packs.push_back(std::move(pk));
@@ -283,6 +295,15 @@ static int narrow_width_for(const vh_table* t, int col, uint32_t nseg) {
   if (!any) return 0;
   return hi < 256 ? 1 : hi < 65536 ? 2 : 0;
 }
+static void narrow_launch(const vh_table* t, const VhNarrow* nw, const VhJob* d_jobs, size_t njobs, hipStream_t st) {
+  const VhColumn& c = t->cols[nw->col];
+  if (nw->width == 1)
+    hipLaunchKernelGGL((narrow_kernel<uint8_t>), dim3((unsigned)njobs), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(c.base), c.stride / 4,
+                       reinterpret_cast<uint8_t*>(nw->base), nw->stride, d_jobs);
+  else
+    hipLaunchKernelGGL((narrow_kernel<uint16_t>), dim3((unsigned)njobs), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(c.base), c.stride / 4,
+                       reinterpret_cast<uint16_t*>(nw->base), nw->stride / 2, d_jobs);
+}
 // Bring the narrow copy up to date with its column: the ranges that changed since it was last copied, ONE launch, no host wait.
 static int narrow_refresh(vh_table* t, VhNarrow* nw, uint32_t first, uint32_t n) {
   (void)first; (void)n;
@@ -305,18 +326,12 @@ static int narrow_refresh(vh_table* t, VhNarrow* nw, uint32_t first, uint32_t n)
     t->device_bytes += bytes;
   }
   if (nw->applied_epoch == t->sync_epoch) return VH_OK;
-  const VhColumn& c = t->cols[nw->col];
   std::vector<VhJob> jobs;
   derived_jobs(t, nw->applied_epoch, nw->seg_mod, t->padded_rows, &jobs);
   if (!jobs.empty()) {
     const VhJob* d_jobs = nullptr;
     if (int rc = derived_upload(t, jobs, &d_jobs)) return rc;
-    if (nw->width == 1)
-      hipLaunchKernelGGL((narrow_kernel<uint8_t>), dim3((unsigned)jobs.size()), dim3(256), 0, g_ctx.stream, reinterpret_cast<const uint32_t*>(c.base), c.stride / 4,
-                         reinterpret_cast<uint8_t*>(nw->base), nw->stride, d_jobs);
-    else
-      hipLaunchKernelGGL((narrow_kernel<uint16_t>), dim3((unsigned)jobs.size()), dim3(256), 0, g_ctx.stream, reinterpret_cast<const uint32_t*>(c.base), c.stride / 4,
-                         reinterpret_cast<uint16_t*>(nw->base), nw->stride / 2, d_jobs);
+    narrow_launch(t, nw, d_jobs, jobs.size(), g_ctx.stream);
     HIP_TRY(hipGetLastError());
     if (int rc = derived_enqueued(t)) return rc;
   }
@@ -379,6 +394,18 @@ static void predpack_drop(vh_table* t, size_t k) {
   for (int q = 0; q < pp->nplanes; ++q) if (pp->pbase[q]) { (void)hipFree(pp->pbase[q]); t->device_bytes -= (size_t)pp->cap_seg * pp->pstride[q] + 256; }
   t->predpacks.erase(t->predpacks.begin() + (long)k);
 }
+static void predpack_launch(const vh_table* t, const VhPredPack* pp, const VhJob* d_jobs, size_t njobs, hipStream_t st) {
+  VhPredPackArgs A{};
+  A.ncols = (int32_t)pp->cols.size(); A.nplanes = pp->nplanes;
+  for (size_t c = 0; c < pp->cols.size(); ++c) {
+    const VhColumn& col = t->cols[pp->cols[c]];
+    A.src[c] = col.base; A.src_stride[c] = col.stride; A.esize[c] = (uint32_t)col.esize; A.bitoff[c] = pp->bitoff[c];
+  }
+  for (int q = 0; q < pp->nplanes; ++q) { A.plane[q] = pp->pbase[q]; A.plane_stride[q] = pp->pstride[q]; A.plane_width[q] = (uint32_t)pp->pwidth[q]; A.plane_pos[q] = (uint32_t)pp->ppos[q]; }
+  A.jobs = d_jobs;
+  if (pp->sliced) hipLaunchKernelGGL(predslice_kernel, dim3((unsigned)njobs), dim3(256), 0, st, A, pp->bits, pp->pitch);
+  else hipLaunchKernelGGL(predpack_kernel, dim3((unsigned)njobs), dim3(256), 0, st, A);
+}
 static int predpack_refresh(vh_table* t, VhPredPack* pp) {
   if (!t->nseg) return VH_OK;
   if (pp->cap_seg < t->cap_seg) {
@@ -407,16 +434,7 @@ static int predpack_refresh(vh_table* t, VhPredPack* pp) {
   if (!jobs.empty()) {
     const VhJob* d_jobs = nullptr;
     if (int rc = derived_upload(t, jobs, &d_jobs)) return rc;
-    VhPredPackArgs A{};
-    A.ncols = (int32_t)pp->cols.size(); A.nplanes = pp->nplanes;
-    for (size_t c = 0; c < pp->cols.size(); ++c) {
-      const VhColumn& col = t->cols[pp->cols[c]];
-      A.src[c] = col.base; A.src_stride[c] = col.stride; A.esize[c] = (uint32_t)col.esize; A.bitoff[c] = pp->bitoff[c];
-    }
-    for (int q = 0; q < pp->nplanes; ++q) { A.plane[q] = pp->pbase[q]; A.plane_stride[q] = pp->pstride[q]; A.plane_width[q] = (uint32_t)pp->pwidth[q]; A.plane_pos[q] = (uint32_t)pp->ppos[q]; }
-    A.jobs = d_jobs;
-    if (pp->sliced) hipLaunchKernelGGL(predslice_kernel, dim3((unsigned)jobs.size()), dim3(256), 0, g_ctx.stream, A, pp->bits, pp->pitch);
-    else hipLaunchKernelGGL(predpack_kernel, dim3((unsigned)jobs.size()), dim3(256), 0, g_ctx.stream, A);
+    predpack_launch(t, pp, d_jobs, jobs.size(), g_ctx.stream);
     HIP_TRY(hipGetLastError());
     if (int rc = derived_enqueued(t)) return rc;
   }
@@ -438,13 +456,10 @@ static VhPredPack* predpack_usable(vh_table* t, const std::vector<int>& cols, in
   }
   return nullptr;
 }
-// Build one for `cols` (ascending, distinct). *built = nullptr when there is nothing to gain: a column that is no non-negative integer,
-// more than 32 bits in all, or no fewer bytes per row than the columns' narrowest copies would take.
-static int table_predpack_locked(vh_table* t, const std::vector<int>& cols, bool automatic, VhPredPack** built, bool sliced) {
-  if (built) *built = nullptr;
-  if (cols.empty() || cols.size() > VH_PACK_MAX_COLS || cols.size() > VJ_MAX_PRED) return VH_OK;
-  for (auto& pp : t->predpacks) if (pp->cols == cols && pp->sliced == sliced) { if (built) *built = predpack_usable(t, cols, sliced ? 1 : 0); return VH_OK; }
+// The fields and planes of a predicate projection of `cols`; *out stays empty when there is nothing to gain.
+static int predpack_describe(vh_table* t, const std::vector<int>& cols, bool automatic, bool sliced, std::unique_ptr<VhPredPack>* out) {
   std::unique_ptr<VhPredPack> pp(new VhPredPack());
+  out->reset();
   uint32_t used = 0, plain = 0;
   for (int c : cols) {
     if (c < 0 || (size_t)c >= t->cols.size()) return vh_fail(VH_E_INVALID, "vh_table_predpack: column %d", c);
@@ -471,6 +486,18 @@ static int table_predpack_locked(vh_table* t, const std::vector<int>& cols, bool
     if (pp->bytes_per_row() >= plain) return VH_OK;
   }
   pp->automatic = automatic;
+  *out = std::move(pp);
+  return VH_OK;
+}
+// Build one for `cols` (ascending, distinct). *built = nullptr when there is nothing to gain: a column that is no non-negative integer,
+// more than 32 bits in all, or no fewer bytes per row than the columns' narrowest copies would take.
+static int table_predpack_locked(vh_table* t, const std::vector<int>& cols, bool automatic, VhPredPack** built, bool sliced) {
+  if (built) *built = nullptr;
+  if (cols.empty() || cols.size() > VH_PACK_MAX_COLS || cols.size() > VJ_MAX_PRED) return VH_OK;
+  for (auto& pp : t->predpacks) if (pp->cols == cols && pp->sliced == sliced) { if (built) *built = predpack_usable(t, cols, sliced ? 1 : 0); return VH_OK; }
+  std::unique_ptr<VhPredPack> pp;
+  if (int drc = predpack_describe(t, cols, automatic, sliced, &pp)) return drc;
+  if (!pp) return VH_OK;
   pp->serial = ++t->layout_serial;
   VhPredPack* raw = pp.get();
   t->predpacks.push_back(std::move(pp));
@@ -595,6 +622,7 @@ extern "C" int vh_table_relocate(vh_table* t, uint32_t which) {
 extern "C" int vh_table_unpack(vh_table* t) {
   if (!t) return vh_fail(VH_E_INVALID, "null table");
   VH_ENTER();
+  build_cancel_table(t, false);      // (before the lock: the running job needs it to finish; what it publishes meanwhile is dropped below)
   std::lock_guard<std::mutex> lk(t->mu);
   if (int src = sync_resolve(t)) return src;
   table_quiesce(t);

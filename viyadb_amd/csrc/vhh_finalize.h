@@ -621,6 +621,7 @@ static int place_layouts(vh_table* t, const vh_plan* plan, vh_result_info* info_
 // the last attempt's info is returned, so the caller sees what a steady-state query of this shape will run on.
 extern "C" int vh_table_prepare(vh_table* t, const vh_plan* plan, vh_result_info* info_out) {
   if (!t || !plan) return vh_fail(VH_E_INVALID, "null argument");
+  (void)build_wait(t, 0, nullptr);      // (background build mode: a job of this table that is queued or running is joined, not duplicated)
   struct Guard { Guard() { g_preparing = true; } ~Guard() { g_preparing = false; } } guard;
   uint32_t last = ~0u;
   for (int round = 0; round < 3; ++round) {

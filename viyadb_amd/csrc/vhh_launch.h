@@ -23,7 +23,7 @@ static int merge_copies_now(vh_result* r, hipStream_t st) {
 // (the first, inside vh_table_prepare) build it for the queries to come, memory permitting. Only where kernels get compiled at all.
 void QueryBuild::predpack_auto(bool want_sliced) {
   const int auto_after = g_preparing ? 1 : knobs().auto_narrow;
-  if (pp_cols.empty() || auto_after <= 0) return;
+  if (pp_cols.empty() || auto_after <= 0 || g_build_quiet) return;
   uint64_t rows = 0;
   for (uint32_t sgi = 0; sgi < t->nseg; ++sgi) rows += t->seg_rows[sgi];
   if (!(vh_jit_policy() == VH_JIT_FORCE || (p->flags & VH_PLAN_FORCE_JIT) || rows >= vh_jit_min_rows())) return;
@@ -32,9 +32,11 @@ void QueryBuild::predpack_auto(bool want_sliced) {
   std::string key = sliced ? "s:" : "b:";
   for (int c : pp_cols) { key += std::to_string(c); key.push_back(','); }
   if (++t->ppred_seen[key] < (uint32_t)auto_after) return;
+  if (build_background(t)) { build_pending |= build_request_layout(t, VB_PREDPACK, pp_cols, sliced, true, key, p); return; }      // (the worker builds it and evaluates the guard)
   size_t free_b = 0, total_b = 0;
   const size_t need = (size_t)t->cap_seg * t->padded_rows * 4;
-  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > need + total_b / 4) (void)table_predpack_locked(t, pp_cols, true, nullptr, sliced);
+  const size_t had = t->predpacks.size();
+  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > need + total_b / 4) { (void)table_predpack_locked(t, pp_cols, true, nullptr, sliced); t->inline_builds += t->predpacks.size() > had; }
   else t->ppred_seen[key] = 0;
 }
 
@@ -121,7 +123,31 @@ int QueryBuild::compile_kernel() {
     }
     if (jit_try) {
       std::string jerr;
-      jk = vh_jit_get(js, &jerr);
+      // background build mode: a lookup. A shape nobody compiled yet (or that is being compiled) is the worker's: this query is planned for the
+      // pre-built kernels as below — but pending is not failure: nothing is remembered, nothing is said, VH_PLAN_FORCE_JIT is no error
+      bool pending = false;
+      if (build_background(t)) {
+        if (vh_jit_peek(js, &jk, &jerr) == 0) pending = build_request_kernel(t, js);
+        if (!pending && !jk && jerr.empty()) jerr = "the build worker is shutting down";
+      } else {
+        VhJitKernel* had = nullptr;
+        std::string ignored;
+        const bool known = vh_jit_peek(js, &had, &ignored) != 0;
+        jk = vh_jit_get(js, &jerr);
+        if (!known) ++t->inline_builds;
+      }
+      if (pending) {
+        vh_plan p2 = *p;
+        p2.flags |= VH_PLAN_NO_JIT;
+        if (mode == VH_MODE_DENSE_PART) p2.flags |= VH_PLAN_FORCE_PART;
+        holder.reset();
+        done = true;
+        ++g_build_quiet;        // (the second plan counts towards no automatic layout: this query has been counted)
+        const int prc = query_launch_locked(t, x, &p2, out, hash_capacity_override, force_hash, part_tuples_override, no_part, plan_only, summary_out, ag, device_rows, hp_passes_override, no_hpart);
+        --g_build_quiet;
+        if (!prc && out && *out) (*out)->info.reserved |= 1u << 19;
+        return prc;
+      }
       if (!jk) {
         // no kernel for this shape (hipRTC missing, or the text did not compile): plan again for the pre-built kernels. The
         // failure is remembered per shape, so only the first query of the shape pays for the attempt.
@@ -617,7 +643,7 @@ int QueryBuild::launch() {
   if (jk) { narrowed = jshape.pp_nplanes || jshape.pp_sliced; for (int k = 0; k < jshape.npred; ++k) narrowed |= jshape.pred[k].width != vh_elem_size(jshape.pred[k].type); }
   r->hpart = hpart;
   r->info.reserved = (hpart ? 64 : 0) | (fastj || jk ? 1 : 0) | (lanes ? 2 : 0) | (P.lds_hash_slots ? 4 : 0) | (packed ? 8 : 0) | (fastj && narrowed ? 16 : 0) | (jk ? 32 : 0) | (packed && packed_compressed ? 128 : 0) | (hpart && hp_pack ? 256 : 0) | (mode == VH_MODE_DENSE_PART && P.gid_bits ? 1024 : 0) | (jk && (jshape.pp_nplanes || jshape.pp_sliced) ? 2048 : 0) | (jk && jshape.qpay ? 4096 : 0) | (jk && jshape.pp_sliced ? 8192 : 0) | (mode == VH_MODE_DENSE_PART && P.gid_bits && P.tuple4 ? 16384 : 0)
-                   | (packed && packed_bits ? 32768 : 0) | (packed ? (uint32_t)(31 - __builtin_clz(std::max<uint32_t>(packed_rec, 2)) - 1) << 16 : 0);
+                   | (build_pending ? 1u << 19 : 0) | (packed && packed_bits ? 32768 : 0) | (packed ? (uint32_t)(31 - __builtin_clz(std::max<uint32_t>(packed_rec, 2)) - 1) << 16 : 0);
   if (r->hp_chunks) memset(x->h_chunk, 0, VH_HP_CHUNKS * sizeof(unsigned long long));      // (what the context's previous query left there)
   // a second pass over heavy level-A partitions of a hashed partitioning: from the first pass's tuples when this plan's table can take them as
   // they are (one key word laid out as the first pass's, narrow ids) — else from the table's rows behind the bitmap, like any heavy range

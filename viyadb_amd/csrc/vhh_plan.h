@@ -244,6 +244,7 @@ struct QueryBuild {
   int pp_boff[VJ_MAX_PRED] = {}, pp_bbits[VJ_MAX_PRED] = {}, pp_soff[VJ_MAX_PRED] = {}, pp_sbits[VJ_MAX_PRED] = {};      // predicate column k's bit field in the byte-plane / bit-sliced projection noted in jshape
   void predpack_auto(bool want_sliced);          // counts this query towards an unasked predicate projection of the form it would have used
   VhJitKernel* jk = nullptr;
+  bool build_pending = false;                    // background build mode: a job for this query's shape is queued or running (vh_result_info.reserved bit 19)
   int jit_block = 256;
   // ---- work decomposition, scratch
   int BLOCK = 256, grid = 1;
@@ -493,10 +494,11 @@ int QueryBuild::shape_filter() {
       if (jit_predpack && !have) return narrow_slot[col] = -1;       // (the compiled kernel reads the predicate projection: no copy of its own for this column)
       const int nwidth = have ? 0 : narrow_width_for(t, col, t->nseg);
       // (every query that filters on the column reads it in full, whatever passes: the copy pays from the first query that uses it on)
-      if (!have && auto_after > 0 && nwidth && ++t->pred_seen[col] >= (uint32_t)auto_after) {
+      if (!have && auto_after > 0 && nwidth && !g_build_quiet && ++t->pred_seen[col] >= (uint32_t)auto_after) {
         size_t free_b = 0, total_b = 0;
         const size_t need = (size_t)t->cap_seg * ((t->segment_rows + 255) / 256 * 256) * (size_t)nwidth;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > need + total_b / 4) (void)table_narrow_locked(t, col, true);
+        if (build_background(t)) build_pending |= build_request_layout(t, VB_NARROW, std::vector<int>{col}, false, true, std::string(), plan_only ? nullptr : p);      // (the worker builds it; the guard is its to evaluate)
+        else if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > need + total_b / 4) { const size_t had = t->narrows.size(); (void)table_narrow_locked(t, col, true); t->inline_builds += t->narrows.size() > had; }
         else t->pred_seen[col] = 0;
       }
       int ns = -1;
@@ -1278,7 +1280,12 @@ int QueryBuild::choose_projection() {
       if (!use && (forced || auto_after > 0)) {
         std::string sig = jit_try ? "c:" : "p:";
         for (int c : gcols) sig += std::to_string(c) + ",";
-        bool build = forced || ++t->gather_seen[sig] >= (uint32_t)auto_after;
+        bool build = forced || (!g_build_quiet && ++t->gather_seen[sig] >= (uint32_t)auto_after);
+        if (build && !forced && build_background(t)) {      // the worker builds it (and evaluates the guard when it starts): this query gathers from the arenas
+          build_pending |= build_request_layout(t, VB_PACK, std::vector<int>(gcols.begin(), gcols.end()), jit_try && !knobs().pack_plain, true, sig, p);
+          build = false;
+        }
+        const size_t packs_had = t->packs.size();
         if (build && !forced) {        // room: the projection must leave a quarter of the device free and not outgrow the table
           uint32_t bytes = 0; for (int c : gcols) bytes += (uint32_t)t->cols[c].esize;
           uint32_t rec = 8; while (rec < bytes) rec <<= 1;
@@ -1288,6 +1295,7 @@ int QueryBuild::choose_projection() {
           if (!build) t->gather_seen[sig] = 0;
         }
         if (build && table_pack_locked(t, gcols.data(), (int32_t)gcols.size(), !forced, &use, jit_try && !knobs().pack_plain) != VH_OK) use = nullptr;
+        t->inline_builds += t->packs.size() > packs_had;
       }
     }
     if (use) {
@@ -1296,7 +1304,8 @@ int QueryBuild::choose_projection() {
         const bool was_auto = use->automatic;
         pack_drop(t, use);
         use = nullptr;
-        if (table_pack_locked(t, gcols.data(), (int32_t)gcols.size(), was_auto, &use, true) != VH_OK) use = nullptr;
+        if (build_background(t)) { if (!g_build_quiet) build_pending |= build_request_layout(t, VB_PACK, std::vector<int>(gcols.begin(), gcols.end()), true, was_auto, std::string("c:"), p); }
+        else { if (table_pack_locked(t, gcols.data(), (int32_t)gcols.size(), was_auto, &use, true) != VH_OK) use = nullptr; else ++t->inline_builds; }
         rc = VH_OK;
       }
       if (rc) { return rc; }

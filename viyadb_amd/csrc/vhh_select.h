@@ -220,6 +220,7 @@ static int comm_alltoallv(vh_comm* c, int32_t ncols, const void* const* send, vo
 // buffer of their slice's size. Local failures are carried to the next status point (agree_status), as in vh_query_agg_sharded.
 extern "C" int vh_query_select_sharded(vh_table* t, const vh_select_plan* sp, vh_comm* comm, int32_t root, vh_rows** out) {
   if (!t || !sp || !comm || !out) return vh_fail(VH_E_INVALID, "null argument");
+  struct InlineBuilds { bool was = g_build_inline; InlineBuilds() { g_build_inline = true; } ~InlineBuilds() { g_build_inline = was; } } inline_builds;      // (sharded queries treat every table as inline: vhh_build.h)
   int R = 0, W = 1;
   comm_shape(comm, &R, &W);
   if (root < 0 || root >= W) return vh_fail(VH_E_INVALID, "root %d of %d ranks", root, W);

@@ -135,7 +135,14 @@ struct vh_table {
   std::mutex mu;             // table metadata, column arenas, projections, planner caches: held while a query is PLANNED and
                              // LAUNCHED and by every sync; not while a launched query runs or is read back
   uint64_t device_bytes = 0;
+  // where the one-time work runs (vhh_build.h)
+  int build_mode = VH_BUILD_INLINE;
+  uint64_t inline_builds = 0;      // compiles and layout builds that ran inside a query of this table
+  std::map<std::string, uint64_t> build_nothing;   // background layout jobs that found nothing to gain -> the sync epoch they judged at (not queued again before the table changes)
+  uint64_t arena_gen = 0;          // bumped whenever table_grow replaces the column arenas: a layout job that enqueued its kernels against the old ones starts over
 };
+static void build_arenas_moving(vh_table* t);              // (vhh_build.h) t->mu held: the arenas are about to be replaced — wait until no background job's kernels read them
+static void build_cancel_table(vh_table* t, bool forget);  // (vhh_build.h) t->mu NOT held: drop the table's queued jobs, wait for the running one
 
 static const uint32_t VH_MAX_SEGMENTS = 1u << 24;   // (segment << 32 | row) positions and u32 segment loops stay far from overflow
 static bool is_dim(int kind) { return kind <= VH_DIM_BOOLEAN; }
@@ -148,6 +155,7 @@ static void trace_alloc(const char* what, const void* p, size_t bytes) {     // 
 static int table_grow(vh_table* t, uint32_t need_seg) {
   if (need_seg <= t->cap_seg) return VH_OK;
   uint32_t ncap = std::max<uint32_t>(need_seg, std::max<uint32_t>(4, t->cap_seg * 2));
+  if (t->cap_seg) { build_arenas_moving(t); ++t->arena_gen; }
   for (auto& c : t->cols) {
     if (is_bitset_elem(c.elem)) {
       c.bs_offsets.resize(ncap, nullptr); c.bs_offsets32.resize(ncap, nullptr); c.bs_values.resize(ncap, nullptr); c.bs_nvalues.resize(ncap, 0); c.bs_maxid.resize(ncap, 0);
@@ -181,6 +189,7 @@ extern "C" int vh_table_create(const vh_col_desc* cols, int32_t ncols, uint64_t 
   vh_table* t = new vh_table();
   t->segment_rows = segment_rows;
   t->padded_rows = (segment_rows + 63) / 64 * 64;
+  t->build_mode = knobs().build_background ? VH_BUILD_BACKGROUND : VH_BUILD_INLINE;
   t->cols.resize(ncols);
   t->stats.resize(ncols);
   for (int i = 0; i < ncols; ++i) {
@@ -279,6 +288,7 @@ static void table_note_change(vh_table* t, uint32_t seg, uint64_t first, uint64_
 extern "C" void vh_table_destroy(vh_table* t) {
   if (!t) return;
   VH_ENTER();
+  build_cancel_table(t, true);
   (void)hipStreamSynchronize(g_ctx.stream);
   for (auto& x : t->execs) { (void)hipStreamSynchronize(x->stream()); exec_free(x.get()); }
   for (auto& c : t->cols) {

@@ -122,6 +122,20 @@ class DeviceTable:
         except Exception:
             pass
 
+    # ---- where the one-time work runs (include/viya_hip.h: vh_table_set_build_mode)
+    def set_build_mode(self, background: bool):
+        capi.check(self.lib.vh_table_set_build_mode(self.handle, capi.BUILD_BACKGROUND if background else capi.BUILD_INLINE))
+
+    def build_info(self) -> capi.BuildInfo:
+        bi = capi.BuildInfo()
+        capi.check(self.lib.vh_table_build_info(self.handle, C.byref(bi)))
+        return bi
+
+    def build_wait(self, timeout_ms: int = 0) -> capi.BuildInfo:
+        bi = capi.BuildInfo()
+        capi.check(self.lib.vh_table_build_wait(self.handle, int(timeout_ms), C.byref(bi)))
+        return bi
+
     # ---- data in
     def sync_segment(self, seg: int, columns: Sequence[Optional[np.ndarray]], nrows: Optional[int] = None):
         ptrs = (C.c_void_p * len(self.cols))()

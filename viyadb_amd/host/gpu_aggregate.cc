@@ -29,6 +29,12 @@ void ensure_device() {
   });
 }
 
+// Database::SetBackgroundBuilds for one table: remembered for a mirror still to be made, applied to one that exists.
+void SetMirrorBuildMode(db::Table& t, bool background) {
+  t.gpu_background_builds = background;
+  if (t.gpu_mirror) vh_check(vh_table_set_build_mode(static_cast<GpuMirror*>(t.gpu_mirror)->handle, background ? VH_BUILD_BACKGROUND : VH_BUILD_INLINE));
+}
+
 GpuMirror* ensure_mirror(db::Table& t) {
   if (!t.gpu_mirror) {
     ensure_device();
@@ -42,6 +48,7 @@ GpuMirror* ensure_mirror(db::Table& t) {
     if (t.has_hidden_count()) cols.push_back({VH_METRIC_HIDDEN_COUNT, VH_U64});
     auto* mir = new GpuMirror();
     vh_check(vh_table_create(cols.data(), (int32_t)cols.size(), t.segment_size(), 1, &mir->handle));
+    if (t.gpu_background_builds) vh_check(vh_table_set_build_mode(mir->handle, VH_BUILD_BACKGROUND));
     t.gpu_mirror = mir;
     t.gpu_mirror_free = free_mirror;
   }
@@ -221,6 +228,7 @@ void FetchGroups(vh_result* res, AggregateQuery& query, Groups& groups, QuerySta
   stats.device_total_ms = info.total_ms;
   stats.path = info.path;
   stats.device_flags = info.reserved; stats.retries = info.retries;
+  stats.build_pending = (info.reserved & (1u << 19)) != 0;
 
   groups.n = info.returned_groups;
   std::vector<void*> kp, sp;
@@ -269,6 +277,8 @@ void AggregateOnMirror(AggregateQuery& query, vh_table* mirror, const std::vecto
   else vh_check(vh_query_agg(mirror, &plan, &res));
   std::unique_ptr<vh_result, void (*)(vh_result*)> guard(res, vh_result_free);
   FetchGroups(res, query, groups, stats);
+  vh_build_info bi;
+  if (vh_table_build_info(mirror, &bi) == VH_OK) stats.compile_ms = bi.compile_ms;
 }
 }  // namespace detail
 

@@ -299,7 +299,7 @@ void Run(Session* s, const uint64_t* fargs, size_t nfargs, const uint64_t* hargs
   q::detail::AggregateOnMirror(query, sh->mirror->handle, s->seg_rows, having_on_device, fa, ha, skip, limit, -1, groups, qs);
   CallbackOutput out(send, ctx);
   q::detail::PostAggregate(query, groups, having_on_device, ha, skip, limit, out, qs);
-  if (stats) *stats = Stats{qs.scanned_segments, qs.scanned_recs, qs.aggregated_recs, qs.output_recs, qs.device_flags, qs.retries, qs.scan_kernel_ms, sync_ms};
+  if (stats) *stats = Stats{qs.scanned_segments, qs.scanned_recs, qs.aggregated_recs, qs.output_recs, qs.device_flags, qs.retries, qs.scan_kernel_ms, sync_ms, qs.build_pending ? 1u : 0u, 0u, qs.compile_ms};
 }
 
 void Close(const void* table_key) {

@@ -239,6 +239,7 @@ public:
             int64_t now = -1);
 
   std::mutex mu;  // one writer / readers: the reference uses RWSpinLocks per segment and store
+  bool gpu_background_builds = false;  // Database::SetBackgroundBuilds: the mirror's build mode (include/viya_hip.h, vh_table_set_build_mode)
   void* gpu_mirror = nullptr;  // owned by query::GpuAggregate (opaque here)
   void (*gpu_mirror_free)(void*) = nullptr;
 

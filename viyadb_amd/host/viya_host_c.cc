@@ -72,6 +72,10 @@ int vdb_join_node(vdb* db, void* vh_comm_handle) {
   return vdbimpl::guard([&] { db->db->JoinNode(vh_comm_handle); });
 }
 
+int vdb_set_background_builds(vdb* db, int on) {
+  return vdbimpl::guard([&] { db->db->SetBackgroundBuilds(on != 0); });
+}
+
 int vdb_create_table(vdb* db, const char* table_json) {
   return vdbimpl::guard([&] { db->db->CreateTable(viya::util::Config(std::string(table_json))); });
 }
@@ -101,6 +105,7 @@ int vdb_query(vdb* db, const char* query_json, int64_t now, char** rows_out, siz
       stats->aggregated_recs = st.aggregated_recs; stats->output_recs = st.output_recs; stats->passed_recs = st.passed_recs;
       stats->compile_time = st.compile_time; stats->whole_time = st.whole_time;
       stats->scan_kernel_ms = st.scan_kernel_ms; stats->device_total_ms = st.device_total_ms; stats->path = st.path;
+  stats->build_pending = st.build_pending ? 1 : 0; stats->compile_ms = st.compile_ms;
     }
   });
 }
@@ -112,6 +117,7 @@ static void fill_stats(vdb_stats* stats, const viya::query::QueryStats& st) {
   stats->aggregated_recs = st.aggregated_recs; stats->output_recs = st.output_recs; stats->passed_recs = st.passed_recs;
   stats->compile_time = st.compile_time; stats->whole_time = st.whole_time;
   stats->scan_kernel_ms = st.scan_kernel_ms; stats->device_total_ms = st.device_total_ms; stats->path = st.path;
+  stats->build_pending = st.build_pending ? 1 : 0; stats->compile_ms = st.compile_ms;
 }
 
 int vdb_query_partial(vdb* db, const char* query_json, int64_t now, char** blob_out, size_t* blob_len, vdb_stats* stats) {

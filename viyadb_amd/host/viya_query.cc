@@ -162,7 +162,13 @@ std::vector<std::string> AggregateQuery::column_names() const {
 
 }  // namespace query
 
+namespace query { namespace detail { void SetMirrorBuildMode(db::Table& t, bool background); } }      // (gpu_aggregate.cc)
 namespace db {
+
+void Database::SetBackgroundBuilds(bool on) {
+  background_builds_ = on;
+  for (auto& kv : tables_) query::detail::SetMirrorBuildMode(*kv.second, on);
+}
 
 Database::Database(const util::Config& config, int device) {
   (void)device;
@@ -175,6 +181,7 @@ void Database::CreateTable(const util::Config& tc) {
   const std::string name = tc.str("name");
   if (tables_.count(name)) throw std::runtime_error("Table already exists: " + name);
   tables_[name] = std::make_unique<Table>(tc, dicts_);
+  tables_[name]->gpu_background_builds = background_builds_;
 }
 
 Table* Database::GetTable(const std::string& name) {

@@ -93,6 +93,8 @@ struct QueryStats {
   double scan_kernel_ms = 0, device_total_ms = 0;
   int path = 0;
   size_t passed_recs = 0;
+  bool build_pending = false;   // background builds (Database::SetBackgroundBuilds): a kernel compile or layout build for this query's shape is queued or running — it ran on what existed
+  double compile_ms = 0;        // ... the build worker's compiles for this table so far, summed (vh_build_info.compile_ms: the analogue of compile_time)
   unsigned device_flags = 0, retries = 0;   // vh_result_info.reserved (compiled kernel, projection, narrow copies, placed pool, ...) and re-plans: the cliffs a maintainer should see
 };
 
@@ -220,6 +222,9 @@ public:
   // Query() on every rank, rows delivered on rank 0, the other ranks sending none (vh_query_agg_sharded / vh_query_select_sharded;
   // replaces the HTTP + TSV merge of src/cluster/query/agg_runner.cc:83-140 and the search runner inside a node). The global
   // storage order is rank, then segment: ranks hold contiguous blocks of the table's segments in rank order. `comm` is a vh_comm* (include/viya_hip.h: vh_comm_init / vh_comm_init_custom), owned by the caller.
+  // Where kernels are compiled and automatic layouts built for this database's tables, present and future: inside the first queries of a
+  // shape (false, the default) or on the device library's build worker while queries answer from what exists (true): QueryStats::build_pending.
+  void SetBackgroundBuilds(bool on);
   void JoinNode(void* comm) { comm_ = comm; }
   void* node_comm() const { return comm_; }
   void Load(const std::string& table, const std::vector<std::vector<std::string>>& rows, int64_t now = -1);
@@ -232,6 +237,7 @@ private:
   Dictionaries dicts_;
   std::map<std::string, std::unique_ptr<Table>> tables_;
   void* comm_ = nullptr;
+  bool background_builds_ = false;
 };
 
 }  // namespace db

@@ -15,7 +15,7 @@ class Stats(C.Structure):
     _fields_ = [("scanned_segments", C.c_uint64), ("scanned_recs", C.c_uint64), ("aggregated_recs", C.c_uint64),
                 ("output_recs", C.c_uint64), ("passed_recs", C.c_uint64), ("compile_time", C.c_double),
                 ("whole_time", C.c_double), ("scan_kernel_ms", C.c_double), ("device_total_ms", C.c_double),
-                ("path", C.c_int32), ("reserved", C.c_int32)]
+                ("path", C.c_int32), ("build_pending", C.c_int32), ("compile_ms", C.c_double)]
 
 
 class HostError(RuntimeError):
@@ -25,7 +25,7 @@ class HostError(RuntimeError):
         self.reference_exception = "invalid_argument" if code == 1 else "runtime_error"
 
 
-SYMBOLS = ["vdb_open", "vdb_close", "vdb_join_node", "vdb_create_table", "vdb_load", "vdb_query", "vdb_query_partial", "vdb_query_merge",
+SYMBOLS = ["vdb_open", "vdb_close", "vdb_join_node", "vdb_set_background_builds", "vdb_create_table", "vdb_load", "vdb_query", "vdb_query_partial", "vdb_query_merge",
            "vdb_table_info", "vdb_free", "vdb_last_error", "vdb_shim_text"]
 _lib = None
 
@@ -44,6 +44,7 @@ def load():
         lib.vdb_close.restype = None
         lib.vdb_create_table.argtypes = [C.c_void_p, C.c_char_p]
         lib.vdb_join_node.argtypes = [C.c_void_p, C.c_void_p]
+        lib.vdb_set_background_builds.argtypes = [C.c_void_p, C.c_int]
         lib.vdb_load.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_size_t, C.c_int64]
         lib.vdb_query.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(Stats)]
         lib.vdb_query_partial.argtypes = [C.c_void_p, C.c_char_p, C.c_int64, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(Stats)]
@@ -72,6 +73,10 @@ class Database:
     def join_node(self, comm):
         """comm: viyadb_amd.distributed.Comm (or None to leave): aggregate queries then cover every rank's rows, rows on rank 0."""
         _check(self.lib.vdb_join_node(self.h, comm.handle if comm is not None else None))
+
+    def set_background_builds(self, on: bool):
+        """Database::SetBackgroundBuilds: kernels and automatic layouts are made beside the queries; stats['build_pending'] tells per query."""
+        _check(self.lib.vdb_set_background_builds(self.h, 1 if on else 0))
 
     def close(self):
         if self.h:
