@@ -204,6 +204,8 @@ enum vh_plan_flags {
   VH_PLAN_NO_QPAY = 1u << 25,     /* ablation: a survivor's values are always GATHERED by row, even where the compiled scan could stream the
                                      bit-field records of a projection beside the predicate columns and queue the survivor's record */
   VH_PLAN_FORCE_QPAY = 1u << 26,  /* testing: streamed records whenever the plan is eligible, whatever the selectivity */
+  VH_PLAN_NO_GROUPED = 1u << 28,  /* ablation: a survivor's record is gathered from the projection's row-order records even where its grouped form
+                                     (tiles of 2048 rows sorted by a narrow column the filter compares for equality) exists */
   VH_PLAN_CARD32 = 1u << 22       /* the cardinality of a 32-bit-id bitset metric (count distinct) is delivered as a uint32 column instead of
                                      uint64 (it cannot exceed 2^32 - 1): vh_result_state_elem() tells what a state column holds */
 };
@@ -269,6 +271,7 @@ typedef struct vh_result_info {
                                 bit 14: DENSE_PART's one-word tuples were FOUR bytes (bit 10 is set too);
                                 bit 15: the projection's records are bit fields (bits 3 and 7 are set too);
                                 bits 16-18: log2 of the projection's record bytes, less one (4 bytes: 1 ... 64 bytes: 5; 0 when bit 3 is clear);
+                                bit 20: the payload records were gathered from the projection's GROUPED form (bits 3, 7, 13 and 15 are set too);
                                 bit 19: (VH_BUILD_BACKGROUND tables) a kernel compile or a layout build for this query's shape is queued or running:
                                         this query ran on what existed (the pre-built kernels, the arenas, layouts already there) */
   uint64_t returned_groups;  /* rows vh_result_copy delivers (= ngroups without HAVING) */

@@ -52,6 +52,11 @@ struct VhJitShape {
   // a ballot and a rank per row — and 1 bit per row and bit of information streamed. pp_slot: the projection's slot (its pitch = bytes
   // between planes). The compacting kernels only; pred[] keeps the columns' own slots for the no-compaction form.
   int pp_sliced = 0, pp_slot = -1;
+  // GROUPED payload records (VhGrouped, vh_grouped.h): the plan's 4-byte bit records are gathered from the form that keeps every 2048-row tile
+  // sorted by predicate column `pp_group` (an index into pred[]; its field has at most VH_GROUP_MAX_BITS bits), which the filter's top-level
+  // AND compares with literal `pp_group_lit` for equality; `pp_group_hdr` is the slot of the tiles' headers. The bit-sliced compacting scan only:
+  // a survivor's queue entry is the place of its record, computed from the planes of pp_group the step has loaded anyway. -1: off.
+  int pp_group = -1, pp_group_hdr = -1, pp_group_lit = 0;
   // Streamed payload: every group / metric value of the plan is a bit field of ONE 4-byte record per row (a bit-field projection, VhPack::bits).
   // Instead of queueing a survivor's ROW and gathering its record afterwards (a random 128-byte line per survivor: at 5 % selectivity 81 % of
   // the projection's lines are fetched anyway, at the rate random lines come in), the scan streams the records with the predicate planes —

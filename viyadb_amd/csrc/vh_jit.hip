@@ -54,6 +54,7 @@ std::string VhJitShape::key() const {
   for (int i = 0; i < npred; ++i) { put(pred[i].slot); put(pred[i].type); put(pred[i].width); }
   put(qpay); put(qpay_slot);
   put(pp_sliced); put(pp_slot);
+  put(pp_group); put(pp_group_hdr); put(pp_group_lit);
   if (pp_sliced) for (int i = 0; i < npred; ++i) { put(pp_off[i]); put(pp_bits[i]); }
   put(pp_nplanes);
   for (int q = 0; q < pp_nplanes; ++q) { put(pp_plane[q].slot); put(pp_plane[q].width); put(pp_plane[q].pos); }
@@ -126,6 +127,8 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
   t += vj_fmt("  static constexpr bool LANES = %s;\n", s.lanes ? "true" : "false");
   t += vj_fmt("  static constexpr int QPAY = %d;\n", s.qpay);
   t += vj_fmt("  static constexpr bool SLICED = %s;\n", s.pp_sliced ? "true" : "false");
+  const bool grouped = s.pp_sliced && s.pp_group >= 0 && s.pp_group < s.npred && !s.qpay && !s.lanes;
+  t += vj_fmt("  static constexpr bool GROUPED = %s;\n  static constexpr int G_HDR = %d, G_BITS = %d;\n", grouped ? "true" : "false", grouped ? s.pp_group_hdr : 0, grouped ? s.pp_bits[s.pp_group] : 0);
   {
     std::vector<int> a, b, c, d, e, f;
     for (int i = 0; i < s.ng; ++i) { a.push_back(s.g[i].type); b.push_back(s.g[i].gran); c.push_back(s.g[i].nroll); d.push_back(s.g[i].micro); e.push_back(s.g[i].key_word); f.push_back(s.g[i].key_shift); }
@@ -181,6 +184,19 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
         } break;
       }
     }
+  // grouped records: the `==` leaf on the grouping column by itself (the lane's rows that hold the literal), and the literal as an index into
+  // a tile's header — ~0u when no value of the field equals it (negative, or beyond the field's bits): the header is never read then
+  std::string gmask_fn, glit_fn;
+  if (grouped) {
+    const int p = s.pp_group, ty = s.pred[p].type;
+    const std::string l = lit_name(s.pp_group_lit, ty);
+    const bool sgn = ty == VH_I8 || ty == VH_I16 || ty == VH_I32 || ty == VH_I64;
+    const std::string c = vj_fmt("(uint64_t)%s%s", sgn ? "(int64_t)" : "", l.c_str()), neg = sgn ? "(" + l + " < 0)" : std::string("false");
+    gmask_fn = vj_fmt("  static __device__ __forceinline__ uint32_t gmask(const Lits& L, const uint32_t (&v)[%d]) {\n    return vj_bits_rel<%d, %d>(v + %d, %s, %s);\n  }\n",
+                      nva, s.pp_bits[p], (int)VH_OP_EQ, sbase[p], c.c_str(), neg.c_str());
+    glit_fn = vj_fmt("  static __device__ __forceinline__ uint32_t glit(const Lits& L) {\n    const uint64_t c = %s;\n    return (%s || (c >> %d) != 0ull) ? ~0u : (uint32_t)c;\n  }\n",
+                     c.c_str(), neg.c_str(), s.pp_bits[p]);
+  }
   std::vector<std::pair<std::string, std::string>> st;      // (mask expression, bool expression)
   for (const VhProgOp& o : s.prog) {
     switch (o.kind()) {
@@ -220,6 +236,7 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
   t += "    __device__ __forceinline__ Lits(const VhPlanDev& P)";
   { bool first = true; for (auto& kv : lit_decl) { t += first ? " : " : ", "; first = false; t += kv.second.substr(kv.second.find('|') + 1); } }
   t += " { (void)P; }\n  };\n";
+  t += gmask_fn + glit_fn;
   if (s.pp_sliced) {
     t += vj_fmt("  static __device__ __forceinline__ uint32_t mask(const Lits& L, const uint32_t (&v)[%d]) {\n    (void)L; (void)v;\n    return %s;\n  }\n", nva, sst.empty() ? "~0u" : sst.back().c_str());
     // a lane's words of the planes the filter reads: one 4-byte load per plane (256 contiguous bytes per wave and plane), non-temporal
@@ -722,6 +739,7 @@ static bool vj_canonical(int which, VhJitShape* s) {
   auto col = [](int slot, int type, int pitch, int rec, int off, int sext) { VhJitCol c; c.slot = slot; c.type = type; c.pitch = pitch; c.rec = rec; c.off = off; c.sext = sext; return c; };
   switch (which) {
     case 19:    // ... case 0 whose tuples leave through the block's ring writer (16 partitions' waiting lines per block, extents by position)
+    case 21:    // ... case 14 gathering from the GROUPED records: tiles sorted by d2 (predicate 0, 2 bits), the headers in slot 14
     case 20:    // ... case 9 with the tuple in FOUR bytes (gid 17 + 10 + 2 bits: thirty-two to a line)
     case 18:    // ... case 9 likewise (one-word tuples: sixteen to a line)
     case 14:    // ... case 10 with the predicate columns BIT-SLICED: 2 + 10 + 10 planes of one bit per row, a lane owns 32 consecutive rows per step
@@ -734,6 +752,8 @@ static bool vj_canonical(int which, VhJitShape* s) {
     case 1: {   // ... the same from the 4-byte arenas, straight into the dense HBM table (what an eighth of the table runs)
       const bool ring = which == 18 || which == 19;
       const bool four = which == 20;      // C3's one-word tuples in 4 bytes
+      const bool by_d2 = which == 21;
+      if (which == 21) which = 14;
       if (which == 18 || which == 20) which = 9;
       if (which == 19) which = 0;
       const bool part = which == 0 || which == 7 || which == 9 || which == 10 || which == 12 || which == 13 || which == 14;
@@ -749,6 +769,7 @@ static bool vj_canonical(int which, VhJitShape* s) {
         S.m[1] = col(13, VH_U32, 32, 0, 16, 0); S.m[1].sop = SOP_ADD32P; S.m[1].tword = 0; S.m[1].tshift = 32;
         if (which == 9 || which == 10 || which == 12 || which == 13 || which == 14) { S.tw = 1; S.gid_bits = 17; S.m[0].tword = 0; S.m[0].tshift = 17; S.m[0].tbits = 10; S.m[1].tword = 0; S.m[1].tshift = 27; S.m[1].tbits = 2; }
         if (four) S.tuple4 = 1;
+        if (by_d2) { S.pp_group = 0; S.pp_group_hdr = 14; S.pp_group_lit = 0; }
         if (which == 13) { S.qpay = 4; S.qpay_slot = 10; }
         if (which == 14) { S.pp_sliced = 1; S.pp_slot = 7; S.pp_off[0] = 0; S.pp_bits[0] = 2; S.pp_off[1] = 2; S.pp_bits[1] = 10; S.pp_off[2] = 12; S.pp_bits[2] = 10; }
         if (which == 12 || which == 13) {

@@ -488,6 +488,32 @@ __device__ __forceinline__ void vj_push_mask(uint32_t* q, uint32_t& cnt, uint32_
   cnt += total;
 }
 
+// The same for a plan that gathers from the GROUPED form of its record projection (J::GROUPED; vh_grouped.h): what a passing row leaves in
+// the queue is the PLACE of its record in the segment — the tile's first row + vh_grouped_pos() of the lane's mask `eq` of rows that hold the
+// grouping literal (m is a subset of it), the lanes' exclusive prefix `before` over those masks and the tile header's start[literal].
+__device__ __forceinline__ void vj_push_mask_grouped(uint32_t* q, uint32_t& cnt, uint32_t m, uint32_t eq, uint32_t before, uint32_t start, uint32_t tile_base, int lane) {
+  const uint32_t c = (uint32_t)__popc(m);
+  uint32_t incl = c;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off); if (lane >= off) incl += o; }
+  const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+  if (total == 0u) return;
+  uint32_t pos = cnt + incl - c;
+  while (m) { q[pos++] = tile_base + vh_grouped_pos(eq, before, start, (uint32_t)__builtin_ctz(m)); m &= m - 1u; }
+  cnt += total;
+}
+// start[literal] of the tile that begins at row `wave_base` of segment `seg` (0 where the step has no row to scan, or no value of the field
+// equals the literal — `lit` is then ~0u and the header is never indexed with it: such a step queues nothing)
+template <class J>
+__device__ __forceinline__ uint32_t vj_group_start(const VhPlanDev& P, uint32_t seg, uint32_t wave_base, uint32_t seg_rows, uint32_t lit) {
+  if constexpr (J::GROUPED) {
+    if (lit == ~0u || wave_base >= seg_rows) return 0u;
+    const char* h = P.colbase[J::G_HDR] + (uint64_t)seg * P.colstride[J::G_HDR] + vh_grouped_hdr_off(wave_base / VH_GROUP_TILE, J::G_BITS);
+    return (uint32_t)reinterpret_cast<const uint16_t*>(h)[lit];
+  }
+  return 0u;
+}
+
 // One row slot of the wave step: the generated predicate for slot I, its ballot, and the passing lanes' rows appended to the
 // wave's queue. FULL = false: the step reaches the end of the segment's snapshot, rows at or beyond size() never pass.
 template <class J, int I, bool FULL>
@@ -589,6 +615,13 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
     if (wave_base + kWaveRows <= seg_rows) J::template preload<true>(P, seg, wave_base + lane * kLaneStride, seg_rows, v);
     else J::template preload<false>(P, seg, wave_base + lane * kLaneStride, seg_rows, v);
   }
+  // grouped payload (J::GROUPED): a wave step is one tile of the grouped records; the tile's start[literal] comes in with the step's planes
+  static_assert(!J::GROUPED || (J::SLICED && J::QPAY == 0 && !J::LANES && kWaveRows == VH_GROUP_TILE), "grouped records: the compacting bit-sliced scan, a tile per wave step");
+  uint32_t glit = ~0u, gstart = 0u;
+  if constexpr (J::GROUPED) {
+    glit = J::glit(L);
+    if (have) gstart = vj_group_start<J>(P, seg, wave_base, seg_rows, glit);
+  }
   uint32_t cnt = 0;
   if constexpr (J::LANES) {
     uint32_t lane_passed = 0;
@@ -630,10 +663,22 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
     const uint32_t row_l = wave_base + lane * kLaneStride;
     const uint32_t cnt0 = cnt;
     uint32_t smask = 0u;                       // (bit-sliced: the lane's pass mask of its 32 rows; pushed below, half by half)
+    uint32_t geq = 0u, gbefore = 0u;           // (grouped records: the lane's rows that hold the grouping literal, and how many the lanes below it hold)
+    const uint32_t gstart_now = gstart;
     if constexpr (J::SLICED) {
       if (wave_base < seg_rows) {
         smask = J::mask(L, v);
+        // (the grouping mask is taken BEFORE the snapshot cuts smask: a lane the snapshot cuts has loaded real bits, the builder ranked the
+        // rows behind the snapshot too, and lanes wholly behind it come after every lane that queues a row)
+        if constexpr (J::GROUPED) geq = J::gmask(L, v);
         if (wave_base + kWaveRows > seg_rows) smask &= row_l + 32u <= seg_rows ? ~0u : row_l < seg_rows ? (1u << (seg_rows - row_l)) - 1u : 0u;
+      }
+      if constexpr (J::GROUPED) {
+        const uint32_t gc = (uint32_t)__popc(geq);
+        uint32_t incl = gc;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off); if (lane >= off) incl += o; }
+        gbefore = incl - gc;
       }
     } else {
       if (wave_base + kWaveRows <= seg_rows) vj_slots<J, true>(L, v, row_l, seg_rows, q, cnt);
@@ -657,9 +702,10 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
     if (nhave) {
       if (nwave_base + kWaveRows <= nseg_rows) J::template preload<true>(P, nseg, nwave_base + lane * kLaneStride, nseg_rows, v);
       else J::template preload<false>(P, nseg, nwave_base + lane * kLaneStride, nseg_rows, v);
+      if constexpr (J::GROUPED) gstart = vj_group_start<J>(P, nseg, nwave_base, nseg_rows, glit);
     }
     __builtin_amdgcn_wave_barrier();
-    const bool flush = !nhave || nseg != seg;       // queue entries are rows of the current segment
+    const bool flush = !nhave || nseg != seg;       // queue entries are rows (grouped records: places) of the current segment
     auto drain_queue = [&](bool all) {
       if constexpr (MODE == VH_MODE_HASH && J::HPART && J::QPAY == 0 && J::ABLATE == 0 && VJ_DRAIN2) {
         while (cnt >= 128) {                        // two rows per lane while there are that many (vj_drain2)
@@ -683,12 +729,14 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
       // 32 rows are one 128-byte line of a 4-byte column (a record array), and a line whose survivors are all queued together is gathered by
       // one or two consecutive drains. Split by rows (16 + 16) the two halves of every line were asked for a whole drain sequence apart — with
       // half the rows passing, C5's scan fetched every payload line twice (FETCH_SIZE 2.9 GB for 1.5 GB of columns; profiles/r05/NOTES.md)
-      vj_push_mask(q, cnt, lane < 32 ? smask : 0u, row_l, lane);
+      if constexpr (J::GROUPED) vj_push_mask_grouped(q, cnt, lane < 32 ? smask : 0u, geq, gbefore, gstart_now, wave_base, lane);
+      else vj_push_mask(q, cnt, lane < 32 ? smask : 0u, row_l, lane);
       npassed += cnt - cnt0;
       __builtin_amdgcn_wave_barrier();
       drain_queue(false);
       const uint32_t cnt1 = cnt;
-      vj_push_mask(q, cnt, lane < 32 ? 0u : smask, row_l, lane);
+      if constexpr (J::GROUPED) vj_push_mask_grouped(q, cnt, lane < 32 ? 0u : smask, geq, gbefore, gstart_now, wave_base, lane);
+      else vj_push_mask(q, cnt, lane < 32 ? 0u : smask, row_l, lane);
       npassed += cnt - cnt1;
       __builtin_amdgcn_wave_barrier();
     }

@@ -17,6 +17,7 @@
 #pragma once
 #include "vh_internal.h"
 #include "vh_time.h"
+#include "vh_grouped.h"
 #include <type_traits>
 
 #ifndef VH_ABLATE

@@ -837,6 +837,87 @@ __global__ __launch_bounds__(256) void pack_bits_kernel(const VhPackBitsArgs A) 
   if (ovf) atomicOr(A.overflow, 1u);
 }
 
+// The GROUPED form of a 4-byte bit-record projection (VhGrouped; vh_grouped.h): the same records as pack_bits_kernel writes, every tile of
+// 2048 rows stable-sorted by the low `gbits` bits of column `gsrc` (the field a bit-sliced predicate projection keeps of it), and the tile's
+// header start[0 .. 2^gbits) beside it. One block per job = per tile (J.first a multiple of 2048); only rows below J.seg_rows take part, so
+// a place never reaches the tile's valid rows. The tile's 8 KB are staged in LDS in their new order and leave as whole lines.
+struct VhGroupArgs {
+  VhPackBitsArgs B;                    // the records: columns, fields, destination = the grouped arena (same stride as the ungrouped one)
+  const char* gsrc; uint64_t gsrc_stride; uint32_t gesize, gbits;
+  char* hdr; uint64_t hdr_stride;      // the headers: bytes between segments
+};
+__global__ __launch_bounds__(256) void group_bits_kernel(const VhGroupArgs A) {
+  constexpr uint32_t NL = VH_GROUP_TILE / 32u;             // lanes of the scan's wave step
+  __shared__ uint32_t s_rec[VH_GROUP_TILE], s_out[VH_GROUP_TILE];
+  __shared__ uint8_t s_val[VH_GROUP_TILE];
+  __shared__ uint32_t s_eq[1 << VH_GROUP_MAX_BITS][NL];       // value v, lane l: the lane's rows that hold v
+  __shared__ uint16_t s_before[1 << VH_GROUP_MAX_BITS][NL];   // ... and how many rows of the lanes below it do
+  __shared__ uint16_t s_total[1 << VH_GROUP_MAX_BITS], s_start[1 << VH_GROUP_MAX_BITS];
+  const VhJob J = A.B.jobs[blockIdx.x];
+  const uint32_t seg = J.seg, tile_base = J.first, nvals = 1u << A.gbits;
+  const uint32_t nvalid = J.seg_rows > tile_base ? (J.seg_rows - tile_base < VH_GROUP_TILE ? J.seg_rows - tile_base : VH_GROUP_TILE) : 0u;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  bool ovf = false;
+  for (uint32_t k = 0; k < VH_GROUP_TILE / 256u; ++k) {
+    const uint32_t i = k * 256u + threadIdx.x, row = tile_base + i;
+    const bool valid = i < nvalid;
+    uint64_t rec = 0; uint32_t val = 0;
+    if (valid) {
+      for (int c = 0; c < A.B.ncols; ++c) {
+        const char* s = A.B.src[c] + (uint64_t)seg * A.B.src_stride[c] + (uint64_t)row * A.B.esize[c];
+        uint64_t v;
+        switch (A.B.esize[c]) {
+          case 1: v = *reinterpret_cast<const uint8_t*>(s); break;
+          case 2: v = *reinterpret_cast<const uint16_t*>(s); break;
+          case 4: v = *reinterpret_cast<const uint32_t*>(s); break;
+          default: v = *reinterpret_cast<const uint64_t*>(s); break;
+        }
+        if (A.B.bitw[c] < 64u) ovf |= (v >> A.B.bitw[c]) != 0ull;
+        rec |= v << A.B.bitoff[c];
+      }
+      const char* g = A.gsrc + (uint64_t)seg * A.gsrc_stride + (uint64_t)row * A.gesize;
+      switch (A.gesize) {
+        case 1: val = *reinterpret_cast<const uint8_t*>(g); break;
+        case 2: val = *reinterpret_cast<const uint16_t*>(g); break;
+        case 4: val = *reinterpret_cast<const uint32_t*>(g); break;
+        default: val = (uint32_t)*reinterpret_cast<const uint64_t*>(g); break;
+      }
+      val &= nvals - 1u;
+    }
+    s_rec[i] = (uint32_t)rec; s_val[i] = (uint8_t)val;
+    // a wave's 64 rows are two lanes of the scan: the ballot of "holds v" is their two masks
+    for (uint32_t v = 0; v < nvals; ++v) {
+      const unsigned long long m = __ballot(valid && val == v);
+      if (lane == 0) { s_eq[v][2u * (k * 4u + wave)] = (uint32_t)m; s_eq[v][2u * (k * 4u + wave) + 1u] = (uint32_t)(m >> 32); }
+    }
+  }
+  __syncthreads();
+  for (uint32_t v = wave; v < nvals; v += 4u) {         // the lanes' exclusive prefix, per value (NL == 64: one wave, one value)
+    const uint32_t c = (uint32_t)__popc(s_eq[v][lane]);
+    uint32_t incl = c;
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off); if (lane >= off) incl += o; }
+    s_before[v][lane] = (uint16_t)(incl - c);
+    if (lane == 63) s_total[v] = (uint16_t)incl;
+  }
+  __syncthreads();
+  if (threadIdx.x < nvals) {
+    uint32_t st = 0;
+    for (uint32_t v = 0; v < threadIdx.x; ++v) st += s_total[v];
+    s_start[threadIdx.x] = (uint16_t)st;
+    reinterpret_cast<uint16_t*>(A.hdr + (uint64_t)seg * A.hdr_stride + vh_grouped_hdr_off(tile_base / VH_GROUP_TILE, A.gbits))[threadIdx.x] = (uint16_t)st;
+  }
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < nvalid; i += 256u) {
+    const uint32_t v = s_val[i], l = i >> 5;
+    s_out[vh_grouped_pos(s_eq[v][l], s_before[v][l], s_start[v], i & 31u)] = s_rec[i];      // (a permutation of [0, nvalid): every valid row has exactly one place)
+  }
+  __syncthreads();
+  uint32_t* dst = reinterpret_cast<uint32_t*>(A.B.dst + (uint64_t)seg * A.B.dst_stride) + tile_base;
+  for (uint32_t i = threadIdx.x; i < nvalid; i += 256u) dst[i] = s_out[i];
+  if (ovf) atomicOr(A.B.overflow, 1u);
+}
+
 // Bit-packed predicate projection (vh_table_predpack): every row's predicate columns as bit fields of one word (<= 32 bits), the word kept as
 // byte planes of 2 or 1 bytes per row. One row per thread and step; values are known to fit their fields (the host sizes the fields from
 // the columns' recorded min / max, which cover every mirrored value, and drops the projection when they no longer do).

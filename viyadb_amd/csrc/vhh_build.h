@@ -26,6 +26,10 @@
 //     the build at (c) — a compressed projection starts over at the widths the stats say now; what was synced after the rows were read is
 //     caught by the first refresh (VH_PACK_STALE) or by the stats check of predpack_usable / narrow_usable, as for any layout. Never silently.
 //   * The journal dropped its older half past E (VH_TEST_JOURNAL_CAP): the job starts over.
+//   * The GROUPED form of a 4-byte bit-record projection (VhGrouped) is a second form of a layout that exists, not a layout of its own, and it
+//     follows its projection's journalled refresh; it is built in one step under t->mu (allocate, enqueue group_bits_kernel on the library's
+//     stream like any refresh, no host wait): by the worker's own query (build_warm) right after the projection and the planes it pairs with
+//     were published, or by a VB_GROUPED job where a caller's query finds both without it. Counted in jobs_done, not in layouts_built.
 // After the last waiting layout job of a table the worker runs the plans that asked for them once more (build_warm: a query whose rows are
 // discarded, counted towards nothing), so that the kernel for the shape the NEW layouts give is queued at once and not by the next caller.
 //
@@ -53,6 +57,7 @@
 
 static thread_local int g_build_quiet = 0;        // this thread's queries count towards no automatic layout and queue none (a pending query's second plan, the worker's own queries)
 static thread_local bool g_build_inline = false;  // this thread's queries treat every table as inline (sharded queries)
+static thread_local bool g_build_worker = false;  // this thread is the worker (its build_warm queries build a projection's grouped form themselves: choose_grouped)
 static bool build_background(const vh_table* t) { return t->build_mode == VH_BUILD_BACKGROUND && !g_preparing && !g_build_inline; }
 
 struct VhPlanCopy {        // a plan that outlives its caller's arrays (segment snapshot dropped: the rows of the last sync)
@@ -78,13 +83,14 @@ struct VhPlanCopy {        // a plan that outlives its caller's arrays (segment 
   }
 };
 
-enum { VB_KERNEL = 0, VB_PACK = 1, VB_PREDPACK = 2, VB_NARROW = 3 };
+enum { VB_KERNEL = 0, VB_PACK = 1, VB_PREDPACK = 2, VB_NARROW = 3, VB_GROUPED = 4 };
 struct VhBuildJob {
   vh_table* t = nullptr;
   int kind = VB_KERNEL;
   std::string key;
   VhJitShape shape;                    // VB_KERNEL
-  std::vector<int> cols;               // layouts: the column set (VB_NARROW: one column)
+  std::vector<int> cols;               // layouts: the column set (VB_NARROW: one column; VB_GROUPED: the grouping column)
+  uint32_t gbits = 0; uint64_t serial = 0;      // VB_GROUPED: the grouping column's field bits, and VhPack::serial of the projection the form belongs to
   bool form = false, automatic = true; // VB_PACK: compressed records; VB_PREDPACK: bit-sliced planes
   std::string seen;                    // the sightings counter that asked (reset when the job comes to nothing)
   std::atomic<bool> cancel{false};
@@ -156,6 +162,13 @@ static bool build_request_layout(vh_table* t, int kind, const std::vector<int>& 
   auto no = t->build_nothing.find(key);
   if (no != t->build_nothing.end()) { if (no->second == t->sync_epoch) return false; t->build_nothing.erase(no); }      // (judged "nothing to gain" at this very state of the table)
   return build_queue(t, kind, key, [&](VhBuildJob& j) { j.cols = cols; j.form = form; j.automatic = automatic; j.seen = seen; }, plan);
+}
+
+// The grouped form (VhGrouped) of projection `serial` by column `col`. It is no layout of its own but a second form of a projection that
+// exists, so its job is short: grouped_build under t->mu (build_run_grouped), the kernel enqueued on the library's stream like any refresh.
+static bool build_request_grouped(vh_table* t, uint64_t serial, int col, uint32_t bits, const std::string& seen, const vh_plan* plan) {
+  const std::string key = "g:" + std::to_string(serial) + ":" + std::to_string(col) + ":" + std::to_string(bits);
+  return build_queue(t, VB_GROUPED, key, [&](VhBuildJob& j) { j.cols.assign(1, col); j.gbits = bits; j.serial = serial; j.seen = seen; }, plan);
 }
 
 static void build_arenas_moving(vh_table* t) {
@@ -249,6 +262,35 @@ static int build_run_kernel(VhBuildJob* j) {
   });
   if (knobs().times) fprintf(stderr, "vh build: kernel %s in %.1f ms on the worker\n", k ? k->name.c_str() : "(failed)", ms);
   return k ? 0 : 1;
+}
+
+// (t->mu held) Room for the grouped form of `pk` under the rule every automatic layout is built by: a quarter of the device stays free.
+static bool grouped_room(const vh_table* t, const VhPack* pk) {
+  size_t free_b = 0, total_b = 0;
+  const size_t need = (size_t)t->cap_seg * pk->stride;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
+  return free_b > need + total_b / 4;
+}
+static int build_run_grouped(VhBuildJob* j) {
+  vh_table* t = j->t;
+  const auto t0 = std::chrono::steady_clock::now();
+  int outcome = 3;
+  {
+    std::lock_guard<std::mutex> lk(t->mu);
+    if (j->cancel) return 2;
+    if (sync_resolve(t)) return 1;
+    VhPack* pk = nullptr;
+    for (auto& q : t->packs) if (q->serial == j->serial) pk = q.get();
+    if (pk && pk->grouped) return 0;          // (vh_table_prepare or the worker's own query was faster; one grouped form per projection)
+    if (pk && grouped_room(t, pk)) {
+      if (grouped_build(t, pk, j->cols[0], j->gbits) != VH_OK) { (void)hipGetLastError(); outcome = 1; }
+      else if (pk->grouped) outcome = 0;
+    }
+    if (outcome != 0) t->gather_seen[j->seen] = 0;      // the job came to nothing: the sightings start again
+  }
+  const double ms = build_ms_since(t0);
+  if (outcome == 0) build_count(t, [&](vh_build_info& i) { i.layout_ms += ms; i.lock_ms += ms; });
+  return outcome;
 }
 
 static int build_run_layout(VhBuildJob* j) {
@@ -395,6 +437,7 @@ static void build_warm(vh_table* t, const VhPlanCopy* pc) {
 }
 
 static void build_worker_main() {
+  g_build_worker = true;
   (void)hipSetDevice(g_ctx.device);
   (void)hipStreamCreateWithFlags(&g_build.stream, hipStreamNonBlocking);
   (void)hipEventCreateWithFlags(&g_build.ev, hipEventDisableTiming);
@@ -419,7 +462,7 @@ static void build_worker_main() {
       if (f != g_build.info.end()) { --f->second.jobs_queued; ++f->second.jobs_running; }
     }
     const bool usable = g_build.stream && g_build.ev && g_build.d_flag;
-    int outcome = j->kind == VB_KERNEL ? build_run_kernel(j.get()) : usable ? build_run_layout(j.get()) : 1;
+    int outcome = j->kind == VB_KERNEL ? build_run_kernel(j.get()) : j->kind == VB_GROUPED ? build_run_grouped(j.get()) : usable ? build_run_layout(j.get()) : 1;
     if (j->kind != VB_KERNEL && !j->cancel) {
       std::vector<std::shared_ptr<VhPlanCopy>> plans;
       {

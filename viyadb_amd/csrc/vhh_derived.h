@@ -98,9 +98,95 @@ static void pack_launch(const vh_table* t, const VhPack* pk, const VhJob* d_jobs
     hipLaunchKernelGGL(pack_kernel, dim3((unsigned)njobs), dim3(256), 256 * pk->rec_bytes, st, A);
   }
 }
+// ---- the grouped form of a bit-record projection (VhGrouped): built and refreshed with its projection, tile by tile
+static void grouped_drop(vh_table* t, VhPack* pk) {      // (the caller quiesced the table)
+  VhGrouped* gr = pk->grouped.get();
+  if (!gr) return;
+  if (gr->base) { (void)hipFree(gr->base); t->device_bytes -= gr->bytes(pk->stride); }
+  if (gr->hdr) { (void)hipFree(gr->hdr); t->device_bytes -= gr->hdr_bytes(); }
+  pk->grouped.reset();
+}
+// Re-derive the tiles that hold a row journalled since the grouped form was last current: derived_jobs' ranges widened to whole tiles (one
+// changed row moves the places of its tile's rows behind it), one block per tile. A projection that grew starts over in new buffers.
+static int grouped_refresh(vh_table* t, VhPack* pk) {
+  VhGrouped* gr = pk->grouped.get();
+  if (!gr || !t->nseg) return VH_OK;
+  if (gr->cap_seg < t->cap_seg) {
+    table_quiesce(t);
+    HIP_TRY(hipStreamSynchronize(g_ctx.stream)); derived_waited(t);
+    if (gr->base) { (void)hipFree(gr->base); t->device_bytes -= gr->bytes(pk->stride); gr->base = nullptr; }
+    if (gr->hdr) { (void)hipFree(gr->hdr); t->device_bytes -= gr->hdr_bytes(); gr->hdr = nullptr; }
+    gr->cap_seg = t->cap_seg;
+    if (hipMalloc(&gr->base, gr->bytes(pk->stride)) != hipSuccess || hipMalloc(&gr->hdr, gr->hdr_bytes()) != hipSuccess) {      // no room: the ungrouped records answer
+      (void)hipGetLastError();
+      if (gr->base) (void)hipFree(gr->base);
+      if (gr->hdr) (void)hipFree(gr->hdr);
+      pk->grouped.reset();
+      return VH_OK;
+    }
+    trace_alloc("grouped projection", gr->base, gr->bytes(pk->stride));
+    t->device_bytes += gr->bytes(pk->stride) + gr->hdr_bytes();
+    gr->seg_mod.assign(t->cap_seg, 0);
+    gr->applied_epoch = 0;
+  }
+  if (gr->applied_epoch == t->sync_epoch) return VH_OK;
+  std::vector<VhJob> ranges, jobs;
+  const uint64_t row_limit = (t->segment_rows + 255) / 256 * 256;
+  derived_jobs(t, gr->applied_epoch, gr->seg_mod, row_limit, &ranges);
+  std::vector<uint64_t> tiles;      // seg << 32 | tile
+  for (const VhJob& j : ranges)
+    for (uint64_t b = (uint64_t)j.first / VH_GROUP_TILE; b * VH_GROUP_TILE < (uint64_t)j.first + j.count; ++b) tiles.push_back(((uint64_t)j.seg << 32) | b);
+  std::sort(tiles.begin(), tiles.end());
+  tiles.erase(std::unique(tiles.begin(), tiles.end()), tiles.end());
+  for (uint64_t k : tiles) { const uint32_t seg = (uint32_t)(k >> 32); jobs.push_back(VhJob{seg, (uint32_t)(k & 0xFFFFFFFFull) * VH_GROUP_TILE, VH_GROUP_TILE, (uint32_t)t->seg_rows[seg]}); }
+  if (!jobs.empty()) {
+    const VhJob* d_jobs = nullptr;
+    if (int rc = derived_upload(t, jobs, &d_jobs)) return rc;
+    if (!t->d_packflag) { HIP_TRY(hipMalloc((void**)&t->d_packflag, 256)); HIP_TRY(hipMemsetAsync(t->d_packflag, 0, 256, g_ctx.stream)); }
+    VhGroupArgs A{};
+    A.B.ncols = (int32_t)pk->cols.size(); A.B.rec_bytes = pk->rec_bytes;
+    for (size_t c = 0; c < pk->cols.size(); ++c) {
+      const VhColumn& col = t->cols[pk->cols[c]];
+      A.B.src[c] = col.base; A.B.src_stride[c] = col.stride; A.B.esize[c] = (uint32_t)col.esize; A.B.bitoff[c] = pk->bitoff[c]; A.B.bitw[c] = pk->bitw[c];
+    }
+    A.B.overflow = t->d_packflag; A.B.dst = gr->base; A.B.dst_stride = pk->stride; A.B.jobs = d_jobs;
+    const VhColumn& gc = t->cols[gr->col];
+    A.gsrc = gc.base; A.gsrc_stride = gc.stride; A.gesize = (uint32_t)gc.esize; A.gbits = gr->bits;
+    A.hdr = gr->hdr; A.hdr_stride = gr->hdr_stride;
+    hipLaunchKernelGGL(group_bits_kernel, dim3((unsigned)jobs.size()), dim3(256), 0, g_ctx.stream, A);
+    HIP_TRY(hipGetLastError());
+    if (int rc = derived_enqueued(t)) return rc;
+  }
+  for (uint32_t s = 0; s < t->nseg; ++s) gr->seg_mod[s] = t->seg_mod[s];
+  gr->applied_epoch = t->sync_epoch;
+  return VH_OK;
+}
+// The grouped form of `pk` by column `col`, whose field in the bit-sliced planes has `bits` bits: built (or built again for another column or
+// width) and brought up to date. Bit-field records of 4 bytes only; nullptr and VH_OK where there is no room for it.
+static int grouped_build(vh_table* t, VhPack* pk, int col, uint32_t bits) {
+  if (!pk->bits || pk->rec_bytes != 4 || bits == 0 || bits > VH_GROUP_MAX_BITS || col < 0 || (size_t)col >= t->cols.size()) return VH_OK;
+  if (pk->grouped && (pk->grouped->col != col || pk->grouped->bits != bits)) {
+    table_quiesce(t);
+    HIP_TRY(hipStreamSynchronize(g_ctx.stream)); derived_waited(t);
+    grouped_drop(t, pk);
+  }
+  if (!pk->grouped) {
+    pk->grouped.reset(new VhGrouped());
+    pk->grouped->col = col; pk->grouped->bits = bits;
+    const uint64_t tiles = (t->segment_rows + VH_GROUP_TILE - 1) / VH_GROUP_TILE;
+    pk->grouped->hdr_stride = (tiles * vh_grouped_hdr_bytes(bits) + 63) / 64 * 64;
+  }
+  return grouped_refresh(t, pk);
+}
+
 // Bring the projection up to date with the arenas: re-pack what changed since it was last packed (derived_jobs) in ONE launch.
+static int pack_refresh_records(vh_table* t, VhPack* pk);
 static int pack_refresh(vh_table* t, VhPack* pk, uint32_t first, uint32_t n) {
   (void)first; (void)n;
+  if (int rc = pack_refresh_records(t, pk)) return rc;
+  return grouped_refresh(t, pk);          // (its grouped form follows in the same call: a plan finds both, and the planes, at one epoch)
+}
+static int pack_refresh_records(vh_table* t, VhPack* pk) {
   if (!t->nseg) return VH_OK;
   if (pk->cap_seg < t->cap_seg) {                      // the table grew: move the arena
     table_quiesce(t);
@@ -149,6 +235,7 @@ static void pack_drop(vh_table* t, VhPack* pk) {
   for (size_t k = 0; k < t->packs.size(); ++k) {
     if (t->packs[k].get() != pk) continue;
     if (pk->base) { (void)hipFree(pk->base); t->device_bytes -= (size_t)pk->cap_seg * pk->stride + 256; }
+    grouped_drop(t, pk);
     t->packs.erase(t->packs.begin() + (long)k);
     return;
   }
@@ -554,12 +641,12 @@ extern "C" int vh_table_pack(vh_table* t, const int32_t* cols, int32_t ncols) { 
 // 2 MB-aligned virtual addresses, so it is nothing a process can compute). What a process can do is try: derived_move copies every layout `which`
 // names (1: projections, 2: predicate planes) to FRESH allocations while the old ones are still held — so that the new ones are other pages —
 // and swaps the pointers (kernels take addresses as arguments); the caller measures and keeps or gives back (vh_table_prepare, vh_table_relocate).
-struct VhMoved {       // kind 1: a projection's records, 2: plane `plane` of a predicate projection; `serial` and `applied_epoch` of the layout at the move
+struct VhMoved {       // kind 1: a projection's records, 2: plane `plane` of a predicate projection, 3: a projection's grouped records (its headers stay: 32 bytes a tile); `serial` and `applied_epoch` of the layout at the move
   int kind; uint64_t serial, applied_epoch; int plane; char* old_ptr; char* new_ptr; size_t bytes;
 };
 static size_t derived_bytes(const vh_table* t, uint32_t which) {
   size_t b = 0;
-  if (which & 1u) for (auto& pk : t->packs) if (pk->base) b += (size_t)pk->cap_seg * pk->stride + 256;
+  if (which & 1u) for (auto& pk : t->packs) { if (pk->base) b += (size_t)pk->cap_seg * pk->stride + 256; if (pk->grouped && pk->grouped->base) b += pk->grouped->bytes(pk->stride); }
   if (which & 2u) for (auto& pp : t->predpacks) for (int q = 0; q < pp->nplanes; ++q) if (pp->pbase[q]) b += (size_t)pp->cap_seg * pp->pstride[q] + 256;
   return b;
 }
@@ -577,6 +664,7 @@ static int derived_move(vh_table* t, uint32_t which, std::vector<VhMoved>* moved
   };
   int rc = VH_OK;
   if (which & 1u) for (auto& pk : t->packs) if (pk->base && !rc) rc = move(1, pk->serial, pk->applied_epoch, 0, pk->base, (size_t)pk->cap_seg * pk->stride + 256, "projection");
+  if (which & 1u) for (auto& pk : t->packs) if (pk->grouped && pk->grouped->base && !rc) rc = move(3, pk->serial, pk->grouped->applied_epoch, 0, pk->grouped->base, pk->grouped->bytes(pk->stride), "grouped projection");
   if (which & 2u) for (auto& pp : t->predpacks) for (int q = 0; q < pp->nplanes && !rc; ++q) if (pp->pbase[q]) rc = move(2, pp->serial, pp->applied_epoch, q, pp->pbase[q], (size_t)pp->cap_seg * pp->pstride[q] + 256, "predicate plane");
   HIP_TRY(hipStreamSynchronize(g_ctx.stream));
   return rc == VH_E_NOMEM ? VH_OK : rc;          // (out of memory: what could be moved was moved)
@@ -598,6 +686,7 @@ static void derived_settle(vh_table* t, std::vector<VhMoved>& moved, bool keep, 
     char** slot = nullptr;
     uint64_t applied = 0;
     if (m.kind == 1) { for (auto& pk : t->packs) if (pk->serial == m.serial && pk->base == m.new_ptr) { slot = &pk->base; applied = pk->applied_epoch; } }
+    else if (m.kind == 3) { for (auto& pk : t->packs) if (pk->serial == m.serial && pk->grouped && pk->grouped->base == m.new_ptr) { slot = &pk->grouped->base; applied = pk->grouped->applied_epoch; } }
     else { for (auto& pp : t->predpacks) if (pp->serial == m.serial && pp->pbase[m.plane] == m.new_ptr) { slot = &pp->pbase[m.plane]; applied = pp->applied_epoch; } }
     if (slot && !keep && applied == m.applied_epoch) { *slot = m.old_ptr; out->push_back(m.new_ptr); }
     else out->push_back(m.old_ptr);
@@ -627,7 +716,7 @@ extern "C" int vh_table_unpack(vh_table* t) {
   if (int src = sync_resolve(t)) return src;
   table_quiesce(t);
   HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-  for (auto& pk : t->packs) if (pk->base) { (void)hipFree(pk->base); t->device_bytes -= (size_t)pk->cap_seg * pk->stride + 256; }
+  for (auto& pk : t->packs) { if (pk->base) { (void)hipFree(pk->base); t->device_bytes -= (size_t)pk->cap_seg * pk->stride + 256; } grouped_drop(t, pk.get()); }
   t->packs.clear();
   t->gather_seen.clear();
   for (auto& nw : t->narrows) if (nw->base) { (void)hipFree(nw->base); t->device_bytes -= (size_t)nw->cap_seg * nw->stride + 256; }

@@ -40,6 +40,75 @@ void QueryBuild::predpack_auto(bool want_sliced) {
   else t->ppred_seen[key] = 0;
 }
 
+// Grouped payload records (vh_grouped.h). A plan takes them when
+//   * it runs the compiled bit-sliced compacting scan (no lanes form, no streamed payload),
+//   * every group and metric value is a field of ONE 4-byte bit record of a projection (nothing else is gathered: no row id, no bitset),
+//   * the filter's top-level AND has exactly one `==` leaf on some column whose field in the planes has at most VH_GROUP_MAX_BITS bits — the
+//     first such column in program order is the grouping column —
+// and the projection's grouped form by that column exists at the planes' epoch. Where the automatic layouts are built (vh_table_prepare, or the
+// VH_AUTO_PACK-th query of the shape; on a background-build table by the worker, see vhh_build.h) it is built under the same
+// "leaves a quarter of the device free" rule. VH_PLAN_NO_GROUPED keeps the ungrouped records: an A/B inside one process.
+void QueryBuild::choose_grouped() {
+  VhJitShape& js = jshape;
+  if ((p->flags & VH_PLAN_NO_GROUPED) || !js.pp_sliced || lanes || js.qpay || !packed || !packed_use || !sliced_use || !packed_bits || packed_rec != 4 || P.nbitset) return;
+  for (int i = 0; i < P.ngroup; ++i) if (slot_rec[P.g[i].slot()] != 0 || slot_bits[P.g[i].slot()] != 4) return;
+  for (int j = 0; j < P.nmetric; ++j) if (metric_col[j] < 0 || P.m[j].slot() == VH_SLOT_ROWID || slot_rec[P.m[j].slot()] != 0 || slot_bits[P.m[j].slot()] != 4) return;
+  // the leaves of the top-level conjunction (a wide AND was folded pairwise: nested ANDs are the same conjunction)
+  const std::vector<VhProgOp>& g = js.prog;
+  if (g.empty() || g.back().kind() != VH_F_AND) return;
+  std::vector<int> leaves;
+  {
+    std::vector<int> sub(g.size(), 1);         // size of the subtree that ends at node k
+    for (size_t k = 0; k < g.size(); ++k)
+      if (g[k].kind() == VH_F_AND || g[k].kind() == VH_F_OR) { int at = (int)k - 1; for (int c = 0; c < (int)g[k].count() && at >= 0; ++c) { sub[k] += sub[at]; at -= sub[at]; } }
+    std::vector<int> todo{(int)g.size() - 1};
+    while (!todo.empty()) {
+      const int k = todo.back(); todo.pop_back();
+      if (g[k].kind() != VH_F_AND) { leaves.push_back(k); continue; }
+      int at = k - 1;
+      for (int c = 0; c < (int)g[k].count() && at >= 0; ++c) { todo.push_back(at); at -= sub[at]; }
+    }
+    std::sort(leaves.begin(), leaves.end());
+  }
+  int eq_leaves[VJ_MAX_PRED] = {}, leaf_of[VJ_MAX_PRED];
+  for (int k : leaves) if (g[k].kind() == VH_F_REL && g[k].op() == VH_OP_EQ && (int)g[k].pslot() < js.npred) { if (!eq_leaves[g[k].pslot()]++) leaf_of[g[k].pslot()] = k; }
+  int gp = -1;
+  for (int k : leaves) {
+    if (g[k].kind() != VH_F_REL || g[k].op() != VH_OP_EQ) continue;
+    const int ps = (int)g[k].pslot();
+    if (ps < js.npred && eq_leaves[ps] == 1 && js.pp_bits[ps] >= 1 && js.pp_bits[ps] <= VH_GROUP_MAX_BITS && jit_pred_col[ps] >= 0) { gp = ps; break; }
+  }
+  if (gp < 0 || P.nslots >= VH_MAX_SLOTS) return;
+  const int gcol = jit_pred_col[gp];
+  const uint32_t gbits = (uint32_t)js.pp_bits[gp];
+  VhGrouped* gr = packed_use->grouped.get();
+  if (!gr || gr->col != gcol || gr->bits != gbits) {
+    const int auto_after = g_preparing ? 1 : knobs().auto_pack;
+    if (auto_after <= 0) return;
+    if (gr && !g_preparing) return;            // (one grouped form per projection: only a prepared plan replaces another column's)
+    const std::string sig = "g:" + std::to_string(packed_use->serial) + ":" + std::to_string(gcol);
+    // background build mode: the worker's own query (build_warm), run because the layouts this plan's sightings asked for now exist, builds the
+    // form here, off every caller's path; a caller's query that finds projection and planes without it asks for a job after its own sightings
+    const bool bg = build_background(t), own = bg && g_build_worker;
+    if (!own) {
+      if (g_build_quiet) return;
+      if (++t->gather_seen[sig] < (uint32_t)auto_after) return;
+      if (bg) { build_pending |= build_request_grouped(t, packed_use->serial, gcol, gbits, sig, p); return; }
+    }
+    if (!grouped_room(t, packed_use)) { t->gather_seen[sig] = 0; return; }
+    if (grouped_build(t, packed_use, gcol, gbits) != VH_OK) { (void)hipGetLastError(); return; }
+    if (!bg) ++t->inline_builds;
+    gr = packed_use->grouped.get();
+    if (!gr) return;
+  }
+  // as current as the planes whose bits give the places, and as the table: anything else is a stale layout
+  if (!gr->base || !gr->hdr || gr->applied_epoch != t->sync_epoch || sliced_use->applied_epoch != t->sync_epoch || packed_use->applied_epoch != t->sync_epoch) return;
+  for (int s = 0; s < P.nslots; ++s) if (slot_rec[s] == 0 && slot_bits[s] == 4) P.colbase[s] = gr->base;      // (a bit record's members all start at the record)
+  P.colbase[P.nslots] = gr->hdr; P.colstride[P.nslots] = gr->hdr_stride; P.colpitch[P.nslots] = vh_grouped_hdr_bytes(gbits);
+  js.pp_group = gp; js.pp_group_hdr = P.nslots++; js.pp_group_lit = (int)g[leaf_of[gp]].lit();
+  grouped = true;
+}
+
 int QueryBuild::compile_kernel() {
   int rc = VH_OK; (void)rc;
   // ---------------- the scan kernel compiled for this plan shape (vh_jit.hip), when there is to be one
@@ -100,6 +169,7 @@ int QueryBuild::compile_kernel() {
       if (js.pp_sliced && nv > 64) { js.pp_sliced = 0; js.pp_slot = -1; }      // (more planes than registers to hold them: the columns themselves)
       if (js.qpay && nv + VH_SUBSTEPS * js.qpay > VJ_MAX_NV) { js.qpay = 0; js.qpay_slot = -1; }
     }
+    if (!lanes) choose_grouped();
     for (int i = 0; i < P.ngroup; ++i) {
       const VhGroupDev& g = P.g[i];
       VhJitCol& c = js.g[i];
@@ -643,7 +713,7 @@ int QueryBuild::launch() {
   if (jk) { narrowed = jshape.pp_nplanes || jshape.pp_sliced; for (int k = 0; k < jshape.npred; ++k) narrowed |= jshape.pred[k].width != vh_elem_size(jshape.pred[k].type); }
   r->hpart = hpart;
   r->info.reserved = (hpart ? 64 : 0) | (fastj || jk ? 1 : 0) | (lanes ? 2 : 0) | (P.lds_hash_slots ? 4 : 0) | (packed ? 8 : 0) | (fastj && narrowed ? 16 : 0) | (jk ? 32 : 0) | (packed && packed_compressed ? 128 : 0) | (hpart && hp_pack ? 256 : 0) | (mode == VH_MODE_DENSE_PART && P.gid_bits ? 1024 : 0) | (jk && (jshape.pp_nplanes || jshape.pp_sliced) ? 2048 : 0) | (jk && jshape.qpay ? 4096 : 0) | (jk && jshape.pp_sliced ? 8192 : 0) | (mode == VH_MODE_DENSE_PART && P.gid_bits && P.tuple4 ? 16384 : 0)
-                   | (build_pending ? 1u << 19 : 0) | (packed && packed_bits ? 32768 : 0) | (packed ? (uint32_t)(31 - __builtin_clz(std::max<uint32_t>(packed_rec, 2)) - 1) << 16 : 0);
+                   | (build_pending ? 1u << 19 : 0) | (jk && grouped ? 1u << 20 : 0) | (packed && packed_bits ? 32768 : 0) | (packed ? (uint32_t)(31 - __builtin_clz(std::max<uint32_t>(packed_rec, 2)) - 1) << 16 : 0);
   if (r->hp_chunks) memset(x->h_chunk, 0, VH_HP_CHUNKS * sizeof(unsigned long long));      // (what the context's previous query left there)
   // a second pass over heavy level-A partitions of a hashed partitioning: from the first pass's tuples when this plan's table can take them as
   // they are (one key word laid out as the first pass's, narrow ids) — else from the table's rows behind the bitmap, like any heavy range

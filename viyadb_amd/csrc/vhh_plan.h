@@ -240,6 +240,10 @@ struct QueryBuild {
   bool packed = false, packed_compressed = false;
   bool packed_bits = false; uint32_t packed_rec = 0;     // ... the projection's records: bit fields, and their bytes (vh_result_info.reserved bits 15-18)
   int qpay = 0, qpay_slot = -1;                  // streamed payload (VhJitShape::qpay): the record's bytes, the slot the records come from
+  VhPack* packed_use = nullptr;                  // the projection the plan gathers from, and the bit-sliced predicate projection shape_filter found:
+  VhPredPack* sliced_use = nullptr;              // what choose_grouped pairs up
+  bool grouped = false;                          // the records come from the projection's grouped form (vh_result_info.reserved bit 20)
+  void choose_grouped();                         // compile_kernel: point a qualifying plan at the grouped records (building them where the automatic layouts are built)
   std::vector<int> pp_cols;                      // the filter's columns (ascending) when every leaf reads a fixed-width column: what a predicate projection must hold
   int pp_boff[VJ_MAX_PRED] = {}, pp_bbits[VJ_MAX_PRED] = {}, pp_soff[VJ_MAX_PRED] = {}, pp_sbits[VJ_MAX_PRED] = {};      // predicate column k's bit field in the byte-plane / bit-sliced projection noted in jshape
   void predpack_auto(bool want_sliced);          // counts this query towards an unasked predicate projection of the form it would have used
@@ -474,6 +478,7 @@ int QueryBuild::shape_filter() {
     if (ps && P.nslots < VH_MAX_SLOTS) {
       P.colbase[P.nslots] = ps->pbase[0]; P.colstride[P.nslots] = ps->pstride[0]; P.colpitch[P.nslots] = (uint32_t)ps->pitch;
       jshape.pp_sliced = 1; jshape.pp_slot = P.nslots++;
+      sliced_use = ps;
       for (int k = 0; k < jshape.npred; ++k) {
         const size_t at = (size_t)(std::find(ps->cols.begin(), ps->cols.end(), jit_pred_col[k]) - ps->cols.begin());
         pp_soff[k] = ps->bitoff[at]; pp_sbits[k] = ps->bitw[at];
@@ -1326,7 +1331,7 @@ int QueryBuild::choose_projection() {
       };
       for (int i = 0; i < p->ngroups; ++i) P.g[i].set_slot((uint16_t)pslot(p->groups[i].col));
       for (int j = 0; j < P.nmetric; ++j) if (metric_col[j] >= 0) P.m[j].set_slot((uint16_t)pslot(metric_col[j]));
-      packed = true;
+      packed = true; packed_use = use;
       packed_compressed = use->compressed;
       packed_bits = use->bits; packed_rec = use->rec_bytes;
       if (qpay_want && use->bits && use->rec_bytes == 4) { qpay = 4; qpay_slot = pslot(gcols[0]); }      // (a bit-field record's members all start at the record: any member's slot is the record's)

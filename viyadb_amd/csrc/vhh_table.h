@@ -40,6 +40,19 @@ struct VhExec {
   hipStream_t stream() const { return g_ctx.stream != g_ctx.own_stream ? g_ctx.stream : own_stream; }
 };
 
+// The GROUPED form of a 4-byte bit-record projection (vh_grouped.h, group_bits_kernel): a second copy of the records in which every tile of
+// 2048 rows is stable-sorted by the field a bit-sliced predicate projection keeps of column `col` (`bits` bits, at most VH_GROUP_MAX_BITS),
+// and the tiles' headers. It belongs to its projection (same stride, dropped and grown with it) but follows the journal by itself: its jobs are
+// whole tiles. A plan reads it only while it is as current as the planes whose bits give the places (QueryBuild::choose_grouped).
+struct VhGrouped {
+  int col = -1; uint32_t bits = 0;
+  char* base = nullptr;             // records: VhPack::stride bytes per segment
+  char* hdr = nullptr; uint64_t hdr_stride = 0;      // headers: (2 << bits) bytes per tile, hdr_stride per segment
+  uint32_t cap_seg = 0;
+  std::vector<uint64_t> seg_mod; uint64_t applied_epoch = 0;
+  size_t bytes(uint64_t stride) const { return (size_t)cap_seg * stride + 256; }
+  size_t hdr_bytes() const { return (size_t)cap_seg * hdr_stride + 256; }
+};
 // Payload projection (vh_table_pack): a row-major copy of a few columns, see pack_kernel.
 struct VhPack {
   std::vector<int> cols;            // table column indices, in record order (widest first)
@@ -56,6 +69,7 @@ struct VhPack {
   uint64_t applied_epoch = 0;       // every change of the table's journal up to this epoch is in the records
   uint64_t serial = 0;              // vh_table::layout_serial when it was built: which projection this is (derived_settle; addresses get reused)
   bool automatic = false;
+  std::unique_ptr<VhGrouped> grouped;      // its grouped form, if one was built (bit-field records of 4 bytes only)
   int col_index(int col) const { for (size_t i = 0; i < cols.size(); ++i) if (cols[i] == col) return (int)i; return -1; }
 };
 // Narrow copy of a predicate column (vh_table_narrow): an unsigned 32-bit column whose values fit 8 or 16 bits, kept a second time
@@ -302,7 +316,7 @@ extern "C" void vh_table_destroy(vh_table* t) {
   if (t->h_sync) (void)hipHostFree(t->h_sync);
   if (t->h_stage) (void)hipHostFree(t->h_stage);
   if (t->d_packflag) (void)hipFree(t->d_packflag);
-  for (auto& pk : t->packs) if (pk->base) (void)hipFree(pk->base);
+  for (auto& pk : t->packs) { if (pk->base) (void)hipFree(pk->base); if (pk->grouped) { (void)hipFree(pk->grouped->base); (void)hipFree(pk->grouped->hdr); } }
   for (auto& nw : t->narrows) if (nw->base) (void)hipFree(nw->base);
   for (auto& pp : t->predpacks) for (char* b : pp->pbase) if (b) (void)hipFree(b);
   if (t->h_jobs) (void)hipHostFree(t->h_jobs);

@@ -92,6 +92,7 @@ class AggResult:
     tuple4: bool = False           # DENSE_PART's one-word tuples were four bytes (gid and values in 32 bits)
     pack_bits: bool = False        # the projection's records are bit fields
     pack_rec_bytes: int = 0        # bytes of one projection record (0: no projection was read)
+    grouped_payload: bool = False  # the records were gathered from the projection's grouped form (tiles sorted by an equality column)
 
 
 
@@ -388,7 +389,8 @@ class DeviceTable:
                          bool(info.reserved & 16), bool(info.reserved & 32), bool(info.reserved & 64), bool(info.reserved & 128), bool(info.reserved & 256),
                          bool(info.reserved & 2048), bool(info.reserved & 8192), bool(info.reserved & 4096), int(info.reserved),
                          bool(info.reserved & 16384), bool(info.reserved & 32768),
-                         (2 << ((info.reserved >> 16) & 7)) if info.reserved & 8 else 0)
+                         (2 << ((info.reserved >> 16) & 7)) if info.reserved & 8 else 0,
+                         bool(info.reserved & capi.INFO_GROUPED_PAYLOAD))
 
     def query_agg(self, plan: AggPlan, copy: bool = True) -> AggResult:
         p, keep = self._build_plan(plan)
