@@ -206,6 +206,8 @@ enum vh_plan_flags {
   VH_PLAN_FORCE_QPAY = 1u << 26,  /* testing: streamed records whenever the plan is eligible, whatever the selectivity */
   VH_PLAN_NO_GROUPED = 1u << 28,  /* ablation: a survivor's record is gathered from the projection's row-order records even where its grouped form
                                      (tiles of 2048 rows sorted by a narrow column the filter compares for equality) exists */
+  VH_PLAN_NO_GPLANES = 1u << 29,  /* ablation: a plan that gathers from the grouped records still reads the row-order bit planes, even where the
+                                     planes clustered in the tiles' grouped order exist (an A/B inside one process) */
   VH_PLAN_CARD32 = 1u << 22       /* the cardinality of a 32-bit-id bitset metric (count distinct) is delivered as a uint32 column instead of
                                      uint64 (it cannot exceed 2^32 - 1): vh_result_state_elem() tells what a state column holds */
 };
@@ -272,6 +274,8 @@ typedef struct vh_result_info {
                                 bit 15: the projection's records are bit fields (bits 3 and 7 are set too);
                                 bits 16-18: log2 of the projection's record bytes, less one (4 bytes: 1 ... 64 bytes: 5; 0 when bit 3 is clear);
                                 bit 20: the payload records were gathered from the projection's GROUPED form (bits 3, 7, 13 and 15 are set too);
+                                bit 21: ... and the predicate bits were read from the planes CLUSTERED in the tiles' grouped order: only the words of
+                                        the run of the `==` literal in every tile (bit 20 is set too);
                                 bit 19: (VH_BUILD_BACKGROUND tables) a kernel compile or a layout build for this query's shape is queued or running:
                                         this query ran on what existed (the pre-built kernels, the arenas, layouts already there) */
   uint64_t returned_groups;  /* rows vh_result_copy delivers (= ngroups without HAVING) */

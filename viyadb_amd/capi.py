@@ -33,6 +33,7 @@ PLAN_NO_PACK, PLAN_FORCE_PACK, PLAN_NO_PART2, PLAN_NO_SHAPE, PLAN_NO_NARROW = 40
 PLAN_NO_JIT, PLAN_FORCE_JIT, PLAN_NO_HPART, PLAN_FORCE_HPART, PLAN_NO_HP_PACK, PLAN_CARD32, PLAN_NO_NARROW_TUPLES = 1 << 17, 1 << 18, 1 << 19, 1 << 20, 1 << 21, 1 << 22, 1 << 23
 PLAN_NO_PREDPACK, PLAN_NO_QPAY, PLAN_FORCE_QPAY, PLAN_NO_SLICED = 1 << 24, 1 << 25, 1 << 26, 1 << 27
 PLAN_NO_GROUPED = 1 << 28
+PLAN_NO_GPLANES = 1 << 29
 # paths
 PATH_SCALAR, PATH_DENSE_LDS, PATH_DENSE_GLOBAL, PATH_HASH, PATH_DENSE_PART = range(5)
 PATH_NAMES = ["scalar", "dense_lds", "dense_global", "hash", "dense_part"]
@@ -136,6 +137,7 @@ COMM_ID_BYTES = 128
 BUILD_INLINE, BUILD_BACKGROUND = 0, 1
 INFO_BUILD_PENDING = 1 << 19      # vh_result_info.reserved bit 19
 INFO_GROUPED_PAYLOAD = 1 << 20    # vh_result_info.reserved bit 20
+INFO_GROUPED_PLANES = 1 << 21     # vh_result_info.reserved bit 21
 
 
 class BuildInfo(C.Structure):

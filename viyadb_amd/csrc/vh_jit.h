@@ -57,6 +57,11 @@ struct VhJitShape {
   // AND compares with literal `pp_group_lit` for equality; `pp_group_hdr` is the slot of the tiles' headers. The bit-sliced compacting scan only:
   // a survivor's queue entry is the place of its record, computed from the planes of pp_group the step has loaded anyway. -1: off.
   int pp_group = -1, pp_group_hdr = -1, pp_group_lit = 0;
+  // ... with the CLUSTERED planes beside them (VhGrouped::planes, vh_grouped.h): the other predicate columns' bits in the tiles' grouped order,
+  // word-major, `gp_G` dwords a word group, in slot `gp_slot`; `gp_goff` is the grouping field's bit offset in the row-order projection (the
+  // fields above it lie pp_bits[pp_group] planes lower in a word group). The scan then reads the run of the literal in every tile and nothing
+  // else: no plane of pp_group (no other leaf reads it), no prefix over its masks. -1: off.
+  int gp_slot = -1, gp_G = 0, gp_goff = 0;
   // Streamed payload: every group / metric value of the plan is a bit field of ONE 4-byte record per row (a bit-field projection, VhPack::bits).
   // Instead of queueing a survivor's ROW and gathering its record afterwards (a random 128-byte line per survivor: at 5 % selectivity 81 % of
   // the projection's lines are fetched anyway, at the rate random lines come in), the scan streams the records with the predicate planes —

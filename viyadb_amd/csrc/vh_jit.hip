@@ -15,6 +15,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdarg>
 #include <condition_variable>
@@ -55,6 +56,7 @@ std::string VhJitShape::key() const {
   put(qpay); put(qpay_slot);
   put(pp_sliced); put(pp_slot);
   put(pp_group); put(pp_group_hdr); put(pp_group_lit);
+  put(gp_slot); put(gp_G); put(gp_goff);
   if (pp_sliced) for (int i = 0; i < npred; ++i) { put(pp_off[i]); put(pp_bits[i]); }
   put(pp_nplanes);
   for (int q = 0; q < pp_nplanes; ++q) { put(pp_plane[q].slot); put(pp_plane[q].width); put(pp_plane[q].pos); }
@@ -129,6 +131,11 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
   t += vj_fmt("  static constexpr bool SLICED = %s;\n", s.pp_sliced ? "true" : "false");
   const bool grouped = s.pp_sliced && s.pp_group >= 0 && s.pp_group < s.npred && !s.qpay && !s.lanes;
   t += vj_fmt("  static constexpr bool GROUPED = %s;\n  static constexpr int G_HDR = %d, G_BITS = %d;\n", grouped ? "true" : "false", grouped ? s.pp_group_hdr : 0, grouped ? s.pp_bits[s.pp_group] : 0);
+  // clustered planes: the other predicate columns' planes occupy vg[gbase[p] .. gbase[p] + pp_bits[p]) of a lane (the grouping column has none)
+  const bool gplanes = grouped && s.gp_slot >= 0 && s.gp_G > 0;
+  int gbase[VJ_MAX_PRED] = {}, gnv = 0;
+  if (gplanes) for (int p = 0; p < s.npred; ++p) if (p != s.pp_group) { gbase[p] = gnv; gnv += s.pp_bits[p]; }
+  t += vj_fmt("  static constexpr bool GPLANES = %s;\n  static constexpr int GP_SLOT = %d, GP_G = %d, NVG = %d;\n", gplanes ? "true" : "false", gplanes ? s.gp_slot : 0, gplanes ? s.gp_G : 0, gnv);
   {
     std::vector<int> a, b, c, d, e, f;
     for (int i = 0; i < s.ng; ++i) { a.push_back(s.g[i].type); b.push_back(s.g[i].gran); c.push_back(s.g[i].nroll); d.push_back(s.g[i].micro); e.push_back(s.g[i].key_word); f.push_back(s.g[i].key_shift); }
@@ -160,13 +167,21 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
   // ---- the filter as one expression per row slot (ComparisonBuilder: composites are bitwise & / |, no short circuit), written
   //      twice: over the comparisons' wave ballots (the slot's pass mask, in scalar registers) and over the lane's own bools
   std::vector<std::string> sst;                             // bit-sliced: the lane's 32-row mask
+  const int* leaf_base = sbase;               // where a leaf's planes lie: v[] of the row-order planes, or vg[] of the clustered ones
+  const char* leaf_regs = "v";
+  int leaf_skip = -1;                         // clustered planes: the one leaf on the grouping column is the word's in-run mask, applied by the frame
   auto sliced_leaf = [&](const VhProgOp& o, int op, int lit_idx) {
     const int p = (int)o.pslot(), ty = (int)o.type();
+    if (p == leaf_skip) return std::string("~0u");
     const std::string l = lit_name(lit_idx, ty);
     const bool sgn = ty == VH_I8 || ty == VH_I16 || ty == VH_I32 || ty == VH_I64;
-    return vj_fmt("vj_bits_rel<%d, %d>(v + %d, (uint64_t)%s%s, %s)", s.pp_bits[p], op, sbase[p], sgn ? "(int64_t)" : "", l.c_str(), sgn ? ("(" + l + " < 0)").c_str() : "false");
+    return vj_fmt("vj_bits_rel<%d, %d>(%s + %d, (uint64_t)%s%s, %s)", s.pp_bits[p], op, leaf_regs, leaf_base[p], sgn ? "(int64_t)" : "", l.c_str(), sgn ? ("(" + l + " < 0)").c_str() : "false");
   };
-  if (s.pp_sliced)
+  std::string gp_expr;
+  for (int pass = 0; pass < (gplanes ? 2 : 1) && s.pp_sliced; ++pass) {
+    if (pass == 0 && gplanes) { leaf_base = gbase; leaf_regs = "vg"; leaf_skip = s.pp_group; }       // first the clustered form, then the usual one (sst is left holding it)
+    else { leaf_base = sbase; leaf_regs = "v"; leaf_skip = -1; }
+    sst.clear();
     for (const VhProgOp& o : s.prog) {
       switch (o.kind()) {
         case VH_F_TRUE: sst.push_back("~0u"); break;
@@ -184,6 +199,8 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
         } break;
       }
     }
+    if (pass == 0 && gplanes) gp_expr = sst.empty() ? "~0u" : sst.back();
+  }
   // grouped records: the `==` leaf on the grouping column by itself (the lane's rows that hold the literal), and the literal as an index into
   // a tile's header — ~0u when no value of the field equals it (negative, or beyond the field's bits): the header is never read then
   std::string gmask_fn, glit_fn;
@@ -246,6 +263,27 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
     for (int p = 0; p < s.npred; ++p)
       for (int b = 0; b < s.pp_bits[p]; ++b)
         t += vj_fmt("    v[%d] = in ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(base + %dull * ps)) : 0u;\n", sbase[p] + b, s.pp_off[p] + b);
+    t += "  }\n";
+  }
+  if (gplanes) {
+    // the filter over a word of the clustered planes (the `==` leaf on the grouping column left out), and the lane's loads of a word group: the
+    // planes the filter reads — as 16-byte non-temporal loads when that is the whole group, one dword per plane otherwise
+    t += vj_fmt("  static __device__ __forceinline__ uint32_t gp_mask(const Lits& L, const uint32_t (&vg)[%d]) {\n    (void)L; (void)vg;\n    return %s;\n  }\n", gnv ? gnv : 1, gp_expr.c_str());
+    t += vj_fmt("  static __device__ __forceinline__ void gp_load(const char* grp, uint32_t (&vg)[%d]) {\n    (void)grp; (void)vg;\n", gnv ? gnv : 1);
+    std::vector<int> where((size_t)(gnv ? gnv : 1), -1);      // vg[i] = dword where[i] of the group
+    const int gbits = s.pp_bits[s.pp_group];
+    for (int p = 0; p < s.npred; ++p) if (p != s.pp_group) for (int b = 0; b < s.pp_bits[p]; ++b) { const int pl = s.pp_off[p] + b; where[(size_t)(gbase[p] + b)] = pl < s.gp_goff ? pl : pl - gbits; }
+    std::vector<int> sorted_where(where.begin(), where.begin() + gnv);
+    std::sort(sorted_where.begin(), sorted_where.end());
+    bool whole = gnv == s.gp_G && s.gp_G % 4 == 0;
+    for (int i = 0; i < gnv && whole; ++i) whole = sorted_where[(size_t)i] == i;
+    if (whole) {
+      const char* comp[4] = {"x", "y", "z", "w"};
+      for (int c = 0; c < s.gp_G / 4; ++c) t += vj_fmt("    const vh_u32x4 g%d = __builtin_nontemporal_load(VJ_GLOBAL(vh_u32x4, grp) + %d);\n", c, c);
+      for (int i = 0; i < gnv; ++i) t += vj_fmt("    vg[%d] = g%d.%s;\n", i, where[(size_t)i] / 4, comp[where[(size_t)i] % 4]);
+    } else {
+      for (int i = 0; i < gnv; ++i) t += vj_fmt("    vg[%d] = __builtin_nontemporal_load(VJ_GLOBAL(uint32_t, grp) + %d);\n", i, where[(size_t)i]);
+    }
     t += "  }\n";
   }
   // ---- accessors: the value of predicate column p in row slot I (I = 4 * sub-step + row of the lane's four), in the column's own type
@@ -738,6 +776,7 @@ static bool vj_canonical(int which, VhJitShape* s) {
   VhJitShape& S = *s;
   auto col = [](int slot, int type, int pitch, int rec, int off, int sext) { VhJitCol c; c.slot = slot; c.type = type; c.pitch = pitch; c.rec = rec; c.off = off; c.sext = sext; return c; };
   switch (which) {
+    case 22:    // ... case 21 reading the CLUSTERED planes beside the grouped records (slot 15, 20 dwords a word group: d3 and d4)
     case 19:    // ... case 0 whose tuples leave through the block's ring writer (16 partitions' waiting lines per block, extents by position)
     case 21:    // ... case 14 gathering from the GROUPED records: tiles sorted by d2 (predicate 0, 2 bits), the headers in slot 14
     case 20:    // ... case 9 with the tuple in FOUR bytes (gid 17 + 10 + 2 bits: thirty-two to a line)
@@ -752,8 +791,8 @@ static bool vj_canonical(int which, VhJitShape* s) {
     case 1: {   // ... the same from the 4-byte arenas, straight into the dense HBM table (what an eighth of the table runs)
       const bool ring = which == 18 || which == 19;
       const bool four = which == 20;      // C3's one-word tuples in 4 bytes
-      const bool by_d2 = which == 21;
-      if (which == 21) which = 14;
+      const bool by_d2 = which == 21 || which == 22, clustered = which == 22;
+      if (which == 21 || which == 22) which = 14;
       if (which == 18 || which == 20) which = 9;
       if (which == 19) which = 0;
       const bool part = which == 0 || which == 7 || which == 9 || which == 10 || which == 12 || which == 13 || which == 14;
@@ -770,6 +809,7 @@ static bool vj_canonical(int which, VhJitShape* s) {
         if (which == 9 || which == 10 || which == 12 || which == 13 || which == 14) { S.tw = 1; S.gid_bits = 17; S.m[0].tword = 0; S.m[0].tshift = 17; S.m[0].tbits = 10; S.m[1].tword = 0; S.m[1].tshift = 27; S.m[1].tbits = 2; }
         if (four) S.tuple4 = 1;
         if (by_d2) { S.pp_group = 0; S.pp_group_hdr = 14; S.pp_group_lit = 0; }
+        if (clustered) { S.gp_slot = 15; S.gp_G = 20; S.gp_goff = 0; }
         if (which == 13) { S.qpay = 4; S.qpay_slot = 10; }
         if (which == 14) { S.pp_sliced = 1; S.pp_slot = 7; S.pp_off[0] = 0; S.pp_bits[0] = 2; S.pp_off[1] = 2; S.pp_bits[1] = 10; S.pp_off[2] = 12; S.pp_bits[2] = 10; }
         if (which == 12 || which == 13) {

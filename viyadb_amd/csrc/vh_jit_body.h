@@ -611,7 +611,7 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
     wave_base = useg * P.unit_rows + wave * kWaveRows;
   }
   uint32_t v[J::NV ? J::NV : 1];
-  if (have) {
+  if (have && !J::GPLANES) {
     if (wave_base + kWaveRows <= seg_rows) J::template preload<true>(P, seg, wave_base + lane * kLaneStride, seg_rows, v);
     else J::template preload<false>(P, seg, wave_base + lane * kLaneStride, seg_rows, v);
   }
@@ -620,9 +620,114 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
   uint32_t glit = ~0u, gstart = 0u;
   if constexpr (J::GROUPED) {
     glit = J::glit(L);
-    if (have) gstart = vj_group_start<J>(P, seg, wave_base, seg_rows, glit);
+    if (have && !J::GPLANES) gstart = vj_group_start<J>(P, seg, wave_base, seg_rows, glit);
   }
   uint32_t cnt = 0;
+  if constexpr (J::GPLANES) {
+    // ---- CLUSTERED planes (vh_grouped.h): the predicate bits of a tile lie in the order of its grouped records, word-major. The wave reads
+    // only the words that cover the run [start[literal], end) of each of its tiles — no plane of the grouping column, no prefix over its
+    // masks: a survivor's place IS its bit position. A run is about a quarter of a tile, so a lane-per-word step over ONE tile would leave
+    // most lanes without loads; instead the wave takes up to 64 of its tiles at a time (lane t keeps tile t's first row and run), deals the
+    // words of all their runs out to its lanes, 64 a batch — item k belongs to the tile whose inclusive prefix of word counts first exceeds k,
+    // found by a binary search over the lanes (six ds_bpermute) — and puts the next batch's loads in flight before it drains this batch's
+    // survivors. The next group's headers travel while this group's batches run. The same tiles in the same order as the row-order scan
+    // (unit decomposition, counters, flush at a segment change, vj_drain): the host cannot tell the two apart.
+    static_assert(J::GROUPED && J::SLICED && !J::LANES && J::QPAY == 0, "clustered planes belong to the grouped records");
+    constexpr uint32_t G = (uint32_t)J::GP_G;
+    if (glit == ~0u) have = false;              // no value of the field equals the literal: nothing is queued (the headers are never indexed with it)
+    const uint32_t nvals = 1u << J::G_BITS;
+    // the next up to 64 tiles of this wave that lie in ONE segment and begin below its snapshot; their header loads are issued, not awaited
+    auto collect = [&](uint32_t& c_n, uint32_t& c_seg, uint32_t& c_base, uint32_t& c_start, uint32_t& c_end) {
+      c_n = 0; c_seg = seg; c_base = 0; c_start = 0; c_end = 0;
+      uint32_t c_rows = 0;
+      while (have && c_n < 64u && (c_n == 0u || seg == c_seg)) {
+        if (wave_base < seg_rows) {
+          if (c_n == 0u) c_seg = seg;
+          if ((uint32_t)lane == c_n) { c_base = wave_base; c_rows = seg_rows; }
+          ++c_n;
+        }
+        wave_base += kStepRows;
+        if (++ustep == spu) {
+          ustep = 0;
+          unit += gridDim.x;
+          have = unit < P.total_units;
+          useg += gmod; seg += gdiv;
+          if (useg >= P.units_per_seg) { useg -= P.units_per_seg; ++seg; }
+          if (have) { seg_rows = P.seg_rows[seg]; wave_base = useg * P.unit_rows + wave * kWaveRows; }
+        }
+      }
+      if ((uint32_t)lane < c_n) {
+        const uint16_t* h = reinterpret_cast<const uint16_t*>(P.colbase[J::G_HDR] + (uint64_t)c_seg * P.colstride[J::G_HDR] + vh_grouped_hdr_off(c_base / VH_GROUP_TILE, J::G_BITS));
+        const uint32_t valid = c_rows - c_base < VH_GROUP_TILE ? c_rows - c_base : VH_GROUP_TILE;
+        c_start = h[glit];
+        c_end = glit + 1u < nvals ? (uint32_t)h[glit + 1u] : valid;       // (the field's last value: the run ends with the tile's valid rows)
+        if (c_end > valid) c_end = valid;                               // (a run never leaves the tile's block, whatever a header says)
+        if (c_start > c_end) c_start = c_end;
+      }
+    };
+    auto drain_gp = [&](uint32_t dseg, bool all) {
+      while (cnt >= 64 || (all && cnt)) {
+        const uint32_t take = cnt >= 64 ? 64u : cnt;
+        cnt -= take;
+        const bool act = (uint32_t)lane < take;
+        const uint32_t r = act ? q[cnt + lane] : 0u;
+        vj_drain<J>(P, dseg, r, act, lds, xoff, nfresh, V);
+        __builtin_amdgcn_wave_barrier();
+      }
+    };
+    uint32_t a_n, a_seg, a_base, a_start, a_end;
+    collect(a_n, a_seg, a_base, a_start, a_end);
+    while (a_n) {
+      const uint32_t first = vh_gplanes_first_word(a_start), nw = vh_gplanes_last_word(a_start, a_end) - first;     // (lanes >= a_n: 0 words)
+      uint32_t incl = nw;
+#pragma unroll
+      for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off); if (lane >= off) incl += o; }
+      const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+      uint32_t b_n, b_seg, b_base, b_start, b_end;
+      collect(b_n, b_seg, b_base, b_start, b_end);
+      const bool flush = !b_n || b_seg != a_seg;        // queue entries are places of segment a_seg
+      const char* const pseg = P.colbase[J::GP_SLOT] + (uint64_t)a_seg * P.colstride[J::GP_SLOT];
+      uint32_t vg[J::NVG ? J::NVG : 1];
+      uint32_t i_place = 0, i_mask = 0;                  // the lane's item of the batch in flight: its word's first place in the segment, its in-run mask
+      auto fetch = [&](uint32_t k0) {
+        const uint32_t k = k0 + (uint32_t)lane;
+        uint32_t t = 0;
+#pragma unroll
+        for (uint32_t step = 32u; step; step >>= 1) { const uint32_t iv = (uint32_t)__shfl((int)incl, (int)(t + step - 1u)); if (iv <= k) t += step; }
+        const bool act = k < total;
+        t &= 63u;
+        const uint32_t t_excl = (uint32_t)__shfl((int)(incl - nw), (int)t), t_first = (uint32_t)__shfl((int)first, (int)t);
+        const uint32_t t_base = (uint32_t)__shfl((int)a_base, (int)t), t_start = (uint32_t)__shfl((int)a_start, (int)t), t_end = (uint32_t)__shfl((int)a_end, (int)t);
+        const uint32_t word = act ? t_first + (k - t_excl) : 0u;
+        i_place = t_base + 32u * word;
+        i_mask = act ? vh_gplanes_word_mask(word, t_start, t_end) : 0u;
+        if (act) J::gp_load(pseg + vh_gplanes_off(t_base / VH_GROUP_TILE, word, G), vg);
+        else {
+#pragma unroll
+          for (int z = 0; z < (J::NVG ? J::NVG : 1); ++z) vg[z] = 0u;
+        }
+      };
+      if (total) fetch(0u);
+      for (uint32_t k0 = 0; k0 < total; k0 += 64u) {
+        const uint32_t m = J::gp_mask(L, vg) & i_mask, place = i_place;
+        if (k0 + 64u < total) fetch(k0 + 64u);           // the next batch travels while this one's survivors are drained
+        const uint32_t cnt0 = cnt;
+        vj_push_mask(q, cnt, lane < 32 ? m : 0u, place, lane);      // (two halves by lanes: at most 1 024 places join the queue between two drains)
+        npassed += cnt - cnt0;
+        __builtin_amdgcn_wave_barrier();
+        drain_gp(a_seg, false);
+        const uint32_t cnt1 = cnt;
+        vj_push_mask(q, cnt, lane < 32 ? 0u : m, place, lane);
+        npassed += cnt - cnt1;
+        __builtin_amdgcn_wave_barrier();
+        drain_gp(a_seg, flush && k0 + 64u >= total);
+      }
+      if (!total && flush) drain_gp(a_seg, true);
+      a_n = b_n; a_seg = b_seg; a_base = b_base; a_start = b_start; a_end = b_end;
+      if (MODE == VH_MODE_HASH && V.H.dead) a_n = 0u;     // this wave saw the table overflow: the attempt is void (see scan_agg_kernel)
+    }
+    have = false;
+  }
   if constexpr (J::LANES) {
     uint32_t lane_passed = 0;
     while (have) {

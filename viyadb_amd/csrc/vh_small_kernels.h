@@ -845,11 +845,18 @@ struct VhGroupArgs {
   VhPackBitsArgs B;                    // the records: columns, fields, destination = the grouped arena (same stride as the ungrouped one)
   const char* gsrc; uint64_t gsrc_stride; uint32_t gesize, gbits;
   char* hdr; uint64_t hdr_stride;      // the headers: bytes between segments
+  // clustered predicate planes (vh_grouped.h; planes == nullptr: none): the bit-sliced predicate projection's source columns and fields — a row's
+  // field word is formed as predslice_kernel forms it —, the grouping column's field in that word, and the arena (G dwords a word group)
+  int32_t pncols; uint32_t goff, G;
+  const char* psrc[VH_PACK_MAX_COLS]; uint64_t psrc_stride[VH_PACK_MAX_COLS];
+  uint32_t pesize[VH_PACK_MAX_COLS], pbitoff[VH_PACK_MAX_COLS];
+  char* planes; uint64_t planes_stride;
 };
 __global__ __launch_bounds__(256) void group_bits_kernel(const VhGroupArgs A) {
   constexpr uint32_t NL = VH_GROUP_TILE / 32u;             // lanes of the scan's wave step
-  __shared__ uint32_t s_rec[VH_GROUP_TILE], s_out[VH_GROUP_TILE];
-  __shared__ uint8_t s_val[VH_GROUP_TILE];
+  constexpr uint32_t NK = VH_GROUP_TILE / 256u;            // rows a thread owns: k * 256 + threadIdx.x — their records, values and field words stay in registers
+  __shared__ __attribute__((aligned(16))) uint32_t s_out[VH_GROUP_TILE];
+  __shared__ uint32_t s_pout[VH_GROUP_TILE];               // clustered planes: the rows' field words in grouped order
   __shared__ uint32_t s_eq[1 << VH_GROUP_MAX_BITS][NL];       // value v, lane l: the lane's rows that hold v
   __shared__ uint16_t s_before[1 << VH_GROUP_MAX_BITS][NL];   // ... and how many rows of the lanes below it do
   __shared__ uint16_t s_total[1 << VH_GROUP_MAX_BITS], s_start[1 << VH_GROUP_MAX_BITS];
@@ -858,10 +865,27 @@ __global__ __launch_bounds__(256) void group_bits_kernel(const VhGroupArgs A) {
   const uint32_t nvalid = J.seg_rows > tile_base ? (J.seg_rows - tile_base < VH_GROUP_TILE ? J.seg_rows - tile_base : VH_GROUP_TILE) : 0u;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   bool ovf = false;
-  for (uint32_t k = 0; k < VH_GROUP_TILE / 256u; ++k) {
+  uint32_t r_rec[NK], r_pw[NK], r_val[NK];
+#pragma unroll
+  for (uint32_t k = 0; k < NK; ++k) {
     const uint32_t i = k * 256u + threadIdx.x, row = tile_base + i;
     const bool valid = i < nvalid;
-    uint64_t rec = 0; uint32_t val = 0;
+    uint64_t rec = 0; uint32_t val = 0, pword = 0;
+    if (valid && A.planes) {
+      for (int c = 0; c < A.pncols; ++c) {
+        const char* s = A.psrc[c] + (uint64_t)seg * A.psrc_stride[c] + (uint64_t)row * A.pesize[c];
+        uint32_t v;
+        switch (A.pesize[c]) {
+          case 1: v = *reinterpret_cast<const uint8_t*>(s); break;
+          case 2: v = *reinterpret_cast<const uint16_t*>(s); break;
+          case 4: v = *reinterpret_cast<const uint32_t*>(s); break;
+          default: v = (uint32_t)*reinterpret_cast<const uint64_t*>(s); break;
+        }
+        pword |= v << A.pbitoff[c];
+      }
+      pword = vh_gplanes_squeeze(pword, A.goff, A.gbits);
+    }
+    r_pw[k] = pword; s_pout[i] = 0u;          // (places at or beyond the valid rows stay zero)
     if (valid) {
       for (int c = 0; c < A.B.ncols; ++c) {
         const char* s = A.B.src[c] + (uint64_t)seg * A.B.src_stride[c] + (uint64_t)row * A.B.esize[c];
@@ -884,7 +908,7 @@ __global__ __launch_bounds__(256) void group_bits_kernel(const VhGroupArgs A) {
       }
       val &= nvals - 1u;
     }
-    s_rec[i] = (uint32_t)rec; s_val[i] = (uint8_t)val;
+    r_rec[k] = (uint32_t)rec; r_val[k] = val;
     // a wave's 64 rows are two lanes of the scan: the ballot of "holds v" is their two masks
     for (uint32_t v = 0; v < nvals; ++v) {
       const unsigned long long m = __ballot(valid && val == v);
@@ -908,13 +932,35 @@ __global__ __launch_bounds__(256) void group_bits_kernel(const VhGroupArgs A) {
     reinterpret_cast<uint16_t*>(A.hdr + (uint64_t)seg * A.hdr_stride + vh_grouped_hdr_off(tile_base / VH_GROUP_TILE, A.gbits))[threadIdx.x] = (uint16_t)st;
   }
   __syncthreads();
-  for (uint32_t i = threadIdx.x; i < nvalid; i += 256u) {
-    const uint32_t v = s_val[i], l = i >> 5;
-    s_out[vh_grouped_pos(s_eq[v][l], s_before[v][l], s_start[v], i & 31u)] = s_rec[i];      // (a permutation of [0, nvalid): every valid row has exactly one place)
+#pragma unroll
+  for (uint32_t k = 0; k < NK; ++k) {
+    const uint32_t i = k * 256u + threadIdx.x;
+    if (i >= nvalid) continue;
+    const uint32_t v = r_val[k], l = i >> 5;
+    const uint32_t at = vh_grouped_pos(s_eq[v][l], s_before[v][l], s_start[v], i & 31u);      // (a permutation of [0, nvalid): every valid row has exactly one place)
+    s_out[at] = r_rec[k]; s_pout[at] = r_pw[k];
   }
   __syncthreads();
   uint32_t* dst = reinterpret_cast<uint32_t*>(A.B.dst + (uint64_t)seg * A.B.dst_stride) + tile_base;
   for (uint32_t i = threadIdx.x; i < nvalid; i += 256u) dst[i] = s_out[i];
+  if (A.planes) {
+    // the tile's block, word-major: a wave takes 64 places = two words a step, the ballot of "bit b of my place's word" is plane b's two dwords
+    // (as predslice_kernel); lanes b >= the planes write the group's padding. Staged in s_out (once the records have left it), stored as whole lines.
+    const uint32_t G = A.G;
+    __syncthreads();
+    for (uint32_t k = wave; k < VH_GROUP_TILE / 64u; k += 4u) {
+      const uint32_t word = s_pout[k * 64u + lane];
+      unsigned long long mine = 0ull;
+      for (uint32_t b = 0; b < G; ++b) {
+        const unsigned long long m = __ballot((word >> b) & 1u);
+        if ((uint32_t)lane == b) mine = m;
+      }
+      if ((uint32_t)lane < G) { s_out[(2u * k) * G + lane] = (uint32_t)mine; s_out[(2u * k + 1u) * G + lane] = (uint32_t)(mine >> 32); }
+    }
+    __syncthreads();
+    vh_u32x4* out = reinterpret_cast<vh_u32x4*>(A.planes + (uint64_t)seg * A.planes_stride + vh_gplanes_off(tile_base / VH_GROUP_TILE, 0u, G));
+    for (uint32_t i = threadIdx.x; i < VH_GROUP_WORDS * G / 4u; i += 256u) out[i] = reinterpret_cast<const vh_u32x4*>(s_out)[i];
+  }
   if (ovf) atomicOr(A.B.overflow, 1u);
 }
 

@@ -91,6 +91,7 @@ struct VhBuildJob {
   VhJitShape shape;                    // VB_KERNEL
   std::vector<int> cols;               // layouts: the column set (VB_NARROW: one column; VB_GROUPED: the grouping column)
   uint32_t gbits = 0; uint64_t serial = 0;      // VB_GROUPED: the grouping column's field bits, and VhPack::serial of the projection the form belongs to
+  uint64_t pp_serial = 0;              // ... and VhPredPack::serial of the bit-sliced predicate projection whose other columns' bits it keeps clustered (0: none)
   bool form = false, automatic = true; // VB_PACK: compressed records; VB_PREDPACK: bit-sliced planes
   std::string seen;                    // the sightings counter that asked (reset when the job comes to nothing)
   std::atomic<bool> cancel{false};
@@ -166,9 +167,9 @@ static bool build_request_layout(vh_table* t, int kind, const std::vector<int>& 
 
 // The grouped form (VhGrouped) of projection `serial` by column `col`. It is no layout of its own but a second form of a projection that
 // exists, so its job is short: grouped_build under t->mu (build_run_grouped), the kernel enqueued on the library's stream like any refresh.
-static bool build_request_grouped(vh_table* t, uint64_t serial, int col, uint32_t bits, const std::string& seen, const vh_plan* plan) {
-  const std::string key = "g:" + std::to_string(serial) + ":" + std::to_string(col) + ":" + std::to_string(bits);
-  return build_queue(t, VB_GROUPED, key, [&](VhBuildJob& j) { j.cols.assign(1, col); j.gbits = bits; j.serial = serial; j.seen = seen; }, plan);
+static bool build_request_grouped(vh_table* t, uint64_t serial, uint64_t pp_serial, int col, uint32_t bits, const std::string& seen, const vh_plan* plan) {
+  const std::string key = "g:" + std::to_string(serial) + ":" + std::to_string(col) + ":" + std::to_string(bits) + ":" + std::to_string(pp_serial);
+  return build_queue(t, VB_GROUPED, key, [&](VhBuildJob& j) { j.cols.assign(1, col); j.gbits = bits; j.serial = serial; j.pp_serial = pp_serial; j.seen = seen; }, plan);
 }
 
 static void build_arenas_moving(vh_table* t) {
@@ -265,11 +266,17 @@ static int build_run_kernel(VhBuildJob* j) {
 }
 
 // (t->mu held) Room for the grouped form of `pk` under the rule every automatic layout is built by: a quarter of the device stays free.
-static bool grouped_room(const vh_table* t, const VhPack* pk) {
+// 0: none; 1: for the grouped records; 2: for the clustered planes of `pp` (gbits of whose bits are the grouping column's) as well. What a form
+// that is about to be replaced holds counts as free.
+static int grouped_room(const vh_table* t, const VhPack* pk, const VhPredPack* pp = nullptr, uint32_t gbits = 0) {
   size_t free_b = 0, total_b = 0;
   const size_t need = (size_t)t->cap_seg * pk->stride;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
-  return free_b > need + total_b / 4;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return 0; }
+  if (const VhGrouped* gr = pk->grouped.get()) free_b += (gr->base ? gr->bytes(pk->stride) : 0) + (gr->planes ? gr->planes_bytes() : 0);
+  if (free_b <= need + total_b / 4) return 0;
+  if (!pp || !pp->sliced || pp->bits <= gbits) return 1;
+  const size_t planes = (size_t)t->cap_seg * vh_gplanes_seg_bytes(t->segment_rows, vh_gplanes_group(pp->bits - gbits));
+  return free_b > need + planes + total_b / 4 ? 2 : 1;
 }
 static int build_run_grouped(VhBuildJob* j) {
   vh_table* t = j->t;
@@ -281,9 +288,13 @@ static int build_run_grouped(VhBuildJob* j) {
     if (sync_resolve(t)) return 1;
     VhPack* pk = nullptr;
     for (auto& q : t->packs) if (q->serial == j->serial) pk = q.get();
-    if (pk && pk->grouped) return 0;          // (vh_table_prepare or the worker's own query was faster; one grouped form per projection)
-    if (pk && grouped_room(t, pk)) {
-      if (grouped_build(t, pk, j->cols[0], j->gbits) != VH_OK) { (void)hipGetLastError(); outcome = 1; }
+    VhPredPack* pp = nullptr;
+    for (auto& q : t->predpacks) if (j->pp_serial && q->serial == j->pp_serial) pp = q.get();
+    if (pk && pk->grouped && (!pp || (pk->grouped->planes && pk->grouped->pp_serial == pp->serial))) return 0;          // (vh_table_prepare or the worker's own query was faster; one grouped form per projection)
+    const int room = pk ? grouped_room(t, pk, pp, j->gbits) : 0;
+    if (pk && pk->grouped && room < 2) return 0;          // (no room for the planes it lacks: the records it has stay)
+    if (room) {
+      if (grouped_build(t, pk, j->cols[0], j->gbits, room == 2 ? pp : nullptr) != VH_OK) { (void)hipGetLastError(); outcome = 1; }
       else if (pk->grouped) outcome = 0;
     }
     if (outcome != 0) t->gather_seen[j->seen] = 0;      // the job came to nothing: the sightings start again

@@ -104,7 +104,19 @@ static void grouped_drop(vh_table* t, VhPack* pk) {      // (the caller quiesced
   if (!gr) return;
   if (gr->base) { (void)hipFree(gr->base); t->device_bytes -= gr->bytes(pk->stride); }
   if (gr->hdr) { (void)hipFree(gr->hdr); t->device_bytes -= gr->hdr_bytes(); }
+  if (gr->planes) { (void)hipFree(gr->planes); t->device_bytes -= gr->planes_bytes(); }
   pk->grouped.reset();
+}
+// The clustered planes' fields: those of bit-sliced predicate projection `pp` without the grouping column's. false: `pp` has nothing to cluster
+// (it lacks the grouping column, or holds no other).
+static bool grouped_planes_describe(const vh_table* t, VhGrouped* gr, const VhPredPack* pp) {
+  if (!pp || !pp->sliced) return false;
+  const size_t at = (size_t)(std::find(pp->cols.begin(), pp->cols.end(), gr->col) - pp->cols.begin());
+  if (at >= pp->cols.size() || pp->bitw[at] != gr->bits || pp->bits <= gr->bits || pp->bits > 32) return false;
+  gr->G = vh_gplanes_group(pp->bits - gr->bits); gr->goff = pp->bitoff[at];
+  gr->planes_stride = vh_gplanes_seg_bytes(t->segment_rows, gr->G);
+  gr->pp_serial = pp->serial; gr->pp_cols = pp->cols; gr->pp_bitoff = pp->bitoff; gr->pp_bitw = pp->bitw;
+  return true;
 }
 // Re-derive the tiles that hold a row journalled since the grouped form was last current: derived_jobs' ranges widened to whole tiles (one
 // changed row moves the places of its tile's rows behind it), one block per tile. A projection that grew starts over in new buffers.
@@ -116,6 +128,7 @@ static int grouped_refresh(vh_table* t, VhPack* pk) {
     HIP_TRY(hipStreamSynchronize(g_ctx.stream)); derived_waited(t);
     if (gr->base) { (void)hipFree(gr->base); t->device_bytes -= gr->bytes(pk->stride); gr->base = nullptr; }
     if (gr->hdr) { (void)hipFree(gr->hdr); t->device_bytes -= gr->hdr_bytes(); gr->hdr = nullptr; }
+    if (gr->planes) { (void)hipFree(gr->planes); t->device_bytes -= gr->planes_bytes(); gr->planes = nullptr; }
     gr->cap_seg = t->cap_seg;
     if (hipMalloc(&gr->base, gr->bytes(pk->stride)) != hipSuccess || hipMalloc(&gr->hdr, gr->hdr_bytes()) != hipSuccess) {      // no room: the ungrouped records answer
       (void)hipGetLastError();
@@ -126,6 +139,10 @@ static int grouped_refresh(vh_table* t, VhPack* pk) {
     }
     trace_alloc("grouped projection", gr->base, gr->bytes(pk->stride));
     t->device_bytes += gr->bytes(pk->stride) + gr->hdr_bytes();
+    if (gr->G) {          // the clustered planes, where there is room for them; the grouped records alone otherwise
+      if (hipMalloc(&gr->planes, gr->planes_bytes()) != hipSuccess) { (void)hipGetLastError(); gr->planes = nullptr; gr->G = 0; gr->pp_serial = 0; }
+      else { trace_alloc("clustered planes", gr->planes, gr->planes_bytes()); t->device_bytes += gr->planes_bytes(); }
+    }
     gr->seg_mod.assign(t->cap_seg, 0);
     gr->applied_epoch = 0;
   }
@@ -153,6 +170,14 @@ static int grouped_refresh(vh_table* t, VhPack* pk) {
     const VhColumn& gc = t->cols[gr->col];
     A.gsrc = gc.base; A.gsrc_stride = gc.stride; A.gesize = (uint32_t)gc.esize; A.gbits = gr->bits;
     A.hdr = gr->hdr; A.hdr_stride = gr->hdr_stride;
+    if (gr->planes) {
+      A.pncols = (int32_t)gr->pp_cols.size(); A.goff = gr->goff; A.G = gr->G;
+      for (size_t c = 0; c < gr->pp_cols.size(); ++c) {
+        const VhColumn& col = t->cols[gr->pp_cols[c]];
+        A.psrc[c] = col.base; A.psrc_stride[c] = col.stride; A.pesize[c] = (uint32_t)col.esize; A.pbitoff[c] = gr->pp_bitoff[c];
+      }
+      A.planes = gr->planes; A.planes_stride = gr->planes_stride;
+    }
     hipLaunchKernelGGL(group_bits_kernel, dim3((unsigned)jobs.size()), dim3(256), 0, g_ctx.stream, A);
     HIP_TRY(hipGetLastError());
     if (int rc = derived_enqueued(t)) return rc;
@@ -163,9 +188,11 @@ static int grouped_refresh(vh_table* t, VhPack* pk) {
 }
 // The grouped form of `pk` by column `col`, whose field in the bit-sliced planes has `bits` bits: built (or built again for another column or
 // width) and brought up to date. Bit-field records of 4 bytes only; nullptr and VH_OK where there is no room for it.
-static int grouped_build(vh_table* t, VhPack* pk, int col, uint32_t bits) {
+// `pp`: the bit-sliced predicate projection whose other columns' bits are kept clustered beside the records (nullptr: records alone — no such
+// projection, or no room). A form whose planes belong to another projection than `pp` starts over: records, headers and planes are one launch.
+static int grouped_build(vh_table* t, VhPack* pk, int col, uint32_t bits, const VhPredPack* pp = nullptr) {
   if (!pk->bits || pk->rec_bytes != 4 || bits == 0 || bits > VH_GROUP_MAX_BITS || col < 0 || (size_t)col >= t->cols.size()) return VH_OK;
-  if (pk->grouped && (pk->grouped->col != col || pk->grouped->bits != bits)) {
+  if (pk->grouped && (pk->grouped->col != col || pk->grouped->bits != bits || (pp && (!pk->grouped->planes || pk->grouped->pp_serial != pp->serial)))) {
     table_quiesce(t);
     HIP_TRY(hipStreamSynchronize(g_ctx.stream)); derived_waited(t);
     grouped_drop(t, pk);
@@ -175,6 +202,7 @@ static int grouped_build(vh_table* t, VhPack* pk, int col, uint32_t bits) {
     pk->grouped->col = col; pk->grouped->bits = bits;
     const uint64_t tiles = (t->segment_rows + VH_GROUP_TILE - 1) / VH_GROUP_TILE;
     pk->grouped->hdr_stride = (tiles * vh_grouped_hdr_bytes(bits) + 63) / 64 * 64;
+    (void)grouped_planes_describe(t, pk->grouped.get(), pp);
   }
   return grouped_refresh(t, pk);
 }
@@ -479,6 +507,12 @@ static void predpack_drop(vh_table* t, size_t k) {
   (void)hipStreamSynchronize(g_ctx.stream); derived_waited(t);
   VhPredPack* pp = t->predpacks[k].get();
   for (int q = 0; q < pp->nplanes; ++q) if (pp->pbase[q]) { (void)hipFree(pp->pbase[q]); t->device_bytes -= (size_t)pp->cap_seg * pp->pstride[q] + 256; }
+  for (auto& pk : t->packs) {       // clustered planes derived from it go with it (the grouped records stay)
+    VhGrouped* gr = pk->grouped.get();
+    if (!gr || gr->pp_serial != pp->serial) continue;
+    if (gr->planes) { (void)hipFree(gr->planes); t->device_bytes -= gr->planes_bytes(); gr->planes = nullptr; }
+    gr->G = 0; gr->pp_serial = 0;
+  }
   t->predpacks.erase(t->predpacks.begin() + (long)k);
 }
 static void predpack_launch(const vh_table* t, const VhPredPack* pp, const VhJob* d_jobs, size_t njobs, hipStream_t st) {
@@ -641,12 +675,12 @@ extern "C" int vh_table_pack(vh_table* t, const int32_t* cols, int32_t ncols) { 
 // 2 MB-aligned virtual addresses, so it is nothing a process can compute). What a process can do is try: derived_move copies every layout `which`
 // names (1: projections, 2: predicate planes) to FRESH allocations while the old ones are still held — so that the new ones are other pages —
 // and swaps the pointers (kernels take addresses as arguments); the caller measures and keeps or gives back (vh_table_prepare, vh_table_relocate).
-struct VhMoved {       // kind 1: a projection's records, 2: plane `plane` of a predicate projection, 3: a projection's grouped records (its headers stay: 32 bytes a tile); `serial` and `applied_epoch` of the layout at the move
+struct VhMoved {       // kind 1: a projection's records, 2: plane `plane` of a predicate projection, 3: a projection's grouped records (its headers stay: 32 bytes a tile), 4: the clustered planes beside them; `serial` and `applied_epoch` of the layout at the move
   int kind; uint64_t serial, applied_epoch; int plane; char* old_ptr; char* new_ptr; size_t bytes;
 };
 static size_t derived_bytes(const vh_table* t, uint32_t which) {
   size_t b = 0;
-  if (which & 1u) for (auto& pk : t->packs) { if (pk->base) b += (size_t)pk->cap_seg * pk->stride + 256; if (pk->grouped && pk->grouped->base) b += pk->grouped->bytes(pk->stride); }
+  if (which & 1u) for (auto& pk : t->packs) { if (pk->base) b += (size_t)pk->cap_seg * pk->stride + 256; if (pk->grouped && pk->grouped->base) b += pk->grouped->bytes(pk->stride); if (pk->grouped && pk->grouped->planes) b += pk->grouped->planes_bytes(); }
   if (which & 2u) for (auto& pp : t->predpacks) for (int q = 0; q < pp->nplanes; ++q) if (pp->pbase[q]) b += (size_t)pp->cap_seg * pp->pstride[q] + 256;
   return b;
 }
@@ -665,6 +699,7 @@ static int derived_move(vh_table* t, uint32_t which, std::vector<VhMoved>* moved
   int rc = VH_OK;
   if (which & 1u) for (auto& pk : t->packs) if (pk->base && !rc) rc = move(1, pk->serial, pk->applied_epoch, 0, pk->base, (size_t)pk->cap_seg * pk->stride + 256, "projection");
   if (which & 1u) for (auto& pk : t->packs) if (pk->grouped && pk->grouped->base && !rc) rc = move(3, pk->serial, pk->grouped->applied_epoch, 0, pk->grouped->base, pk->grouped->bytes(pk->stride), "grouped projection");
+  if (which & 1u) for (auto& pk : t->packs) if (pk->grouped && pk->grouped->planes && !rc) rc = move(4, pk->serial, pk->grouped->applied_epoch, 0, pk->grouped->planes, pk->grouped->planes_bytes(), "clustered planes");
   if (which & 2u) for (auto& pp : t->predpacks) for (int q = 0; q < pp->nplanes && !rc; ++q) if (pp->pbase[q]) rc = move(2, pp->serial, pp->applied_epoch, q, pp->pbase[q], (size_t)pp->cap_seg * pp->pstride[q] + 256, "predicate plane");
   HIP_TRY(hipStreamSynchronize(g_ctx.stream));
   return rc == VH_E_NOMEM ? VH_OK : rc;          // (out of memory: what could be moved was moved)
@@ -687,6 +722,7 @@ static void derived_settle(vh_table* t, std::vector<VhMoved>& moved, bool keep, 
     uint64_t applied = 0;
     if (m.kind == 1) { for (auto& pk : t->packs) if (pk->serial == m.serial && pk->base == m.new_ptr) { slot = &pk->base; applied = pk->applied_epoch; } }
     else if (m.kind == 3) { for (auto& pk : t->packs) if (pk->serial == m.serial && pk->grouped && pk->grouped->base == m.new_ptr) { slot = &pk->grouped->base; applied = pk->grouped->applied_epoch; } }
+    else if (m.kind == 4) { for (auto& pk : t->packs) if (pk->serial == m.serial && pk->grouped && pk->grouped->planes == m.new_ptr) { slot = &pk->grouped->planes; applied = pk->grouped->applied_epoch; } }
     else { for (auto& pp : t->predpacks) if (pp->serial == m.serial && pp->pbase[m.plane] == m.new_ptr) { slot = &pp->pbase[m.plane]; applied = pp->applied_epoch; } }
     if (slot && !keep && applied == m.applied_epoch) { *slot = m.old_ptr; out->push_back(m.new_ptr); }
     else out->push_back(m.old_ptr);

@@ -82,24 +82,32 @@ void QueryBuild::choose_grouped() {
   const int gcol = jit_pred_col[gp];
   const uint32_t gbits = (uint32_t)js.pp_bits[gp];
   VhGrouped* gr = packed_use->grouped.get();
-  if (!gr || gr->col != gcol || gr->bits != gbits) {
+  // the form is built where it is missing, is another column's, or lacks the clustered planes of the bit-sliced projection this plan reads
+  // (that projection was dropped and described again since): records, headers and planes come out of one launch, so it starts over
+  const bool other = gr && (gr->col != gcol || gr->bits != gbits);
+  const bool bare = gr && !other && sliced_use->bits > gbits && (!gr->planes || gr->pp_serial != sliced_use->serial);
+  auto build = [&]() {
     const int auto_after = g_preparing ? 1 : knobs().auto_pack;
     if (auto_after <= 0) return;
-    if (gr && !g_preparing) return;            // (one grouped form per projection: only a prepared plan replaces another column's)
-    const std::string sig = "g:" + std::to_string(packed_use->serial) + ":" + std::to_string(gcol);
+    if (other && !g_preparing) return;         // (one grouped form per projection: only a prepared plan replaces another column's)
+    const std::string sig = "g:" + std::to_string(packed_use->serial) + ":" + std::to_string(gcol) + (bare ? ":" + std::to_string(sliced_use->serial) : std::string());
     // background build mode: the worker's own query (build_warm), run because the layouts this plan's sightings asked for now exist, builds the
     // form here, off every caller's path; a caller's query that finds projection and planes without it asks for a job after its own sightings
     const bool bg = build_background(t), own = bg && g_build_worker;
     if (!own) {
       if (g_build_quiet) return;
       if (++t->gather_seen[sig] < (uint32_t)auto_after) return;
-      if (bg) { build_pending |= build_request_grouped(t, packed_use->serial, gcol, gbits, sig, p); return; }
+      if (bg) { build_pending |= build_request_grouped(t, packed_use->serial, sliced_use->serial, gcol, gbits, sig, p); return; }
     }
-    if (!grouped_room(t, packed_use)) { t->gather_seen[sig] = 0; return; }
-    if (grouped_build(t, packed_use, gcol, gbits) != VH_OK) { (void)hipGetLastError(); return; }
+    const int room = grouped_room(t, packed_use, sliced_use, gbits);
+    if (!room || (bare && room < 2)) { t->gather_seen[sig] = 0; return; }      // (a form that lacks only its planes is kept where there is no room for them)
+    if (grouped_build(t, packed_use, gcol, gbits, room == 2 ? sliced_use : nullptr) != VH_OK) { (void)hipGetLastError(); return; }
     if (!bg) ++t->inline_builds;
+  };
+  if (!gr || other || bare) {
+    build();
     gr = packed_use->grouped.get();
-    if (!gr) return;
+    if (!gr || gr->col != gcol || gr->bits != gbits) return;
   }
   // as current as the planes whose bits give the places, and as the table: anything else is a stale layout
   if (!gr->base || !gr->hdr || gr->applied_epoch != t->sync_epoch || sliced_use->applied_epoch != t->sync_epoch || packed_use->applied_epoch != t->sync_epoch) return;
@@ -107,6 +115,21 @@ void QueryBuild::choose_grouped() {
   P.colbase[P.nslots] = gr->hdr; P.colstride[P.nslots] = gr->hdr_stride; P.colpitch[P.nslots] = vh_grouped_hdr_bytes(gbits);
   js.pp_group = gp; js.pp_group_hdr = P.nslots++; js.pp_group_lit = (int)g[leaf_of[gp]].lit();
   grouped = true;
+  // The CLUSTERED planes beside the grouped records (vh_grouped.h): the scan reads only the words that cover the run [start[literal], end) of
+  // every tile, and no plane of the grouping column at all. A plan takes them when
+  //   * they exist, derived from the bit-sliced projection this plan reads (same serial), at the same epoch as records and headers (one launch),
+  //   * no filter leaf other than the one `==` leaf reads the grouping column (the planes hold no bit of it),
+  //   * every segment's snapshot is the rows the form was built with or a multiple of the tile (0 included): places have lost their row
+  //     numbers, so a snapshot that cuts into a built tile cannot be honoured — such a plan keeps the row-order planes, as before.
+  // VH_PLAN_NO_GPLANES keeps the row-order planes: an A/B inside one process.
+  if ((p->flags & VH_PLAN_NO_GPLANES) || !gr->planes || !gr->G || gr->pp_serial != sliced_use->serial || P.nslots >= VH_MAX_SLOTS) return;
+  int reads = 0;
+  for (const VhProgOp& o : g) if (o.kind() != VH_F_AND && o.kind() != VH_F_OR && o.kind() != VH_F_TRUE && (int)o.pslot() == gp) ++reads;
+  if (reads != 1) return;
+  for (uint32_t s = 0; s < nseg; ++s) if (x->h_segrows[s] != (uint32_t)t->seg_rows[s] && x->h_segrows[s] % VH_GROUP_TILE != 0) return;
+  P.colbase[P.nslots] = gr->planes; P.colstride[P.nslots] = gr->planes_stride; P.colpitch[P.nslots] = 4u * gr->G;
+  js.gp_slot = P.nslots++; js.gp_G = (int)gr->G; js.gp_goff = (int)gr->goff;
+  gplanes = true;
 }
 
 int QueryBuild::compile_kernel() {
@@ -713,7 +736,7 @@ int QueryBuild::launch() {
   if (jk) { narrowed = jshape.pp_nplanes || jshape.pp_sliced; for (int k = 0; k < jshape.npred; ++k) narrowed |= jshape.pred[k].width != vh_elem_size(jshape.pred[k].type); }
   r->hpart = hpart;
   r->info.reserved = (hpart ? 64 : 0) | (fastj || jk ? 1 : 0) | (lanes ? 2 : 0) | (P.lds_hash_slots ? 4 : 0) | (packed ? 8 : 0) | (fastj && narrowed ? 16 : 0) | (jk ? 32 : 0) | (packed && packed_compressed ? 128 : 0) | (hpart && hp_pack ? 256 : 0) | (mode == VH_MODE_DENSE_PART && P.gid_bits ? 1024 : 0) | (jk && (jshape.pp_nplanes || jshape.pp_sliced) ? 2048 : 0) | (jk && jshape.qpay ? 4096 : 0) | (jk && jshape.pp_sliced ? 8192 : 0) | (mode == VH_MODE_DENSE_PART && P.gid_bits && P.tuple4 ? 16384 : 0)
-                   | (build_pending ? 1u << 19 : 0) | (jk && grouped ? 1u << 20 : 0) | (packed && packed_bits ? 32768 : 0) | (packed ? (uint32_t)(31 - __builtin_clz(std::max<uint32_t>(packed_rec, 2)) - 1) << 16 : 0);
+                   | (build_pending ? 1u << 19 : 0) | (jk && grouped ? 1u << 20 : 0) | (jk && grouped && gplanes ? 1u << 21 : 0) | (packed && packed_bits ? 32768 : 0) | (packed ? (uint32_t)(31 - __builtin_clz(std::max<uint32_t>(packed_rec, 2)) - 1) << 16 : 0);
   if (r->hp_chunks) memset(x->h_chunk, 0, VH_HP_CHUNKS * sizeof(unsigned long long));      // (what the context's previous query left there)
   // a second pass over heavy level-A partitions of a hashed partitioning: from the first pass's tuples when this plan's table can take them as
   // they are (one key word laid out as the first pass's, narrow ids) — else from the table's rows behind the bitmap, like any heavy range

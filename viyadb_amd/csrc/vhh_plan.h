@@ -243,6 +243,7 @@ struct QueryBuild {
   VhPack* packed_use = nullptr;                  // the projection the plan gathers from, and the bit-sliced predicate projection shape_filter found:
   VhPredPack* sliced_use = nullptr;              // what choose_grouped pairs up
   bool grouped = false;                          // the records come from the projection's grouped form (vh_result_info.reserved bit 20)
+  bool gplanes = false;                          // ... and the predicate bits from the clustered planes beside them (bit 21)
   void choose_grouped();                         // compile_kernel: point a qualifying plan at the grouped records (building them where the automatic layouts are built)
   std::vector<int> pp_cols;                      // the filter's columns (ascending) when every leaf reads a fixed-width column: what a predicate projection must hold
   int pp_boff[VJ_MAX_PRED] = {}, pp_bbits[VJ_MAX_PRED] = {}, pp_soff[VJ_MAX_PRED] = {}, pp_sbits[VJ_MAX_PRED] = {};      // predicate column k's bit field in the byte-plane / bit-sliced projection noted in jshape

@@ -52,6 +52,14 @@ struct VhGrouped {
   std::vector<uint64_t> seg_mod; uint64_t applied_epoch = 0;
   size_t bytes(uint64_t stride) const { return (size_t)cap_seg * stride + 256; }
   size_t hdr_bytes() const { return (size_t)cap_seg * hdr_stride + 256; }
+  // CLUSTERED predicate planes (vh_grouped.h): the other columns' bits of the bit-sliced predicate projection `pp_serial`, in the tiles' grouped
+  // order, word-major, G dwords a word. Written by the launch that writes records and headers (one epoch, one refresh path). The fields the
+  // launch reads are copied from the projection when the arena is made; a plan pairs the two by serial, so a projection that was dropped or
+  // re-described never meets planes of other fields. nullptr: none (no room, or no projection yet) — the grouped records alone answer.
+  char* planes = nullptr; uint64_t planes_stride = 0; uint32_t G = 0;
+  uint64_t pp_serial = 0; uint32_t goff = 0;
+  std::vector<int> pp_cols; std::vector<uint8_t> pp_bitoff, pp_bitw;
+  size_t planes_bytes() const { return (size_t)cap_seg * planes_stride + 256; }
 };
 // Payload projection (vh_table_pack): a row-major copy of a few columns, see pack_kernel.
 struct VhPack {
@@ -316,7 +324,7 @@ extern "C" void vh_table_destroy(vh_table* t) {
   if (t->h_sync) (void)hipHostFree(t->h_sync);
   if (t->h_stage) (void)hipHostFree(t->h_stage);
   if (t->d_packflag) (void)hipFree(t->d_packflag);
-  for (auto& pk : t->packs) { if (pk->base) (void)hipFree(pk->base); if (pk->grouped) { (void)hipFree(pk->grouped->base); (void)hipFree(pk->grouped->hdr); } }
+  for (auto& pk : t->packs) { if (pk->base) (void)hipFree(pk->base); if (pk->grouped) { (void)hipFree(pk->grouped->base); (void)hipFree(pk->grouped->hdr); if (pk->grouped->planes) (void)hipFree(pk->grouped->planes); } }
   for (auto& nw : t->narrows) if (nw->base) (void)hipFree(nw->base);
   for (auto& pp : t->predpacks) for (char* b : pp->pbase) if (b) (void)hipFree(b);
   if (t->h_jobs) (void)hipHostFree(t->h_jobs);

@@ -93,6 +93,7 @@ class AggResult:
     pack_bits: bool = False        # the projection's records are bit fields
     pack_rec_bytes: int = 0        # bytes of one projection record (0: no projection was read)
     grouped_payload: bool = False  # the records were gathered from the projection's grouped form (tiles sorted by an equality column)
+    grouped_planes: bool = False   # ... and the predicate bits read from the planes clustered in the same order (the literal's run of every tile only)
 
 
 
@@ -390,7 +391,7 @@ class DeviceTable:
                          bool(info.reserved & 2048), bool(info.reserved & 8192), bool(info.reserved & 4096), int(info.reserved),
                          bool(info.reserved & 16384), bool(info.reserved & 32768),
                          (2 << ((info.reserved >> 16) & 7)) if info.reserved & 8 else 0,
-                         bool(info.reserved & capi.INFO_GROUPED_PAYLOAD))
+                         bool(info.reserved & capi.INFO_GROUPED_PAYLOAD), bool(info.reserved & capi.INFO_GROUPED_PLANES))
 
     def query_agg(self, plan: AggPlan, copy: bool = True) -> AggResult:
         p, keep = self._build_plan(plan)
