@@ -113,8 +113,24 @@ enum vh_fkind {
   VH_F_REL = 1,  /* (col OP lit)               (filter.cc:206-221)           */
   VH_F_IN = 2,   /* OR of == / AND of !=       (filter.cc:223-241)           */
   VH_F_AND = 3,  /* bitwise & of `count` operands, no short circuit (:243-256)*/
-  VH_F_OR = 4    /* bitwise | of `count` operands                            */
+  VH_F_OR = 4,   /* bitwise | of `count` operands                            */
+  VH_F_INSET = 5 /* the VH_F_IN node with the same fields — col, op (1 = IN, 0 = NOT IN), count >= 1, values in lits[lit .. lit + count),
+                    duplicates allowed — and exactly its result and counters, evaluated as ONE set lookup per row however long the list
+                    (viyadb_amd/csrc/vh_inset.h): the values are sorted and de-duplicated once per query into a bitmap (largest - smallest
+                    < 2^20: at most 128 KiB) or a sorted array searched in ceil(log2 n) steps, uploaded with the plan. The values do not
+                    count against VH_PLAN_INLINE_LITS, so a plan with a long list keeps the scan compiled for its shape — and that kernel
+                    does not depend on the list's length or form (editing a list never compiles). For columns of an integer element type
+                    (VH_U8 .. VH_I64: string, time and boolean dimensions, integer numeric dimensions and metrics); VH_F32 / VH_F64 columns
+                    and bitset metrics return VH_E_UNSUPPORTED (the caller keeps VH_F_IN). At most VH_MAX_SETS set leaves per plan
+                    (VH_E_UNSUPPORTED beyond); a set's size is bounded by vh_plan.nlits alone (the 65535-literal limit of a filter counts REL / IN literals, not
+                    set members); not valid in `having`, nor with count < 1 (VH_E_INVALID). The bit-sliced predicate planes,
+                    and the grouped records and clustered planes that rest on them, do not serve a plan with a set leaf: it reads byte
+                    planes, narrow copies or the columns. The library never rewrites a caller's VH_F_IN by itself.                      */
 };
+#define VH_MAX_SETS 4
+/* A plan whose REL / IN leaves carry more literals than this in all is answered by the generic (interpreting) scan kernel, one comparison
+ * per literal and row; at or below it the register-resident kernels and the scan compiled for the plan's shape are eligible. */
+#define VH_PLAN_INLINE_LITS 32
 enum vh_relop { /* same order as query::RelOpFilter::Operator filter.h:60-67 */
   VH_OP_EQ = 0, VH_OP_NE = 1, VH_OP_LT = 2, VH_OP_LE = 3, VH_OP_GT = 4, VH_OP_GE = 5
 };
@@ -208,6 +224,7 @@ enum vh_plan_flags {
                                      (tiles of 2048 rows sorted by a narrow column the filter compares for equality) exists */
   VH_PLAN_NO_GPLANES = 1u << 29,  /* ablation: a plan that gathers from the grouped records still reads the row-order bit planes, even where the
                                      planes clustered in the tiles' grouped order exist (an A/B inside one process) */
+  VH_PLAN_SET_SEARCH = 1u << 30,  /* testing: every set of a VH_F_INSET leaf takes the sorted-array form, whatever its span */
   VH_PLAN_CARD32 = 1u << 22       /* the cardinality of a 32-bit-id bitset metric (count distinct) is delivered as a uint32 column instead of
                                      uint64 (it cannot exceed 2^32 - 1): vh_result_state_elem() tells what a state column holds */
 };
@@ -276,6 +293,8 @@ typedef struct vh_result_info {
                                 bit 20: the payload records were gathered from the projection's GROUPED form (bits 3, 7, 13 and 15 are set too);
                                 bit 21: ... and the predicate bits were read from the planes CLUSTERED in the tiles' grouped order: only the words of
                                         the run of the `==` literal in every tile (bit 20 is set too);
+                                bit 22: the filter's VH_F_INSET leaves were evaluated by set lookup;
+                                bit 23: ... at least one of them by binary search in a sorted array (the others, or all: one bit of a bitmap);
                                 bit 19: (VH_BUILD_BACKGROUND tables) a kernel compile or a layout build for this query's shape is queued or running:
                                         this query ran on what existed (the pre-built kernels, the arenas, layouts already there) */
   uint64_t returned_groups;  /* rows vh_result_copy delivers (= ngroups without HAVING) */
@@ -677,7 +696,7 @@ VH_API int vh_measure_read_bandwidth(uint64_t bytes, int32_t iters, double* byte
 
 /* Test hook for the per-query compiled scan kernels (viyadb_amd/csrc/vh_jit.hip — the GPU analogue of the reference's
  * codegen + Compiler::Compile, src/codegen/compiler.cc:97-144): writes the HIP text for canonical plan shape `which`
- * (0..6) into `text`, compiles it with hipRTC for gfx950 — no GPU needed — and stores the code object at `hsaco_path`
+ * (0..24, see vj_canonical) into `text`, compiles it with hipRTC for gfx950 — no GPU needed — and stores the code object at `hsaco_path`
  * (NULL: nowhere). VH_E_INVALID: no such shape; VH_E_UNSUPPORTED: the compile failed (`text` then starts with the log). */
 VH_API int vh_jit_selftest(int32_t which, const char* hsaco_path, char* text, uint64_t text_bytes);
 

@@ -21,7 +21,9 @@ ELEM_SIZE = [1, 2, 4, 8, 1, 2, 4, 8, 4, 8]
 DIM_STRING, DIM_NUMERIC, DIM_TIME, DIM_BOOLEAN = 0, 1, 2, 3
 METRIC_MAX, METRIC_MIN, METRIC_SUM, METRIC_AVG, METRIC_COUNT, METRIC_BITSET, METRIC_HIDDEN_COUNT = 16, 17, 18, 19, 20, 21, 22
 # enum vh_fkind / vh_relop
-F_TRUE, F_REL, F_IN, F_AND, F_OR = range(5)
+F_TRUE, F_REL, F_IN, F_AND, F_OR, F_INSET = range(6)
+MAX_SETS = 4                      # VH_MAX_SETS: set leaves (F_INSET) per plan
+PLAN_INLINE_LITS = 32             # VH_PLAN_INLINE_LITS
 OP_EQ, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE = range(6)
 # enum vh_time_unit
 T_YEAR, T_MONTH, T_WEEK, T_DAY, T_HOUR, T_MINUTE, T_SECOND, T_NONE = range(8)
@@ -34,6 +36,7 @@ PLAN_NO_JIT, PLAN_FORCE_JIT, PLAN_NO_HPART, PLAN_FORCE_HPART, PLAN_NO_HP_PACK, P
 PLAN_NO_PREDPACK, PLAN_NO_QPAY, PLAN_FORCE_QPAY, PLAN_NO_SLICED = 1 << 24, 1 << 25, 1 << 26, 1 << 27
 PLAN_NO_GROUPED = 1 << 28
 PLAN_NO_GPLANES = 1 << 29
+PLAN_SET_SEARCH = 1 << 30         # testing: every set of an F_INSET leaf takes the sorted-array form
 # paths
 PATH_SCALAR, PATH_DENSE_LDS, PATH_DENSE_GLOBAL, PATH_HASH, PATH_DENSE_PART = range(5)
 PATH_NAMES = ["scalar", "dense_lds", "dense_global", "hash", "dense_part"]
@@ -138,6 +141,8 @@ BUILD_INLINE, BUILD_BACKGROUND = 0, 1
 INFO_BUILD_PENDING = 1 << 19      # vh_result_info.reserved bit 19
 INFO_GROUPED_PAYLOAD = 1 << 20    # vh_result_info.reserved bit 20
 INFO_GROUPED_PLANES = 1 << 21     # vh_result_info.reserved bit 21
+INFO_INSET = 1 << 22              # vh_result_info.reserved bit 22: the filter's set leaves were evaluated by lookup
+INFO_INSET_SEARCH = 1 << 23       # ... bit 23: at least one of them by binary search in a sorted array
 
 
 class BuildInfo(C.Structure):

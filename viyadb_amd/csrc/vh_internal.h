@@ -10,10 +10,12 @@
 #include <stdint.h>
 #include "../../include/viya_hip.h"
 #endif
+#include "vh_inset.h"     // VhSetDev and its lookups (plain C++)
 
 #define VH_MAX_LITS 65535  // literal pool (VhProgOp::lit is 16 bits)
 #define VH_INLINE_PROG 24  // filter programs up to this size (and VH_INLINE_LITS literals) also travel in the kernel arguments, where the
 #define VH_INLINE_LITS 32  // register-resident kernels read them: loads off the kernarg segment are hoisted out of the scan loop, loads through a pointer are not
+static_assert(VH_PLAN_INLINE_LITS == VH_INLINE_LITS, "include/viya_hip.h states the literal budget of the inline program");
 #define VH_MAX_GROUP 16   // group-by columns
 #define VH_MAX_METRIC 20  // selected metrics (+ hidden count)
 #define VH_MAX_SLOTS 32   // distinct columns a query may reference (a payload projection adds one slot per gathered column)
@@ -259,6 +261,11 @@ struct VhPlanDev {
   //                [3] reserved hash slot (key == sentinel) in use, [4] distinct (group, id) pairs,
   //                [5] extent allocation cursor (DENSE_PART, and the stream pool of the hashed partitioning)
   unsigned long long* counters;
+  // ---- set leaves (VH_F_INSET; vh_inset.h): VhProgOp::lit() of such a leaf indexes this array of up to VH_MAX_SETS descriptors. Descriptors and
+  // tables lie behind the literals in the uploaded plan block [segment snapshot | program | literals | sets]; form, bounds and size are run-time
+  // data (one code object per shape). A pointer, not the array itself: with hp_heavy_tuples_kernel's second argument the array would carry the
+  // kernel arguments past 4 KB; the address is uniform, so the descriptor's words still arrive by scalar loads.
+  const VhSetDev* set;
 };
 
 // VhMetricDev::slot of the virtual row-id column (VH_COL_ROWID): value = (segment << 32) | row

@@ -192,6 +192,7 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
           sst.push_back("(" + e + ")");
         } break;
         case VH_F_REL: sst.push_back(sliced_leaf(o, (int)o.op(), (int)o.lit())); break;
+        case VH_F_INSET: sst.push_back("vj_a_set_leaf_reads_rows_not_bit_planes"); break;      // (the planner never pairs the two: a compile error, not a wrong answer)
         default: {         // IN: OR of ==, NOT IN: AND of != (filter.cc:223-241)
           std::string e = o.op() ? "0u" : "~0u";
           for (int k = 0; k < (int)o.count(); ++k) e += std::string(o.op() ? " | " : " & ") + sliced_leaf(o, o.op() ? VH_OP_EQ : VH_OP_NE, (int)o.lit() + k);
@@ -215,6 +216,8 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
                      c.c_str(), neg.c_str(), s.pp_bits[p]);
   }
   std::vector<std::pair<std::string, std::string>> st;      // (mask expression, bool expression)
+  std::string set_decl;                                     // set leaves: one lookup per row slot and leaf, shared by the two expressions
+  int nz = 0;
   for (const VhProgOp& o : s.prog) {
     switch (o.kind()) {
       case VH_F_TRUE: st.push_back({"vj_b(true)", "true"}); break;
@@ -235,6 +238,14 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
         if (o.kind() == VH_F_REL) {
           const std::string cmp = "(" + c + " " + vj_relop((int)o.op()) + " " + lit_name((int)o.lit(), ty) + ")";
           st.push_back({"vj_b" + cmp, cmp});
+        } else if (o.kind() == VH_F_INSET) {       // membership in P.set[lit]: form, bounds and size are run-time data (vh_inset.h) — the text knows the element type only
+          const int k = (int)o.lit();
+          const std::string sn = vj_fmt("s%d", k);
+          if (!lit_decl.count(sn)) lit_decl[sn] = "VhSetDev " + sn + "|" + vj_fmt("%s(P.set[%d])", sn.c_str(), k);
+          set_decl += vj_fmt("    const bool z%d = vj_inset<%s>(L.%s, %s);\n", nz, vj_ctype(ty), sn.c_str(), c.c_str());
+          const std::string z = vj_fmt(o.op() ? "z%d" : "!z%d", nz);
+          ++nz;
+          st.push_back({"vj_b(" + z + ")", "(" + z + ")"});
         } else {           // IN: OR of ==, NOT IN: AND of != (filter.cc:223-241)
           std::string e = o.op() ? "0ull" : "vj_b(true)", f = o.op() ? "false" : "true";
           for (int k = 0; k < (int)o.count(); ++k) {
@@ -320,7 +331,7 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
     t += "  }\n";
   }
   if (!s.pp_sliced)
-  t += vj_fmt("  template <int I> static __device__ __forceinline__ uint64_t pass(const Lits& L, const uint32_t (&v)[%d], bool& p) {\n    (void)L; (void)v;\n    p = ", nva) + filter_bool +
+  t += vj_fmt("  template <int I> static __device__ __forceinline__ uint64_t pass(const Lits& L, const uint32_t (&v)[%d], bool& p) {\n    (void)L; (void)v;\n", nva) + set_decl + "    p = " + filter_bool +
        ";\n    return " + filter_mask + ";\n  }\n";
   if (s.qpay)     // the record of row slot I, as it came in with the step's loads: what a passing row leaves in the wave's queue
     t += vj_fmt("  template <int I> static __device__ __forceinline__ uint32_t payload(const uint32_t (&v)[%d]) { return v[%d + I]; }\n", nva, base[qpay_stream]);
@@ -776,6 +787,7 @@ static bool vj_canonical(int which, VhJitShape* s) {
   VhJitShape& S = *s;
   auto col = [](int slot, int type, int pitch, int rec, int off, int sext) { VhJitCol c; c.slot = slot; c.type = type; c.pitch = pitch; c.rec = rec; c.off = off; c.sext = sext; return c; };
   switch (which) {
+    case 23:    // ... case 12 with its d3 leaf as a SET (VH_F_INSET): membership looked up per row, the value a bit field of the byte planes
     case 22:    // ... case 21 reading the CLUSTERED planes beside the grouped records (slot 15, 20 dwords a word group: d3 and d4)
     case 19:    // ... case 0 whose tuples leave through the block's ring writer (16 partitions' waiting lines per block, extents by position)
     case 21:    // ... case 14 gathering from the GROUPED records: tiles sorted by d2 (predicate 0, 2 bits), the headers in slot 14
@@ -791,7 +803,8 @@ static bool vj_canonical(int which, VhJitShape* s) {
     case 1: {   // ... the same from the 4-byte arenas, straight into the dense HBM table (what an eighth of the table runs)
       const bool ring = which == 18 || which == 19;
       const bool four = which == 20;      // C3's one-word tuples in 4 bytes
-      const bool by_d2 = which == 21 || which == 22, clustered = which == 22;
+      const bool by_d2 = which == 21 || which == 22, clustered = which == 22, d3_set = which == 23;
+      if (which == 23) which = 12;
       if (which == 21 || which == 22) which = 14;
       if (which == 18 || which == 20) which = 9;
       if (which == 19) which = 0;
@@ -801,6 +814,7 @@ static bool vj_canonical(int which, VhJitShape* s) {
       S.pred[0] = VhJitPred{part ? 7 : 0, VH_U32, part ? 1 : 4}; S.pred[1] = VhJitPred{part ? 8 : 1, VH_U32, part ? 2 : 4}; S.pred[2] = VhJitPred{part ? 9 : 2, VH_U32, part ? 2 : 4};
       S.prog = {vj_leaf(VH_F_REL, VH_U32, VH_OP_EQ, 0, 0), vj_leaf(VH_F_REL, VH_U32, VH_OP_LT, 1, 1), vj_leaf(VH_F_REL, VH_U32, VH_OP_GE, 2, 2), vj_node(VH_F_AND, 3)};
       S.nlits = 3; S.ng = 2; S.nm = 2;
+      if (d3_set) { S.prog[1] = vj_leaf(VH_F_INSET, VH_U32, 1, 1, 0, 0); S.prog[2] = vj_leaf(VH_F_REL, VH_U32, VH_OP_GE, 2, 1); S.nlits = 2; }      // (members are not literals: set 0, two literals left)
       (void)ring;
       if (part) {
         S.g[0] = col(10, VH_U32, 32, 0, 8, 1); S.g[1] = col(11, VH_U32, 32, 0, 12, 1);
@@ -864,6 +878,15 @@ static bool vj_canonical(int which, VhJitShape* s) {
       S.m[0].rowid = 1; S.m[0].type = VH_U64; S.m[0].sop = SOP_MIN_U64;
       S.m[1] = col(4, VH_I8, 1, -1, 0, 1); S.m[1].sop = SOP_MIN_I32;
       S.m[2] = col(5, VH_F32, 4, -1, 0, 0); S.m[2].sop = SOP_ADDF32;
+      return true;
+    }
+    case 24: {  // a NOT-IN set on an i64 column streamed from its arena & u8 != x, GROUP BY a u32 through the hash table with its LDS front table, COUNT
+      S.mode = VH_MODE_HASH; S.block = 512; S.scope = __HIP_MEMORY_SCOPE_AGENT; S.carrier = -1; S.key_words = 1; S.lds_hash = 1;
+      S.npred = 2; S.pred[0] = VhJitPred{0, VH_I64, 8}; S.pred[1] = VhJitPred{1, VH_U8, 1};
+      S.prog = {vj_leaf(VH_F_INSET, VH_I64, 0, 0, 0, 0), vj_leaf(VH_F_REL, VH_U8, VH_OP_NE, 1, 0), vj_node(VH_F_AND, 2)};
+      S.nlits = 1; S.ng = 1; S.nm = 1;
+      S.g[0] = col(2, VH_U32, 4, -1, 0, 0); S.g[0].key_word = 0; S.g[0].key_shift = 0;
+      S.m[0] = col(3, VH_U32, 4, -1, 0, 0); S.m[0].sop = SOP_ADD32;
       return true;
     }
     case 11: {  // C2 itself in the no-compaction form: a range on one u32 column, GROUP BY a u32 code, SUM(long) + SUM(int) in an LDS table, 256-thread blocks

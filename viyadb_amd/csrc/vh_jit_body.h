@@ -41,6 +41,10 @@ template <typename T> __device__ __forceinline__ T vj_gload(const T* p) {
   return *p;
 }
 
+// A set leaf (VH_F_INSET) for one row slot: the value's membership in the plan's set, one lookup (vh_inset.h). The set's form is
+// wave-uniform run-time data — the branch on it is a scalar one — so one code object serves every list on the plan's shape.
+template <typename T> __device__ __forceinline__ bool vj_inset(const VhSetDev& s, T v) { return vh_inset_has<T>(s, v); }
+
 template <class J, int I>
 __device__ __forceinline__ uint64_t vj_time_rollup(uint64_t ts, const VhGroupDev& g) {
   constexpr bool micro = J::g_micro[I] != 0;

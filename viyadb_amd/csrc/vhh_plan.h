@@ -51,7 +51,7 @@ static bool typed_le(int elem, uint64_t a_bits, uint64_t b_bits) {
 }
 
 // SegmentSkipBuilder (src/codegen/query/filter.cc:263-335) for one segment.
-static bool segment_passes(const vh_table* t, const vh_plan* p, uint32_t seg) {
+static bool segment_passes(const vh_table* t, const vh_plan* p, uint32_t seg, const std::vector<VhSetHost>* sets = nullptr) {
   if (p->nfilter <= 0) return true;
   // (called once per segment and query — a thousand times for C3 —: the evaluation stack lives on the caller's stack, not on the heap: 17 of the 36 us
   // a C3 query spent planning were these allocations)
@@ -60,6 +60,7 @@ static bool segment_passes(const vh_table* t, const vh_plan* p, uint32_t seg) {
   char* st = small;
   if ((size_t)p->nfilter + 1 > sizeof(small)) { big.resize((size_t)p->nfilter + 1); st = big.data(); }
   int sp = 0;
+  size_t set_k = 0;          // set leaves come in program order
   for (int i = 0; i < p->nfilter; ++i) {
     const vh_filter_node& n = p->filter[i];
     switch (n.kind) {
@@ -81,6 +82,9 @@ static bool segment_passes(const vh_table* t, const vh_plan* p, uint32_t seg) {
               case VH_OP_GT: case VH_OP_GE: r = typed_le(c.elem, v, dmax); break;
               default: r = true; break;
             }
+          } else if (n.kind == VH_F_INSET && sets && set_k < sets->size()) {
+            // the verdict of the VH_F_IN loop below — some member lies in [dmin, dmax] — by binary search in the sorted members
+            r = (*sets)[set_k].any_in(order_key_of_bits(c.elem, dmin), order_key_of_bits(c.elem, dmax));
           } else {  // IN and NOT IN alike (the reference does not look at equal())
             r = false;
             for (int k = 0; k < n.count; ++k) {
@@ -90,6 +94,7 @@ static bool segment_passes(const vh_table* t, const vh_plan* p, uint32_t seg) {
             if (n.count == 0) r = false;
           }
         }
+        if (n.kind == VH_F_INSET) ++set_k;
         st[sp++] = r;
       } break;
     }
@@ -102,10 +107,13 @@ static bool segment_passes(const vh_table* t, const vh_plan* p, uint32_t seg) {
 // Decides between direct global atomics (cheap per query, ~30-60 G updates/s) and radix-partitioned
 // LDS aggregation (two passes over 16 B per survivor, but no global atomics).
 static int estimate_selectivity(vh_table* t, VhExec* x, const VhPlanDev& P, const std::vector<VhProgOp>& prog, const std::vector<uint64_t>& lits, uint32_t nseg,
-                                double* sel, uint64_t* passed_out = nullptr, uint64_t* sampled_out = nullptr, bool generic = false) {
+                                double* sel, uint64_t* passed_out = nullptr, uint64_t* sampled_out = nullptr, bool generic = false, const std::vector<VhSetHost>* sets = nullptr) {
   const uint32_t kRows = 16384;
   const size_t rows_bytes = ((size_t)std::max<uint32_t>(nseg, 1) * sizeof(uint32_t) + 7) / 8 * 8;
-  const size_t need = 256 + 256 + rows_bytes + prog.size() * sizeof(VhProgOp) + lits.size() * sizeof(uint64_t);
+  size_t set_bytes = sets ? sets->size() * sizeof(VhSetDev) : 0;
+  VhSetDev* set_desc = x->probe_sets;      // (read by an asynchronous copy: the context's, so it outlives an early return)
+  if (sets) for (const VhSetHost& sh : *sets) set_bytes += sh.words.size() * sizeof(uint32_t);
+  const size_t need = 256 + 256 + rows_bytes + prog.size() * sizeof(VhProgOp) + lits.size() * sizeof(uint64_t) + set_bytes;
   if (need > x->d_sample_bytes) {
     if (x->d_sample) HIP_TRY(hipFree(x->d_sample));
     HIP_TRY(hipMalloc(&x->d_sample, need * 2));
@@ -133,6 +141,18 @@ static int estimate_selectivity(vh_table* t, VhExec* x, const VhPlanDev& P, cons
   S.lits = reinterpret_cast<const uint64_t*>(x->d_sample + 512 + rows_bytes + prog.size() * sizeof(VhProgOp));
   HIP_TRY(hipMemcpyAsync(const_cast<VhProgOp*>(S.prog), prog.data(), prog.size() * sizeof(VhProgOp), hipMemcpyHostToDevice, st));
   if (!lits.empty()) HIP_TRY(hipMemcpyAsync(const_cast<uint64_t*>(S.lits), lits.data(), lits.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  if (sets && !sets->empty()) {       // the counting launch looks members up like any other: descriptors and tables go behind the literals (every piece a multiple of 8 bytes)
+    char* desc_at = x->d_sample + 512 + rows_bytes + prog.size() * sizeof(VhProgOp) + lits.size() * sizeof(uint64_t);
+    char* at = desc_at + sets->size() * sizeof(VhSetDev);
+    for (size_t k = 0; k < sets->size() && k < VH_MAX_SETS; ++k) {
+      const VhSetHost& sh = (*sets)[k];
+      HIP_TRY(hipMemcpyAsync(at, sh.words.data(), sh.words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+      set_desc[k] = sh.dev(at);
+      at += sh.words.size() * sizeof(uint32_t);
+    }
+    HIP_TRY(hipMemcpyAsync(desc_at, set_desc, std::min<size_t>(sets->size(), VH_MAX_SETS) * sizeof(VhSetDev), hipMemcpyHostToDevice, st));
+    S.set = reinterpret_cast<const VhSetDev*>(desc_at);
+  }
   const size_t qbytes = (size_t)16 * VhScanCfg<1024>::kQueueCap * sizeof(uint32_t);
   // (generic: predicate columns of other widths than 4 bytes — plans only the per-query compiled kernels run register-resident)
   if (generic) vh_launch_scan_generic(VH_MODE_DENSE_LDS, S, (int)std::min<uint32_t>(nseg, (uint32_t)g_ctx.num_cu), 16 + qbytes, false, st);
@@ -203,6 +223,7 @@ struct QueryBuild {
   int slot_bits[VH_MAX_SLOTS];                   // bit-field records (VhPack::bits): the record's bytes (4 / 8), slot_recoff = the field's bit offset, slot_stored = its bits; 0 otherwise
   uint64_t bytes_per_row = 0;
   bool fast_ok = false;
+  bool has_set = false, set_search = false;            // the filter has VH_F_INSET leaves (r->h_sets); at least one of them in the sorted-array form
   int pred_col[VH_MAX_PRED] = {-1, -1, -1, -1};        // table column behind predicate slot k of the register-resident kernels
   int pred_wide_slot[VH_MAX_PRED] = {-1, -1, -1, -1};  // its 4-byte arena's slot when the plan was pointed at a narrow copy
   VhJitShape jshape;
@@ -313,7 +334,11 @@ int QueryBuild::shape_filter() {
     return vh_fail(VH_E_INVALID, "plan has a negative count");
   if ((p->nfilter && !p->filter) || (p->nlits && !p->lits) || (p->ngroups && !p->groups) || (p->nmetrics && !p->metrics) || (p->nhaving && !p->having))
     return vh_fail(VH_E_INVALID, "plan has a count without its array");
-  if (p->nlits > VH_MAX_LITS) return vh_fail(VH_E_UNSUPPORTED, "filter has %d literals (max %d)", p->nlits, VH_MAX_LITS);
+  {   // VhProgOp::lit is 16 bits: the limit holds for the pool the program indexes — a set leaf's members are not in it
+    bool sets = false;
+    for (int i = 0; i < p->nfilter; ++i) sets |= p->filter[i].kind == VH_F_INSET;
+    if (!sets && p->nlits > VH_MAX_LITS) return vh_fail(VH_E_UNSUPPORTED, "filter has %d literals (max %d)", p->nlits, VH_MAX_LITS);
+  }
   if (p->ngroups > VH_MAX_GROUP) return vh_fail(VH_E_UNSUPPORTED, "%d group columns (max %d)", p->ngroups, VH_MAX_GROUP);
   if (p->nmetrics > VH_MAX_METRIC - 1) return vh_fail(VH_E_UNSUPPORTED, "%d metrics in one pass (max %d; vh_query_agg splits wider queries into passes)", p->nmetrics, VH_MAX_METRIC - 1);
   nseg = p->seg_rows ? p->nseg : t->nseg;
@@ -329,14 +354,52 @@ int QueryBuild::shape_filter() {
 
   // ---------------- filter program (+ stack depth check)
   fast_ok = !(p->flags & VH_PLAN_NO_FAST);
+  // Set leaves (VH_F_INSET) keep their members out of the literal pool: only REL / IN literals travel in h_lits / ilits and count against
+  // VH_INLINE_LITS — else a plan with one long list would still be refused the compiled scan. A plan WITH a set leaf therefore gets its
+  // REL / IN literals re-indexed (lit_at[i]: where node i's literals begin in the compacted pool); a plan without one keeps the caller's pool
+  // and indices exactly as before.
+  std::vector<int> lit_at;
+  for (int i = 0; i < p->nfilter; ++i) has_set |= p->filter[i].kind == VH_F_INSET;
+  if (has_set) {
+    fast_ok = false;                                    // (the pre-built register-resident kernels do not look members up)
+    lit_at.assign((size_t)p->nfilter, 0);
+    for (int i = 0; i < p->nfilter; ++i) {
+      const vh_filter_node& n = p->filter[i];
+      if (n.kind != VH_F_REL && n.kind != VH_F_IN) continue;
+      const int cnt = n.kind == VH_F_REL ? 1 : n.count;
+      if (n.lit < 0 || cnt < 0 || n.lit + cnt > p->nlits) continue;       // (refused below)
+      lit_at[(size_t)i] = (int)r->h_lits.size();
+      for (int k = 0; k < cnt; ++k) r->h_lits.push_back(p->lits[n.lit + k].u64);
+    }
+    if (r->h_lits.size() > VH_MAX_LITS) return vh_fail(VH_E_UNSUPPORTED, "filter has %d REL / IN literals (max %d)", (int)r->h_lits.size(), VH_MAX_LITS);
+  }
   int depth = 0, maxdepth = 0;
   std::vector<size_t> seg_start;          // where the piece of program behind each value on the (simulated) stack begins
   for (int i = 0; i < p->nfilter; ++i) {
     const vh_filter_node& n = p->filter[i];
     VhProgOp o{};
-    if (n.kind == VH_F_REL || n.kind == VH_F_IN || n.kind == VH_F_TRUE) seg_start.push_back(prog.size());
+    if (n.kind == VH_F_REL || n.kind == VH_F_IN || n.kind == VH_F_INSET || n.kind == VH_F_TRUE) seg_start.push_back(prog.size());
     o.set_kind((uint8_t)n.kind); o.set_op((uint8_t)n.op); o.set_count((uint8_t)std::min(n.count, 255));
-    if (n.kind == VH_F_REL || n.kind == VH_F_IN) {
+    if (n.kind == VH_F_INSET) {
+      // validate, build the set (once per query), and leave a leaf that names it: no member count in the program — the plan shape the
+      // compile cache is keyed by holds only "a set leaf on element type T"
+      if (n.col < 0 || n.col >= ncols || n.col >= 256) { return vh_fail(VH_E_INVALID, "filter node %d: bad column %d", i, n.col); }
+      const int elem = t->cols[n.col].elem;
+      if (elem < VH_U8 || elem > VH_I64) { return vh_fail(VH_E_UNSUPPORTED, "filter node %d: a set leaf needs a column of an integer element type (column %d: use VH_F_IN)", i, n.col); }
+      if (n.count < 1) { return vh_fail(VH_E_INVALID, "filter node %d: a set of %d values", i, n.count); }
+      if (n.lit < 0 || n.lit + n.count > p->nlits) { return vh_fail(VH_E_INVALID, "filter node %d: literal range", i); }
+      if (r->h_sets.size() >= VH_MAX_SETS) { return vh_fail(VH_E_UNSUPPORTED, "more than %d set leaves in one filter", VH_MAX_SETS); }
+      const int s = slot(n.col);
+      if (s < 0) { return vh_fail(VH_E_INVALID, "filter node %d: bad column %d", i, n.col); }
+      std::vector<uint64_t> members((size_t)n.count);
+      for (int k = 0; k < n.count; ++k) members[(size_t)k] = p->lits[n.lit + k].u64;
+      const int k = (int)r->h_sets.size();
+      r->h_sets.emplace_back();
+      vh_inset_build(elem, members.data(), members.size(), (p->flags & VH_PLAN_SET_SEARCH) != 0, &r->h_sets.back());
+      set_search |= r->h_sets.back().form != VH_SET_BITMAP;
+      o.set_op(n.op ? 1 : 0); o.set_count(0); o.set_slot((uint8_t)s); o.set_type((uint8_t)elem); o.set_lit((uint16_t)k);
+      ++depth;
+    } else if (n.kind == VH_F_REL || n.kind == VH_F_IN) {
       int s = slot(n.col);
       if (s == -2) {     // a bitset metric: the predicate compares the row's cardinality (offsets of the CSR mirror)
         s = -1;
@@ -352,7 +415,8 @@ int QueryBuild::shape_filter() {
       if (s < 0) { return vh_fail(VH_E_INVALID, "filter node %d: bad column %d", i, n.col); }
       const int cnt = n.kind == VH_F_REL ? 1 : n.count;
       if (n.lit < 0 || n.count < 0 || n.lit + cnt > p->nlits) { return vh_fail(VH_E_INVALID, "filter node %d: literal range", i); }
-      o.set_slot((uint8_t)s); o.set_type((uint8_t)t->cols[n.col].elem); o.set_lit((uint16_t)n.lit);
+      const int lit0 = has_set ? lit_at[(size_t)i] : n.lit;
+      o.set_slot((uint8_t)s); o.set_type((uint8_t)t->cols[n.col].elem); o.set_lit((uint16_t)lit0);
       // fast path bookkeeping: distinct 4-byte predicate columns
       if (is_bitset_elem(t->cols[n.col].elem) || vh_elem_size(t->cols[n.col].elem) != 4) fast_ok = false;
       if (fast_ok) {
@@ -366,7 +430,7 @@ int QueryBuild::shape_filter() {
         // pairwise — OR of the chunks for IN, AND for NOT IN — so the mask stack grows by one entry only
         for (int first = 0; first < n.count; first += 255) {
           VhProgOp c = o;
-          c.set_count((uint8_t)std::min(255, n.count - first)); c.set_lit((uint16_t)(n.lit + first));
+          c.set_count((uint8_t)std::min(255, n.count - first)); c.set_lit((uint16_t)(lit0 + first));
           prog.push_back(c);
           if (first) { VhProgOp f{}; f.set_kind(n.op ? VH_F_OR : VH_F_AND); f.set_count(2); prog.push_back(f); }
         }
@@ -418,8 +482,10 @@ int QueryBuild::shape_filter() {
     if (P.nprog == 1 && last != VH_F_AND && last != VH_F_OR) P.prog_flat = 1;
     else if (leaves && P.nprog > 1 && (last == VH_F_AND || last == VH_F_OR) && (int)prog[P.nprog - 1].count() == P.nprog - 1) P.prog_flat = last == VH_F_AND ? 1 : 2;
   }
-  r->h_lits.resize(std::max(p->nlits, 0));
-  for (int i = 0; i < p->nlits; ++i) r->h_lits[i] = p->lits[i].u64;
+  if (!has_set) {
+    r->h_lits.resize(std::max(p->nlits, 0));
+    for (int i = 0; i < p->nlits; ++i) r->h_lits[i] = p->lits[i].u64;
+  }
   if (prog.size() <= VH_INLINE_PROG && r->h_lits.size() <= VH_INLINE_LITS) {   // the register-resident kernels read the program from the kernel arguments
     memcpy(P.iprog, prog.data(), prog.size() * sizeof(VhProgOp));
     memcpy(P.ilits, r->h_lits.data(), r->h_lits.size() * sizeof(uint64_t));
@@ -433,7 +499,7 @@ int QueryBuild::shape_filter() {
     jshape.prog = prog;
     int nv = 0;
     for (VhProgOp& o : jshape.prog) {
-      if (o.kind() != VH_F_REL && o.kind() != VH_F_IN) continue;
+      if (o.kind() != VH_F_REL && o.kind() != VH_F_IN && o.kind() != VH_F_INSET) continue;
       const int es = vh_elem_size((int)o.type());
       if (!es) { jit_try = false; break; }                       // a bitset metric's cardinality: the generic kernel
       int ps = -1;
@@ -463,7 +529,7 @@ int QueryBuild::shape_filter() {
     pp_cols.erase(std::unique(pp_cols.begin(), pp_cols.end()), pp_cols.end());
     if (!all_cols) pp_cols.clear();
     VhPredPack* pb = all_cols ? predpack_usable(t, pp_cols, 0) : nullptr;
-    VhPredPack* ps = all_cols ? predpack_usable(t, pp_cols, 1) : nullptr;
+    VhPredPack* ps = all_cols && !has_set ? predpack_usable(t, pp_cols, 1) : nullptr;      // (bit-serial comparisons cannot look a member up: a set leaf wants the row's value)
     if (pb && P.nslots + pb->nplanes <= VH_MAX_SLOTS) {
       jshape.pp_nplanes = pb->nplanes;
       for (int q = 0; q < pb->nplanes; ++q) {
@@ -538,20 +604,24 @@ int QueryBuild::shape_filter() {
 int QueryBuild::snapshot_segments() {
   int rc = VH_OK; (void)rc;
   // ---------------- segments: snapshot + skip
-  // one pinned staging block [segment snapshot | program | literals] -> one upload per query
+  // one pinned staging block [segment snapshot | program | literals | sets] -> one upload per query
   const size_t seg_words = ((size_t)std::max<uint32_t>(nseg, 1) + 1) / 2 * 2;
-  const size_t plan_words = seg_words + 2 * (prog.size() + r->h_lits.size());
+  size_t plan_words = seg_words + 2 * (prog.size() + r->h_lits.size());
+  r->set_desc_word = plan_words;
+  plan_words += r->h_sets.size() * (sizeof(VhSetDev) / sizeof(uint32_t));                                                  // the descriptors (vh_result::place_sets fills them in), then the tables
+  for (size_t k = 0; k < r->h_sets.size(); ++k) { r->set_word[k] = plan_words; plan_words += r->h_sets[k].words.size(); }      // (every table an even number of words: 8-byte aligned)
   rc = ensure_segrows(x, plan_words);
   if (rc) { return rc; }
   memcpy(x->h_segrows + seg_words, prog.data(), prog.size() * sizeof(VhProgOp));
   memcpy(x->h_segrows + seg_words + 2 * prog.size(), r->h_lits.data(), r->h_lits.size() * sizeof(uint64_t));
+  for (size_t k = 0; k < r->h_sets.size(); ++k) memcpy(x->h_segrows + r->set_word[k], r->h_sets[k].words.data(), r->h_sets[k].words.size() * sizeof(uint32_t));
   r->plan_words = plan_words; r->seg_words = seg_words;
   uint64_t scanned_recs = 0, scanned_segments = 0;
   for (uint32_t s = 0; s < nseg; ++s) {
     uint64_t rows = p->seg_rows ? p->seg_rows[s] : t->seg_rows[s];
     if (rows > t->seg_rows[s]) { return vh_fail(VH_E_INVALID, "segment %u: snapshot %llu rows > mirrored %llu", s, (unsigned long long)rows, (unsigned long long)t->seg_rows[s]); }
     scanned_recs += rows;
-    const bool keep = segment_passes(t, p, s);
+    const bool keep = segment_passes(t, p, s, &r->h_sets);
     if (keep) { ++scanned_segments; rows_to_scan += rows; if (rows) live.push_back(s); }
     x->h_segrows[s] = keep ? (uint32_t)rows : 0u;
   }
@@ -576,10 +646,14 @@ int QueryBuild::probed_selectivity(double* sel) {
   if (p->nfilter == 0) { *sel = 1.0; probe_passed = probe_sampled = rows_to_scan; return VH_OK; }   // no filter: every row passes
   std::string key((const char*)prog.data(), sizeof(VhProgOp) * prog.size());
   key.append((const char*)r->h_lits.data(), sizeof(uint64_t) * r->h_lits.size());
+  for (const VhSetHost& sh : r->h_sets) {      // (a set leaf's members are not in the literal pool)
+    key += "|s" + std::to_string(sh.form) + ":";
+    key.append((const char*)sh.keys.data(), sizeof(uint64_t) * sh.keys.size());
+  }
   key += "|" + std::to_string(nseg) + "|" + std::to_string(rows_to_scan) + "|" + std::to_string(t->sync_epoch);
   auto hit = t->sel_cache.find(key);
   if (hit != t->sel_cache.end()) { probe_passed = hit->second.first; probe_sampled = hit->second.second; *sel = probe_sampled ? (double)probe_passed / (double)probe_sampled : 0.0; return VH_OK; }
-  const int prc = estimate_selectivity(t, x, P, r->h_prog, r->h_lits, nseg, sel, &probe_passed, &probe_sampled, !fast_ok);
+  const int prc = estimate_selectivity(t, x, P, r->h_prog, r->h_lits, nseg, sel, &probe_passed, &probe_sampled, !fast_ok, &r->h_sets);
   if (prc) return prc;
   if (t->sel_cache.size() > 256) t->sel_cache.clear();
   t->sel_cache[key] = std::make_pair(probe_passed, probe_sampled);

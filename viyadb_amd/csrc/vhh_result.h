@@ -84,10 +84,21 @@ struct vh_result {
   // the ONE way work gets onto a finished result's stream (exchange, partitioning, device buffers ...): whoever enqueues behind the query
   // takes the stream from here, which is also what makes the destructor wait for it before the context goes to the next query
   hipStream_t stream_for_work() { stream_quiet = false; return exec->stream(); }
-  size_t plan_words = 0, seg_words = 0;        // layout of the pinned staging block [segment snapshot | program | literals] in u32 words
+  size_t plan_words = 0, seg_words = 0;        // layout of the pinned staging block [segment snapshot | program | literals | sets] in u32 words
   int h_slot = -1;                             // staging buffer of `exec` this query finalises into
   std::string kernel;                          // symbol(s) of the scan kernel(s) launched for this query
   std::vector<VhProgOp> h_prog; std::vector<uint64_t> h_lits;   // the filter program as uploaded (VhPlanDev::prog / lits point into device scratch)
+  std::vector<VhSetHost> h_sets;               // the sets of the filter's VH_F_INSET leaves (VhPlanDev::set order), built once per query ...
+  size_t set_word[VH_MAX_SETS] = {};           // ... and where each one's table begins in the staging block, in u32 words ...
+  size_t set_desc_word = 0;                    // ... behind their VhSetDev descriptors, which begin here
+  // the descriptors get their tables' device addresses once the plan block has its place in device scratch (`block`), in the pinned staging
+  // block the upload reads; -> what VhPlanDev::set points at
+  const VhSetDev* place_sets(uint32_t* staging, char* block) const {
+    if (h_sets.empty()) return nullptr;
+    VhSetDev* d = reinterpret_cast<VhSetDev*>(staging + set_desc_word);
+    for (size_t k = 0; k < h_sets.size(); ++k) d[k] = h_sets[k].dev(block + set_word[k] * 4);
+    return reinterpret_cast<const VhSetDev*>(block + set_desc_word * 4);
+  }
   std::vector<int> filter_bitset_cols;         // bitset metrics the filter compares the cardinality of (VhPlanDev::fbs_offs order)
   bool device_rows = false;                    // emitted rows must (also) exist in device memory: they are exchanged or gathered next
   VhExec* exec = nullptr;                      // owned from launch to vh_result_free: stream, scratch (device-side state), staging (host view)

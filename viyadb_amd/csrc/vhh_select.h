@@ -72,6 +72,7 @@ static int select_count_locked(vh_table* t, VhExec* x, const vh_select_plan* sp,
   char* S = s->S = x->scratch;
   HIP_TRY(hipEventRecord(x->ev[0], st));
   HIP_TRY(hipMemsetAsync(S + o_ctr, 0, 256, st));
+  P.set = pr->place_sets(x->h_segrows, S + o_segrows);      // (into the pinned staging block, BEFORE the asynchronous upload reads it)
   HIP_TRY(hipMemcpyAsync(S + o_segrows, x->h_segrows, pr->plan_words * 4, hipMemcpyHostToDevice, st));
   P.prog = reinterpret_cast<const VhProgOp*>(S + o_segrows + pr->seg_words * 4);
   P.lits = reinterpret_cast<const uint64_t*>(S + o_segrows + pr->seg_words * 4 + pr->h_prog.size() * sizeof(VhProgOp));

@@ -27,6 +27,7 @@ struct VhExec {
   uint32_t* h_segrows = nullptr; size_t h_segrows_cap = 0;
   unsigned long long* h_counters = nullptr;     // pinned: 16 words of counters + 64 words for a big result's header
   char* d_sample = nullptr; size_t d_sample_bytes = 0;   // selectivity probe: counters + presence + seg rows
+  VhSetDev probe_sets[VH_MAX_SETS] = {};                 // ... and the set descriptors its upload reads (the source of an asynchronous copy outlives any early return)
   char* h_out[2] = {nullptr, nullptr}; size_t h_out_bytes[2] = {0, 0}; int h_out_next = 0;  // pinned result staging (two alternate: a
                                                                                             // zero-copy view outlives vh_result_free until the second-next query)
   hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};

@@ -51,7 +51,8 @@ class GroupSpec:
 @dataclass
 class AggPlan:
     """Postfix filter + group columns + metric columns (see include/viya_hip.h)."""
-    filter: Sequence = ()          # ("rel", col, op, value) | ("in", col, equal, [values]) | ("and"|"or", n) | ("true",)
+    filter: Sequence = ()          # ("rel", col, op, value) | ("in", col, equal, [values]) | ("inset", col, equal, [values]) | ("and"|"or", n) | ("true",)
+                                   # ("inset": the same result as "in", one set lookup per row; integer-typed columns, scan filter only)
     groups: Sequence[GroupSpec] = ()
     metrics: Sequence[int] = ()
     seg_rows: Optional[Sequence[int]] = None
@@ -94,6 +95,8 @@ class AggResult:
     pack_rec_bytes: int = 0        # bytes of one projection record (0: no projection was read)
     grouped_payload: bool = False  # the records were gathered from the projection's grouped form (tiles sorted by an equality column)
     grouped_planes: bool = False   # ... and the predicate bits read from the planes clustered in the same order (the literal's run of every tile only)
+    inset: bool = False            # the filter's "inset" leaves were evaluated by set lookup
+    inset_search: bool = False     # ... at least one of them by binary search in a sorted array (the others: one bit of a bitmap)
 
 
 
@@ -241,7 +244,7 @@ class DeviceTable:
 
     def filter_columns(self, plan: "AggPlan"):
         """Table columns the plan's filter reads."""
-        return sorted({f[1] for f in plan.filter if f[0] in ("rel", "in")})
+        return sorted({f[1] for f in plan.filter if f[0] in ("rel", "in", "inset")})
 
     def gather_columns(self, plan: AggPlan) -> List[int]:
         """Columns a survivor's values are gathered from: group columns + value metrics (not bitsets, not the row id)."""
@@ -284,9 +287,9 @@ class DeviceTable:
                 _, col, op, val = f
                 hnodes.append(capi.FilterNode(capi.F_REL, col, op, 1, len(lits), 0))
                 lits.append(val if isinstance(val, capi.AnyNum) else anynum(result_elem[col], val))
-            elif k == "in":
+            elif k in ("in", "inset"):      # (the library refuses a set leaf in HAVING: passed on as given)
                 _, col, equal, vals = f
-                hnodes.append(capi.FilterNode(capi.F_IN, col, 1 if equal else 0, len(vals), len(lits), 0))
+                hnodes.append(capi.FilterNode(capi.F_IN if k == "in" else capi.F_INSET, col, 1 if equal else 0, len(vals), len(lits), 0))
                 for v in vals:
                     lits.append(v if isinstance(v, capi.AnyNum) else anynum(result_elem[col], v))
             else:
@@ -299,9 +302,9 @@ class DeviceTable:
                 _, col, op, val = f
                 nodes.append(capi.FilterNode(capi.F_REL, col, op, 1, len(lits), 0))
                 lits.append(val if isinstance(val, capi.AnyNum) else anynum(self.cols[col][1], val))
-            elif k == "in":
+            elif k in ("in", "inset"):
                 _, col, equal, vals = f
-                nodes.append(capi.FilterNode(capi.F_IN, col, 1 if equal else 0, len(vals), len(lits), 0))
+                nodes.append(capi.FilterNode(capi.F_IN if k == "in" else capi.F_INSET, col, 1 if equal else 0, len(vals), len(lits), 0))
                 for v in vals:
                     lits.append(v if isinstance(v, capi.AnyNum) else anynum(self.cols[col][1], v))
             elif k in ("and", "or"):
@@ -391,7 +394,8 @@ class DeviceTable:
                          bool(info.reserved & 2048), bool(info.reserved & 8192), bool(info.reserved & 4096), int(info.reserved),
                          bool(info.reserved & 16384), bool(info.reserved & 32768),
                          (2 << ((info.reserved >> 16) & 7)) if info.reserved & 8 else 0,
-                         bool(info.reserved & capi.INFO_GROUPED_PAYLOAD), bool(info.reserved & capi.INFO_GROUPED_PLANES))
+                         bool(info.reserved & capi.INFO_GROUPED_PAYLOAD), bool(info.reserved & capi.INFO_GROUPED_PLANES),
+                         bool(info.reserved & capi.INFO_INSET), bool(info.reserved & capi.INFO_INSET_SEARCH))
 
     def query_agg(self, plan: AggPlan, copy: bool = True) -> AggResult:
         p, keep = self._build_plan(plan)

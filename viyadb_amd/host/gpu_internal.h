@@ -89,7 +89,41 @@ private:
 // scan filter: a column is its storage index in the table (a bitset metric compares its per-row cardinality on the device: filter.cc:216,235)
 struct PlanFilterBuilder {
   PlanFilterBuilder(const db::Table& t, const std::vector<db::AnyNum>& args) : table(t), prog(args, lits), nodes(prog.nodes) {}
-  void Add(const Filter& f) { prog.Add(f, [this](const std::string& name) { return (int32_t)table.column(name)->storage_index; }); }
+  void Add(const Filter& f) {
+    prog.Add(f, [this](const std::string& name) {
+      const db::Column* c = table.column(name);
+      const bool integer = !c->num_type().fp() && !(c->type() == db::Column::METRIC && c->agg_type() == db::Column::BITSET);
+      if (integer) integer_cols_.push_back((int32_t)c->storage_index);
+      return (int32_t)c->storage_index;
+    });
+    LongListsToSets();
+  }
+  // A filter that carries more than VH_PLAN_INLINE_LITS literals in all would be answered by the interpreting scan, one comparison per
+  // value and row. Its MEMBER leaves on integer-typed columns become set leaves (VH_F_INSET: one lookup per row, the values outside the
+  // literal budget), the longest list first, until the rest fits — and only when up to VH_MAX_SETS sets CAN make the rest fit: a filter
+  // that would stay over the limit anyway (a long list on a floating-point column, say) is left exactly as it is, like every filter at or
+  // under the limit. Floating-point columns and bitset metrics keep VH_F_IN.
+  void LongListsToSets() {
+    if (lits.size() <= (size_t)VH_PLAN_INLINE_LITS) return;
+    std::vector<vh_filter_node*> picked;
+    size_t left = lits.size();
+    while ((int)picked.size() < VH_MAX_SETS && left > (size_t)VH_PLAN_INLINE_LITS) {
+      vh_filter_node* longest = nullptr;
+      for (vh_filter_node& n : nodes) {
+        if (n.kind != VH_F_IN || (longest && n.count <= longest->count)) continue;
+        bool integer = false, taken = false;
+        for (int32_t c : integer_cols_) integer |= c == n.col;
+        for (vh_filter_node* q : picked) taken |= q == &n;
+        if (integer && !taken) longest = &n;
+      }
+      if (!longest) break;
+      picked.push_back(longest);
+      left -= (size_t)longest->count;
+    }
+    if (left > (size_t)VH_PLAN_INLINE_LITS) return;       // (nothing to gain: the interpreting kernel would answer all the same)
+    for (vh_filter_node* n : picked) n->kind = VH_F_INSET;
+  }
+  std::vector<int32_t> integer_cols_;
   const db::Table& table;
   std::vector<vh_anynum> lits;
   PlanProgram prog;

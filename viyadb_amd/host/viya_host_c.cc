@@ -106,6 +106,7 @@ int vdb_query(vdb* db, const char* query_json, int64_t now, char** rows_out, siz
       stats->compile_time = st.compile_time; stats->whole_time = st.whole_time;
       stats->scan_kernel_ms = st.scan_kernel_ms; stats->device_total_ms = st.device_total_ms; stats->path = st.path;
   stats->build_pending = st.build_pending ? 1 : 0; stats->compile_ms = st.compile_ms;
+  stats->device_flags = st.device_flags; stats->retries = st.retries;
     }
   });
 }
@@ -118,6 +119,7 @@ static void fill_stats(vdb_stats* stats, const viya::query::QueryStats& st) {
   stats->compile_time = st.compile_time; stats->whole_time = st.whole_time;
   stats->scan_kernel_ms = st.scan_kernel_ms; stats->device_total_ms = st.device_total_ms; stats->path = st.path;
   stats->build_pending = st.build_pending ? 1 : 0; stats->compile_ms = st.compile_ms;
+  stats->device_flags = st.device_flags; stats->retries = st.retries;
 }
 
 int vdb_query_partial(vdb* db, const char* query_json, int64_t now, char** blob_out, size_t* blob_len, vdb_stats* stats) {

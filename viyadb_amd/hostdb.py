@@ -15,7 +15,8 @@ class Stats(C.Structure):
     _fields_ = [("scanned_segments", C.c_uint64), ("scanned_recs", C.c_uint64), ("aggregated_recs", C.c_uint64),
                 ("output_recs", C.c_uint64), ("passed_recs", C.c_uint64), ("compile_time", C.c_double),
                 ("whole_time", C.c_double), ("scan_kernel_ms", C.c_double), ("device_total_ms", C.c_double),
-                ("path", C.c_int32), ("build_pending", C.c_int32), ("compile_ms", C.c_double)]
+                ("path", C.c_int32), ("build_pending", C.c_int32), ("compile_ms", C.c_double),
+                ("device_flags", C.c_uint32), ("retries", C.c_uint32)]
 
 
 class HostError(RuntimeError):
