@@ -138,6 +138,7 @@ class CommOps(C.Structure):
 COMM_ID_BYTES = 128
 
 BUILD_INLINE, BUILD_BACKGROUND = 0, 1
+INFO_PACKED = 1 << 3             # vh_result_info.reserved bit 3: group / metric values came from a payload projection
 INFO_BUILD_PENDING = 1 << 19      # vh_result_info.reserved bit 19
 INFO_GROUPED_PAYLOAD = 1 << 20    # vh_result_info.reserved bit 20
 INFO_GROUPED_PLANES = 1 << 21     # vh_result_info.reserved bit 21
