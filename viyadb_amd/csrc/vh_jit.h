@@ -72,8 +72,19 @@ struct VhJitShape {
   int ng = 0, nm = 0;
   VhJitCol g[VJ_MAX_COLS], m[VJ_MAX_COLS];
   int ablate = 0;                       // measurement builds only (VH_JIT_ABLATE): 1 = no gathers, 2 = no sink
+  // Pipelined drain (vj_drain_pipe, vh_jit_body.h): groups of 64 survivors whose records are in flight while the group before them is
+  // sunk. Only plans whose survivor payload is ONE packed record of 4 or 8 bytes (vh_jit_rec_bytes) have one; 0 = one drain after another.
+  int drain_depth = 0;
   std::string key() const;
 };
+// Bytes of the one packed record a survivor of this shape gathers (4 or 8), 0 for every other payload: arenas, wider records or more than one,
+// streamed records, row ids, the hashed partitioning (its drain takes two survivors per lane: vj_drain2), the no-compaction form.
+int vh_jit_rec_bytes(const VhJitShape& s);
+#define VH_DRAIN_DEPTH_MAX 2
+#define VH_DRAIN_DEPTH_DEFAULT 1       // (measured: profiles/r09/NOTES.md)
+// The depth a shape is compiled with: the default, or VH_TEST_DRAIN_DEPTH (a test hook, read when the shape is built: switched between
+// two queries of one process); 0 for shapes without a packed record, whatever is asked for (viya_hip.hip).
+int vh_jit_drain_depth(const VhJitShape& s);
 
 struct VhJitKernel {
   hipModule_t mod = nullptr;

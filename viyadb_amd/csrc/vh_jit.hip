@@ -70,7 +70,29 @@ std::string VhJitShape::key() const {
   };
   for (int i = 0; i < ng; ++i) col(g[i]);
   for (int j = 0; j < nm; ++j) col(m[j]);
+  if (drain_depth) { k += "dd"; put(drain_depth); }      // (depth 0 keeps the names its kernels always had)
   return k;
+}
+
+// The one packed record of a survivor (see vh_jit.h): every group and metric column a member of the same projection, which is a 4- or 8-byte
+// bit-field word or a compressed record of 4 or 8 bytes — what gather() below fetches with ONE load.
+int vh_jit_rec_bytes(const VhJitShape& s) {
+  if (s.qpay || s.lanes || s.hpart || s.ablate || s.ng + s.nm == 0) return 0;
+  const VhJitCol* b0 = nullptr;
+  int dwords = 0;                    // (a compressed record: the dwords its members touch — gather() fetches exactly those)
+  for (int i = 0; i < s.ng + s.nm; ++i) {
+    const VhJitCol& c = i < s.ng ? s.g[i] : s.m[i - s.ng];
+    if (c.rowid || c.bitset || c.rec < 0) return 0;
+    if (!b0) b0 = &c;
+    if (c.rec != b0->rec || c.pitch != b0->pitch || c.bits != b0->bits) return 0;
+    if (!c.bits) {
+      const int es = c.stored ? c.stored : vh_elem_size(c.type);
+      if (c.off < 0 || c.off + es > c.pitch || c.pitch > 8) return 0;
+      for (int by = c.off; by < c.off + es; by += 4) dwords |= 1 << (by / 4);
+    }
+  }
+  if (b0->bits) return b0->bits == 4 || b0->bits == 8 ? b0->bits : 0;
+  return b0->pitch == 4 && dwords == 1 ? 4 : b0->pitch == 8 && dwords == 3 ? 8 : 0;      // (the whole record in ONE aligned load, as gather() has it)
 }
 
 // ------------------------------------------------------------------ source text
@@ -440,6 +462,27 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
   for (int i = 0; i < s.ng; ++i) t += vj_fmt("    gv[%d] = %s;\n", i, value(&s.g[i]).c_str());
   for (int j = 0; j < s.nm; ++j) t += vj_fmt("    mv[%d] = %s;\n", j, value(&s.m[j]).c_str());
   t += "  }\n";
+  {
+    // ---- the same survivor in two steps, for the pipelined drain (vj_drain_pipe): rec_load issues the record's ONE load and hands back its
+    //      raw bits — nothing looks at them, so nothing waits — and rec_unpack turns them into gather()'s values one sink later
+    const int rb = vh_jit_rec_bytes(s);
+    const int depth = rb ? s.drain_depth : 0;
+    t += vj_fmt("  static constexpr int REC_BYTES = %d, DRAIN_DEPTH = %d;\n  typedef %s rec_t;\n", rb, depth, rb == 8 ? "vj_u32x2" : "uint32_t");
+    if (rb) {
+      const VhJitCol* b0 = cols[0];
+      const int back = b0->bits ? 0 : b0->off;      // (a compressed record's members lie at byte offsets of the slot's base; a bit-field record's all at its start)
+      t += vj_fmt("  static __device__ __forceinline__ rec_t rec_load(const VhPlanDev& P, uint32_t seg, uint32_t row) {\n"
+                  "    return vj_gload(reinterpret_cast<const rec_t*>(P.colbase[%d] - %d + (uint64_t)seg * P.colstride[%d] + (uint64_t)row * %uu));\n  }\n",
+                  b0->slot, back, b0->slot, (unsigned)b0->pitch);
+      t += vj_fmt("  static __device__ __forceinline__ void rec_unpack(rec_t raw, uint64_t (&gv)[%d], uint64_t (&mv)[%d]) {\n    const uint32_t seg = 0, row = 0; (void)seg; (void)row;\n",
+                  s.ng ? s.ng : 1, s.nm ? s.nm : 1);
+      if (b0->bits) t += rb == 4 ? vj_fmt("    const uint64_t w%d = (uint64_t)raw;\n", b0->rec) : vj_fmt("    const uint64_t w%d = ((uint64_t)raw.y << 32) | raw.x;\n", b0->rec);
+      else t += "    const rec_t u0 = raw;\n";          // (gather()'s name for the record's one load)
+      for (int i = 0; i < s.ng; ++i) t += vj_fmt("    gv[%d] = %s;\n", i, value(&s.g[i]).c_str());
+      for (int j = 0; j < s.nm; ++j) t += vj_fmt("    mv[%d] = %s;\n", j, value(&s.m[j]).c_str());
+      t += "  }\n";
+    }
+  }
   if (s.qpay) {   // ... and the same values out of a QUEUED record (every column is a bit field of record 0's word)
     t += vj_fmt("  static __device__ __forceinline__ void unpack(uint32_t rec, uint64_t (&gv)[%d], uint64_t (&mv)[%d]) {\n    const uint64_t w0 = rec; const uint32_t seg = 0, row = 0; (void)seg; (void)row; (void)w0;\n",
                 s.ng ? s.ng : 1, s.nm ? s.nm : 1);
@@ -786,6 +829,15 @@ static VhProgOp vj_node(int kind, int count) { VhProgOp o{}; o.set_kind((uint8_t
 static bool vj_canonical(int which, VhJitShape* s) {
   VhJitShape& S = *s;
   auto col = [](int slot, int type, int pitch, int rec, int off, int sext) { VhJitCol c; c.slot = slot; c.type = type; c.pitch = pitch; c.rec = rec; c.off = off; c.sext = sext; return c; };
+  // the pipelined drain (VhJitShape::drain_depth): 25 / 26 = case 22 at depth 1 / 2; 27, 28, 29 = cases 21 (row-order planes over the grouped
+  // records), 7 (the compressed 8-byte record) and 1 (arenas: no packed record, so depth 0 whatever is asked for) at the depth a query gets
+  int depth = -1;
+  switch (which) { case 25: which = 22; depth = 1; break; case 26: which = 22; depth = 2; break; case 27: which = 21; depth = -2; break; case 28: which = 7; depth = -2; break; case 29: which = 1; depth = -2; break; default: break; }
+  if (depth != -1) {
+    if (!vj_canonical(which, s)) return false;
+    S.drain_depth = depth == -2 ? vh_jit_drain_depth(S) : vh_jit_rec_bytes(S) ? depth : 0;
+    return true;
+  }
   switch (which) {
     case 23:    // ... case 12 with its d3 leaf as a SET (VH_F_INSET): membership looked up per row, the value a bit field of the byte planes
     case 22:    // ... case 21 reading the CLUSTERED planes beside the grouped records (slot 15, 20 dwords a word group: d3 and d4)

@@ -20,7 +20,7 @@
 
 // (the wave's survivor queue holds VJ_QUEUE_CAP rows: vh_internal.h)
 #ifndef VJ_ABL
-#define VJ_ABL 0           // measurement builds only (VH_JIT_FLAGS=-DVJ_ABL=n): 8 = tuples are built, nothing is appended
+#define VJ_ABL 0           // measurement builds only (VH_JIT_FLAGS=-DVJ_ABL=n): 1 = every gather hits (the segment's first 64 records, whatever the survivor; the depth-0 drain), 8 = tuples are built, nothing is appended
 #endif
 #ifndef VJ_NT_GATHER
 #define VJ_NT_GATHER 0     // 1: a survivor's record is fetched with non-temporal loads
@@ -163,6 +163,7 @@ __device__ __forceinline__ void vj_drain(const VhPlanDev& P, uint32_t seg, uint3
   } else if constexpr (J::QPAY != 0) {
     J::unpack(row, gv, mv);            // `row` IS the survivor's record (vj_slot queued it): nothing to fetch
   } else {
+    if (VJ_ABL & 1) row = threadIdx.x & 63u;      // (measurement: ever the same 64 records of the segment — gathers that hit, wrong results)
     J::gather(P, seg, row, gv, mv);    // every load of the survivor is issued before the first value is looked at
   }
   if constexpr (J::ABLATE & 2) {       // ... the gathers and nothing behind them
@@ -175,6 +176,49 @@ __device__ __forceinline__ void vj_drain(const VhPlanDev& P, uint32_t seg, uint3
     return;
   }
   vj_sink<J>(P, seg, row, active, gv, mv, lds, xoff, nfresh, V);
+}
+// The pipelined drain (J::DRAIN_DEPTH groups deep; plans whose survivor is ONE packed record, J::REC_BYTES). One drain is a chain — queue
+// entry out of LDS, the record's gather, key and tuple, three or four LDS round trips of the ring writer — and a wave that runs one chain
+// after another sits out a random HBM line per 64 survivors with the few resident waves a writing scan keeps (vhh_launch.h, occ_cap). Here
+// the wave takes the NEXT group off the queue and issues its record loads before it sinks the oldest group it holds: a gather has a whole
+// sink (or two) to arrive in. A pending group is carried RAW — one or two registers a lane, unpacked only when it is sunk; carried unpacked,
+// the first shift would wait for the load — in a shift register of named values (r0 the newest), so the sink is compiled once per call
+// site whatever the depth. n0 / n1: entries of the group (wave-uniform; 0 = none).
+template <class J>
+struct VjPend {
+  typename J::rec_t r0, r1;
+  uint32_t n0 = 0, n1 = 0;
+};
+// `all`: a segment change, the end of the wave's work: everything queued AND everything pending is sunk, in the order it left the queue, under
+// `seg` — every pending entry is a place of that segment, because every segment change comes through here with `all` set. A wave that gives up
+// (MODE == HASH, V.H.dead) simply never comes back: what it holds is dropped with the attempt.
+template <class J>
+__device__ __forceinline__ void vj_drain_pipe(const VhPlanDev& P, uint32_t seg, const uint32_t* q, uint32_t& cnt, bool all, int lane, VjPend<J>& Q, char* lds, uint64_t xoff,
+                                              unsigned long long& nfresh, VjWave& V) {
+  static_assert(J::DRAIN_DEPTH == 1 || J::DRAIN_DEPTH == 2, "pipelined drain: one or two groups in flight");
+  for (;;) {
+    const bool more = cnt >= 64 || (all && cnt);
+    if (!more && !(all && (Q.n0 | Q.n1))) break;
+    uint32_t take = 0;
+    typename J::rec_t nr = Q.r0;                // (nothing to take: an empty group is shifted in behind the pending ones)
+    if (more) {
+      take = cnt >= 64 ? 64u : cnt;
+      cnt -= take;
+      const uint32_t r = (uint32_t)lane < take ? q[cnt + lane] : 0u;      // (idle lanes: record 0 of the segment, as vj_drain has it)
+      nr = J::rec_load(P, seg, r);
+    }
+    uint32_t on;
+    typename J::rec_t orec;
+    if constexpr (J::DRAIN_DEPTH == 1) { on = Q.n0; orec = Q.r0; }
+    else { on = Q.n1; orec = Q.r1; Q.n1 = Q.n0; Q.r1 = Q.r0; }
+    Q.n0 = take; Q.r0 = nr;
+    if (on) {
+      uint64_t gv[J::NG ? J::NG : 1], mv[J::NM ? J::NM : 1];
+      J::rec_unpack(orec, gv, mv);
+      vj_sink<J>(P, seg, 0u, (uint32_t)lane < on, gv, mv, lds, xoff, nfresh, V);
+      __builtin_amdgcn_wave_barrier();
+    }
+  }
 }
 // Two surviving rows per active lane (hashed partitioning): a survivor's loads are two or three dependent round trips — its columns and
 // where its ids lie, then the ids — and a wave that takes them one drain at a time sits out each of them with nothing else to do (few waves
@@ -627,6 +671,10 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
     if (have && !J::GPLANES) gstart = vj_group_start<J>(P, seg, wave_base, seg_rows, glit);
   }
   uint32_t cnt = 0;
+  // survivors whose records are in flight (vj_drain_pipe); depth 0, and every plan without a packed record: one drain after another, as ever
+  constexpr bool kPipe = J::REC_BYTES != 0 && J::DRAIN_DEPTH > 0 && J::ABLATE == 0 && !(VJ_ABL & 1);
+  VjPend<J> pend;
+  if constexpr (kPipe) { pend.r0 = typename J::rec_t(0); pend.r1 = typename J::rec_t(0); }
   if constexpr (J::GPLANES) {
     // ---- CLUSTERED planes (vh_grouped.h): the predicate bits of a tile lie in the order of its grouped records, word-major. The wave reads
     // only the words that cover the run [start[literal], end) of each of its tiles — no plane of the grouping column, no prefix over its
@@ -670,6 +718,7 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
       }
     };
     auto drain_gp = [&](uint32_t dseg, bool all) {
+      if constexpr (kPipe) { vj_drain_pipe<J>(P, dseg, q, cnt, all, lane, pend, lds, xoff, nfresh, V); return; }
       while (cnt >= 64 || (all && cnt)) {
         const uint32_t take = cnt >= 64 ? 64u : cnt;
         cnt -= take;
@@ -816,6 +865,7 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
     __builtin_amdgcn_wave_barrier();
     const bool flush = !nhave || nseg != seg;       // queue entries are rows (grouped records: places) of the current segment
     auto drain_queue = [&](bool all) {
+      if constexpr (kPipe) { vj_drain_pipe<J>(P, seg, q, cnt, all, lane, pend, lds, xoff, nfresh, V); return; }
       if constexpr (MODE == VH_MODE_HASH && J::HPART && J::QPAY == 0 && J::ABLATE == 0 && VJ_DRAIN2) {
         while (cnt >= 128) {                        // two rows per lane while there are that many (vj_drain2)
           cnt -= 128;

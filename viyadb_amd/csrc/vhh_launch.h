@@ -132,6 +132,13 @@ void QueryBuild::choose_grouped() {
   gplanes = true;
 }
 
+int vh_jit_drain_depth(const VhJitShape& s) {
+  if (!vh_jit_rec_bytes(s)) return 0;
+  int depth = VH_DRAIN_DEPTH_DEFAULT;
+  if (const char* e = test_env("VH_TEST_DRAIN_DEPTH")) depth = std::min(std::max(atoi(e), 0), VH_DRAIN_DEPTH_MAX);      // (A/B: depth 0 is the drain as it was)
+  return depth;
+}
+
 int QueryBuild::compile_kernel() {
   int rc = VH_OK; (void)rc;
   // ---------------- the scan kernel compiled for this plan shape (vh_jit.hip), when there is to be one
@@ -216,6 +223,7 @@ int QueryBuild::compile_kernel() {
       c.sext = vh_sop_sext((int)m.sop());
       if (!c.rowid && !c.bitset) { c.slot = (int)m.slot(); c.pitch = (int)P.colpitch[m.slot()]; c.rec = slot_rec[m.slot()]; c.off = slot_recoff[m.slot()]; c.stored = slot_stored[m.slot()]; c.bits = slot_bits[m.slot()]; }
     }
+    js.drain_depth = vh_jit_drain_depth(js);      // (last: it goes by the columns above)
     if (jit_try) {
       std::string jerr;
       // background build mode: a lookup. A shape nobody compiled yet (or that is being compiled) is the worker's: this query is planned for the
@@ -348,7 +356,11 @@ int QueryBuild::decompose_work() {
   // CU already stream at full rate, and every block fewer is a table flush fewer: C2 0.315 -> 0.308 ms, 400 M rows 1.217 -> 1.179)
   // (through the block's ring writer a block keeps its partitions' lines open, not every wave: four blocks per CU — over four fresh processes each
   // 1.296-1.312 ms per C3 query against 1.265-1.405 with three and 1.31-1.48 with five; an eighth of the table 0.283 against 0.294)
-  const int occ_cap = jk && mode == VH_MODE_DENSE_PART ? (jshape.part_ring ? 4 : 3) : jk && hpart ? 4 : jk && lanes ? 2 : 8;
+  // (round 9, the scan reading the clustered planes: no longer bound by bytes and open lines but by the latency of its drains — the gather of
+  // a survivor's packed record, the ring writer's LDS round trips — which a fifth block per CU hides: C3's scan + phase 2 0.771 / 0.676 / 0.633 ms
+  // with three / four / five, 0.745 / 0.663 / 0.631 with the pipelined drain; five is what 85-88 registers allow. Plans without a packed
+  // record were not measured again and keep four: profiles/r09/NOTES.md)
+  const int occ_cap = jk && mode == VH_MODE_DENSE_PART ? (jshape.part_ring ? (vh_jit_rec_bytes(jshape) ? 5 : 4) : 3) : jk && hpart ? 4 : jk && lanes ? 2 : 8;
   int blocks_per_cu = env_bpc > 0 ? env_bpc : occupancy > 0 ? std::min(occupancy, occ_cap) : (BLOCK == 1024 ? 1 : 4);
   if (const char* e = test_env("VH_TEST_BLOCKS_PER_CU")) { if (atoi(e) > 0) blocks_per_cu = occupancy > 0 ? std::min(occupancy, atoi(e)) : atoi(e); }   // (measurement: switched between two queries of one process)
   uint32_t unit_rows = step;
