@@ -110,7 +110,10 @@ def case_held_then_released():
     """Cases 1 and 2: the same history on a background table (worker held, then released) and on an inline twin; the modes converge."""
     hold("start")
     a = Twin(background=True)
+    arenas = a.dt.info()[2]
     fa = history(a, True)
+    a.dt.unpack()          # what the worker published goes out of the table's byte ledger as it came in
+    assert a.dt.info()[2] == arenas, f"device_bytes {a.dt.info()[2]} after vh_table_unpack, {arenas} before the first query"
     a.close()
     b = Twin(background=False)
     fb = history(b, False)

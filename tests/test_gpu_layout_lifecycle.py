@@ -425,3 +425,54 @@ def test_lifecycle_state_machine(place):
     if not JIT_OFF:                    # (compressed projections and predicate planes are read by the compiled kernels alone)
         need.update(planes=5, rebuild=3)
     assert all(total[k] >= v for k, v in need.items()), total
+
+
+def test_device_bytes_ledger():
+    """vh_table_info's device_bytes is a ledger every derived layout pays into and out of. A table that builds every kind of layout — narrow
+    copies, a projection, predicate planes in both forms, the grouped records and clustered planes — relocates them, grows past its reserve
+    (every arena moves, the grouped form starts over) and loses its predicate projections to a value that outgrew their bits reports, after
+    vh_table_unpack, exactly the bytes of an identical table that took the same syncs and never built a layout. Two segments of 5 000 rows
+    with room for 8 192: two full tiles and one of 904 rows. No byte count is written here: the second table is the yardstick throughout."""
+    h = C3Host(nseg=2, rows=5000, cap=8192, reserve=2)
+    y = C3Host(nseg=2, rows=5000, cap=8192, reserve=2)
+    try:
+        assert h.dt.info()[2] == y.dt.info()[2]
+        cols = h.dt.filter_columns(h.plan(0))
+        h.dt.narrow(cols)
+        _layouts(h)
+        h.dt.predpack(cols, sliced=False)
+        h.dt.predpack(cols, sliced=True)
+        flags = h.dt.warm(h.plan(HOT))
+        if not JIT_OFF:
+            assert flags & capi.INFO_GROUPED_PAYLOAD and flags & capi.INFO_GROUPED_PLANES, hex(flags)
+        built = h.dt.info()[2]
+        assert built > y.dt.info()[2]
+        res = h.check(HOT, "every layout built")
+        _assert_layouts(res, "every layout built")
+        assert JIT_OFF or (res.grouped_payload and res.grouped_planes), hex(res.flags)
+        assert h.check(capi.PLAN_NO_JIT, "narrow copies").narrow
+        h.dt.relocate(0)
+        assert h.dt.info()[2] == built
+        _assert_layouts(h.check(HOT, "relocated"), "relocated")
+        for t in (h, y):
+            t.add_segment(5000)                      # a third segment with room for two: every arena and every layout moves or starts over
+        assert h.dt.info()[0] == 3 and h.dt.info()[2] > y.dt.info()[2] > 0
+        res = h.check(HOT, "grown")
+        _assert_layouts(res, "grown")
+        assert JIT_OFF or (res.grouped_payload and res.grouped_planes), hex(res.flags)
+        assert h.check(capi.PLAN_NO_JIT, "narrow copies, grown").narrow
+        d = h.tab.segments[0]["d"]
+        row = int(np.flatnonzero((d[D2][:5000] == 1) & (d[D3][:5000] < 447) & (d[D4][:5000] >= 553))[0])
+        for t in (h, y):
+            t.tab.segments[0]["d"][D2][row] = 4      # d2 held 0..3 in 2 bits: both predicate projections and the clustered planes are void
+            t.sync(0, row, 1)
+        res = h.check(HOT, "d2 outgrew the planes")
+        assert res.packed and not res.predpack and not res.grouped_planes, hex(res.flags)
+        assert h.dt.info()[2] > y.dt.info()[2]
+        h.dt.unpack()
+        assert h.dt.info()[2] == y.dt.info()[2]
+        res = h.check(HOT & ~PACK, "no layout left")
+        assert not res.packed and not res.predpack and not res.narrow, hex(res.flags)
+    finally:
+        h.close()
+        y.close()

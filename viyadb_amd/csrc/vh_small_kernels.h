@@ -3,6 +3,7 @@
 #pragma once
 #include "vh_kernels.h"
 #include "vh_topk_key.h"
+#include "vhh_layout_math.h"
 
 // ----------------------------------------------------------- table finalisation
 // Combine the per-XCD private copies of a dense table into copy 0 (they were only ever
@@ -742,11 +743,8 @@ __global__ __launch_bounds__(256) void iota_kernel(uint64_t* p, uint64_t n) {
 // per column (C3: four lines of four column arenas -> one 32 B record). Built from the column arenas in HBM; a block
 // stages 256 records in LDS so that both the column reads and the record writes are coalesced.
 #define VH_PACK_MAX_COLS 8
-// One unit of work of the derived-layout kernels: rows [first, first + count) of segment `seg` (first a multiple of 256, count a multiple of 4
-// and at most VH_JOB_ROWS), of which the segment holds `seg_rows`. The host cuts what changed since a layout was last refreshed — whole
-// segments when it is built, the row ranges an upsert batch touched afterwards (vh_table::journal) — into such jobs; one block each.
-#define VH_JOB_ROWS 16384u
-struct VhJob { uint32_t seg, first, count, seg_rows; };
+// One unit of work of the derived-layout kernels is a VhJob (vhh_layout_math.h, with the host's job cutter): rows [first, first + count) of a
+// segment, one block each.
 struct VhPackArgs {
   int32_t ncols; uint32_t rec_bytes;
   const char* src[VH_PACK_MAX_COLS];   // column arenas

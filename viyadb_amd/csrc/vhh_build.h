@@ -17,7 +17,7 @@
 //       (behind an event on the library's stream: every sync up to E has landed when they start);
 //   (b) t->mu released: the kernels run; the worker waits for its stream;
 //   (c) under t->mu: publish — applied_epoch = E, per-segment stamps as of (a), linked into t->packs / t->predpacks / t->narrows.
-// The journalled refresh every derived layout has (derived_jobs) then re-derives what was synced after E before the first query reads the
+// The journalled refresh every derived layout has (derived_refresh) then re-derives what was synced after E before the first query reads the
 // layout; a row a sync rewrote while (b) read it lies in such a range by construction.
 //   * What keeps the arenas in place during (b): table_grow — the only code that replaces them — calls build_arenas_moving first, which waits
 //     (t->mu held by the sync, not needed by step (b)) until the worker's stream is idle, and bumps vh_table::arena_gen; step (c) sees the
@@ -107,7 +107,7 @@ struct VhBuild {
   std::thread worker;
   bool started = false, stop = false;
   hipStream_t stream = nullptr; hipEvent_t ev = nullptr; unsigned int* d_flag = nullptr;
-  VhJob* h_jobs = nullptr; size_t h_jobs_bytes = 0;
+  VhJobStage jobs;                     // the job list of the running layout job (one at a time: the worker waits for its stream before the next)
   ~VhBuild() {
     { std::lock_guard<std::mutex> lk(mu); stop = true; }
     cv.notify_all();
@@ -270,9 +270,9 @@ static int build_run_kernel(VhBuildJob* j) {
 // that is about to be replaced holds counts as free.
 static int grouped_room(const vh_table* t, const VhPack* pk, const VhPredPack* pp = nullptr, uint32_t gbits = 0) {
   size_t free_b = 0, total_b = 0;
-  const size_t need = (size_t)t->cap_seg * pk->stride;
-  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return 0; }
-  if (const VhGrouped* gr = pk->grouped.get()) free_b += (gr->base ? gr->bytes(pk->stride) : 0) + (gr->planes ? gr->planes_bytes() : 0);
+  const size_t need = (size_t)t->cap_seg * pk->rec.stride;
+  if (!device_mem(&free_b, &total_b)) return 0;
+  if (const VhGrouped* gr = pk->grouped.get()) free_b += gr->rec.held + gr->planes.held;
   if (free_b <= need + total_b / 4) return 0;
   if (!pp || !pp->sliced || pp->bits <= gbits) return 1;
   const size_t planes = (size_t)t->cap_seg * vh_gplanes_seg_bytes(t->segment_rows, vh_gplanes_group(pp->bits - gbits));
@@ -290,7 +290,7 @@ static int build_run_grouped(VhBuildJob* j) {
     for (auto& q : t->packs) if (q->serial == j->serial) pk = q.get();
     VhPredPack* pp = nullptr;
     for (auto& q : t->predpacks) if (j->pp_serial && q->serial == j->pp_serial) pp = q.get();
-    if (pk && pk->grouped && (!pp || (pk->grouped->planes && pk->grouped->pp_serial == pp->serial))) return 0;          // (vh_table_prepare or the worker's own query was faster; one grouped form per projection)
+    if (pk && pk->grouped && (!pp || (pk->grouped->planes.ptr && pk->grouped->pp_serial == pp->serial))) return 0;          // (vh_table_prepare or the worker's own query was faster; one grouped form per projection)
     const int room = pk ? grouped_room(t, pk, pp, j->gbits) : 0;
     if (pk && pk->grouped && room < 2) return 0;          // (no room for the planes it lacks: the records it has stay)
     if (room) {
@@ -315,24 +315,26 @@ static int build_run_layout(VhBuildJob* j) {
   };
   std::vector<int> sorted_cols = j->cols;
   std::sort(sorted_cols.begin(), sorted_cols.end());
-  auto exists = [&] {                      // (t->mu held) an explicit call built the same meanwhile
-    if (j->kind == VB_PACK) { for (auto& pk : t->packs) { std::vector<int> have = pk->cols; std::sort(have.begin(), have.end()); if (have == sorted_cols && pk->compressed == j->form) return true; } }
-    else if (j->kind == VB_PREDPACK) { for (auto& pp : t->predpacks) if (pp->cols == sorted_cols && pp->sliced == j->form) return true; }
-    else { for (auto& nw : t->narrows) if (nw->col == j->cols[0]) return true; }
-    return false;
+  auto exists = [&]() -> bool {            // (t->mu held) an explicit call built the same meanwhile
+    if (j->kind == VB_PACK) return pack_find(t, sorted_cols, j->form);
+    if (j->kind == VB_PREDPACK) return predpack_find(t, sorted_cols, j->form);
+    return narrow_find(t, j->cols[0]);
   };
   const auto t_begin = std::chrono::steady_clock::now();
   double lock_ms = 0;
   for (int attempt = 0; attempt < 4; ++attempt) {
+    // the ONE layout this job builds: its kind's object, and what every kind shares — the common state `L`, its arenas, its launch
     std::unique_ptr<VhPack> pk; std::unique_ptr<VhPredPack> pp; std::unique_ptr<VhNarrow> nw;
-    std::vector<char*> bufs;
+    VhLayout* L = nullptr;
+    std::vector<VhBuf*> bufs;
+    std::function<void(const VhJob*, size_t)> launch;
     size_t bytes = 0;
     uint64_t E = 0, gen = 0;
     uint32_t nseg_a = 0;
     std::vector<uint64_t> mod_a;
     size_t njobs = 0;
     hipError_t he = hipSuccess;
-    auto drop = [&] { for (char* b : bufs) if (b) (void)hipFree(b); bufs.clear(); };
+    auto drop = [&] { for (VhBuf* b : bufs) buf_free(nullptr, b); };
     // ---- (a)
     {
       const auto a0 = std::chrono::steady_clock::now();
@@ -341,53 +343,40 @@ static int build_run_layout(VhBuildJob* j) {
       if (j->cancel) return 2;
       if (sync_resolve(t)) return 1;
       if (exists()) return 0;
+      uint64_t row_limit = t->padded_rows;
       if (j->kind == VB_PACK) {
         if (pack_describe(t, j->cols, j->automatic, j->form, &pk)) return nothing(true);
-        pk->cap_seg = t->cap_seg;
-        bufs.push_back(nullptr); bytes = (size_t)t->cap_seg * pk->stride + 256;
+        L = pk.get(); bufs.push_back(&pk->rec); row_limit = rows_padded_256(t);
+        launch = [&](const VhJob* d_jobs, size_t n) { pack_launch(t, pk.get(), d_jobs, n, g_build.d_flag, g_build.stream); };
       } else if (j->kind == VB_PREDPACK) {
         if (predpack_describe(t, sorted_cols, j->automatic, j->form, &pp) || !pp) return nothing(true);
-        pp->cap_seg = t->cap_seg;
-        for (int q = 0; q < pp->nplanes; ++q) { bufs.push_back(nullptr); bytes += (size_t)t->cap_seg * pp->pstride[q] + 256; }
+        L = pp.get();
+        for (int q = 0; q < pp->nplanes; ++q) bufs.push_back(&pp->plane[q]);
+        launch = [&](const VhJob* d_jobs, size_t n) { predpack_launch(t, pp.get(), d_jobs, n, g_build.stream); };
       } else {
-        const int w = narrow_width_for(t, j->cols[0], t->nseg);
-        if (!w) return nothing(true);
-        nw.reset(new VhNarrow());
-        nw->col = j->cols[0]; nw->width = w; nw->automatic = j->automatic; nw->stride = t->padded_rows * (uint64_t)w; nw->cap_seg = t->cap_seg;
-        bufs.push_back(nullptr); bytes = (size_t)t->cap_seg * nw->stride + 256;
+        narrow_describe(t, j->cols[0], j->automatic, &nw);
+        if (!nw) return nothing(true);
+        L = nw.get(); bufs.push_back(&nw->copy);
+        launch = [&](const VhJob* d_jobs, size_t n) { narrow_launch(t, nw.get(), d_jobs, n, g_build.stream); };
       }
-      size_t free_b = 0, total_b = 0;      // room: a quarter of the device stays free, and a projection does not outgrow the table
-      if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b <= bytes + total_b / 4 || (j->kind == VB_PACK && bytes > t->device_bytes + 256)) return nothing(false);
-      for (size_t q = 0; q < bufs.size(); ++q) {
-        const size_t b = pk ? bytes : nw ? bytes : (size_t)t->cap_seg * pp->pstride[q] + 256;
-        if (hipMalloc(&bufs[q], b) != hipSuccess) { (void)hipGetLastError(); drop(); return nothing(false); }
-        trace_alloc("background layout", bufs[q], b);
-      }
-      if (pk) pk->base = bufs[0];
-      if (nw) nw->base = bufs[0];
-      if (pp) for (int q = 0; q < pp->nplanes; ++q) pp->pbase[q] = bufs[q];
+      L->cap_seg = t->cap_seg; L->seg_mod.assign(t->cap_seg, 0);
+      for (VhBuf* b : bufs) bytes += b->bytes(t->cap_seg);
+      // room: a quarter of the device stays free, and a projection does not outgrow the table
+      if (!device_room(bytes) || (pk && bytes > t->device_bytes + 256)) return nothing(false);
+      for (VhBuf* b : bufs) if (buf_alloc(nullptr, b, t->cap_seg, "background layout", true)) { drop(); return nothing(false); }
       E = t->sync_epoch; gen = t->arena_gen; nseg_a = t->nseg; mod_a = t->seg_mod;
       std::vector<VhJob> jobs;
-      derived_jobs(t, 0, std::vector<uint64_t>(t->cap_seg, 0), pk ? (t->segment_rows + 255) / 256 * 256 : t->padded_rows, &jobs);
+      derived_jobs(t, *L, row_limit, false, &jobs);
       njobs = jobs.size();
       if (njobs) {
-        if (njobs * sizeof(VhJob) > g_build.h_jobs_bytes) {
-          if (g_build.h_jobs) (void)hipHostFree(g_build.h_jobs);
-          g_build.h_jobs = nullptr; g_build.h_jobs_bytes = 0;
-          const size_t nb = std::max<size_t>(njobs * sizeof(VhJob) * 2, 1u << 16);
-          if (hipHostMalloc((void**)&g_build.h_jobs, nb, hipHostMallocCoherent) != hipSuccess) { (void)hipGetLastError(); drop(); return 1; }
-          g_build.h_jobs_bytes = nb;
-        }
-        memcpy(g_build.h_jobs, jobs.data(), njobs * sizeof(VhJob));
+        const VhJob* d_jobs = nullptr;
+        bool pending = false;                        // (the worker waited for its stream after the last list: the staging is free)
+        g_build.jobs.used = 0;
+        if (derived_upload(&g_build.jobs, &pending, jobs, &d_jobs)) { (void)hipGetLastError(); drop(); return 1; }
         he = hipEventRecord(g_build.ev, g_ctx.stream);                       // every sync up to E has landed before the build kernels read
         if (he == hipSuccess) he = hipStreamWaitEvent(g_build.stream, g_build.ev, 0);
         if (he == hipSuccess && pk) he = hipMemsetAsync(g_build.d_flag, 0, 256, g_build.stream);
-        if (he == hipSuccess) {
-          if (pk) pack_launch(t, pk.get(), g_build.h_jobs, njobs, g_build.d_flag, g_build.stream);
-          else if (pp) predpack_launch(t, pp.get(), g_build.h_jobs, njobs, g_build.stream);
-          else narrow_launch(t, nw.get(), g_build.h_jobs, njobs, g_build.stream);
-          he = hipGetLastError();
-        }
+        if (he == hipSuccess) { launch(d_jobs, njobs); he = hipGetLastError(); }
         std::lock_guard<std::mutex> bl(g_build.mu);
         g_build.reading = true;
       }
@@ -410,7 +399,7 @@ static int build_run_layout(VhBuildJob* j) {
       const auto c0 = std::chrono::steady_clock::now();
       std::unique_lock<std::mutex> lk(t->mu);
       struct Timer { double& acc; std::chrono::steady_clock::time_point t0; ~Timer() { acc += build_ms_since(t0); } } timer{lock_ms, c0};
-      const bool moved = t->arena_gen != gen || t->cap_seg != (pk ? pk->cap_seg : pp ? pp->cap_seg : nw->cap_seg) || (E && E < t->journal_floor);
+      const bool moved = t->arena_gen != gen || t->cap_seg != L->cap_seg || (E && E < t->journal_floor);
       const bool again = !j->cancel && he == hipSuccess && (moved || (ovf && pk && pk->compressed));
       if (j->cancel || he != hipSuccess || moved || ovf || exists()) {
         lk.unlock();
@@ -420,12 +409,12 @@ static int build_run_layout(VhBuildJob* j) {
         if (he != hipSuccess || ovf) { std::lock_guard<std::mutex> l2(t->mu); (void)nothing(false); return he != hipSuccess ? 1 : 3; }
         return 0;
       }
-      std::vector<uint64_t> stamps(t->cap_seg, 0);
-      for (uint32_t s = 0; s < nseg_a && s < stamps.size(); ++s) stamps[s] = mod_a[s];
-      if (pk) { pk->seg_mod = stamps; pk->applied_epoch = E; pk->serial = ++t->layout_serial; t->packs.push_back(std::move(pk)); }
-      else if (pp) { pp->seg_mod = stamps; pp->applied_epoch = E; pp->serial = ++t->layout_serial; t->predpacks.push_back(std::move(pp)); }
-      else { nw->seg_mod = stamps; nw->applied_epoch = E; t->narrows.push_back(std::move(nw)); }
-      t->device_bytes += bytes;
+      for (uint32_t s = 0; s < nseg_a && s < L->seg_mod.size(); ++s) L->seg_mod[s] = mod_a[s];      // the stamps as of (a)
+      L->applied_epoch = E; L->serial = ++t->layout_serial;
+      for (VhBuf* b : bufs) t->device_bytes += b->held;      // (the one place beside buf_alloc: the arenas were made before the layout was the table's)
+      if (pk) t->packs.push_back(std::move(pk));
+      else if (pp) t->predpacks.push_back(std::move(pp));
+      else t->narrows.push_back(std::move(nw));
     }
     const double ms = build_ms_since(t_begin);
     build_count(t, [&](vh_build_info& i) { ++i.layouts_built; i.layout_ms += ms; i.lock_ms += lock_ms; });

@@ -1,58 +1,44 @@
 // vhh_derived.h — host side of libviya_hip, part of viya_hip.hip's translation unit (included there, in order; not a stand-alone header):
-// derived layouts: payload projections (vh_table_pack) and narrow predicate copies (vh_table_narrow).
-// ------------------------------------------------------- payload projections (vh_table_pack)
-static uint64_t order_key_of_bits(int elem, uint64_t bits);      // (typed host helpers: vhh_result.h)
-static uint64_t bits_of_order_key(int elem, uint64_t k);
+// the derived layouts — second forms of the column arenas that the scan kernels read instead of them:
+//   * payload projections (vh_table_pack, VhPack): a few columns row-major in one record per row, plain, compressed or as bit fields;
+//   * their grouped form (VhGrouped): the 4-byte bit records of every 2048-row tile sorted by an equality column, the tiles' headers, and
+//     beside them the clustered planes — the other predicate columns' bits in the tiles' grouped order;
+//   * narrow copies (vh_table_narrow, VhNarrow): an unsigned 32-bit predicate column at 8 or 16 bits;
+//   * predicate projections (vh_table_predpack, VhPredPack): the predicate columns as bit fields of one word per row, as byte planes or bit-sliced.
+// They have ONE shape. Every layout is a VhLayout (capacity, per-segment stamps, the journal epoch it is current at, serial) that owns
+// VhBuf arenas (vhh_table.h); arenas come and go through buf_alloc / buf_free alone, which keep the table's byte ledger; derived_each
+// visits every arena of a table (bytes, move, settle, unpack, destroy). What is specific to a kind is its description (*_describe: fields
+// and strides from the recorded stats, on top of vhh_layout_math.h), its build kernel (*_launch) and how it is found (*_find); the
+// rest is written once:
+//   * derived_refresh — grow with the table, cut what the journal says changed into jobs (vh_cut_jobs, vhh_layout_math.h), upload, launch,
+//     order queries behind the launch, stamp. The background build (vhh_build.h) uses the same describe / launch / upload pieces off the lock;
+//   * derived_drop — quiesce the table, wait for the library's stream, free through the ledger, erase;
+//   * derived_move / derived_settle — try other places for the arenas (vh_table_prepare, vh_table_relocate).
 #define VH_PACK_STALE 9001      // (internal) pack_refresh: a value no longer fits its stored width, the projection must go
-// What a derived layout that was current at `applied_epoch` (per segment: at `seg_mod[s]`) has to re-derive, as jobs for its kernel: the
-// row ranges journalled since (vh_table::journal), cut at 256-row boundaries, merged, and split into pieces of VH_JOB_ROWS; whole segments
-// for a layout that is new, or so far behind that the journal no longer reaches back to it. `row_limit`: rows a segment of the layout has
-// room for (a projection's stride is padded to 256 rows, a narrow copy's to 64).
-static void derived_jobs(const vh_table* t, uint64_t applied_epoch, const std::vector<uint64_t>& seg_mod, uint64_t row_limit, std::vector<VhJob>* jobs) {
-  jobs->clear();
-  std::vector<std::pair<uint64_t, uint64_t>> ranges;      // (seg << 32 | first, last)
-  auto whole = [&](uint32_t s) { if (s < seg_mod.size() && seg_mod[s] != t->seg_mod[s]) ranges.emplace_back((uint64_t)s << 32, row_limit); };
-  if (applied_epoch == 0 || applied_epoch < t->journal_floor) {
-    for (uint32_t s = 0; s < t->nseg; ++s) whole(s);
-  } else {
-    auto it = std::upper_bound(t->journal.begin(), t->journal.end(), applied_epoch, [](uint64_t e, const VhChange& c) { return e < c.epoch; });
-    for (; it != t->journal.end(); ++it) {
-      if (it->seg >= t->nseg || it->seg >= seg_mod.size()) continue;
-      if (seg_mod[it->seg] == 0) { whole(it->seg); continue; }          // a segment this layout never held (the table grew)
-      const uint64_t a = it->first & ~255ull, b = std::min<uint64_t>(((uint64_t)it->last + 255) & ~255ull, row_limit);
-      if (a < b) ranges.emplace_back(((uint64_t)it->seg << 32) | a, b);
-    }
-  }
-  if (ranges.empty()) return;
-  std::sort(ranges.begin(), ranges.end());
-  size_t o = 0;
-  for (size_t i = 1; i < ranges.size(); ++i) {
-    if ((ranges[i].first >> 32) == (ranges[o].first >> 32) && (ranges[i].first & 0xFFFFFFFFull) <= ranges[o].second) ranges[o].second = std::max(ranges[o].second, ranges[i].second);
-    else ranges[++o] = ranges[i];
-  }
-  ranges.resize(o + 1);
-  for (const auto& r : ranges) {
-    const uint32_t seg = (uint32_t)(r.first >> 32);
-    const uint64_t a = r.first & 0xFFFFFFFFull, b = std::min(r.second, row_limit);
-    for (uint64_t f = a; f < b; f += VH_JOB_ROWS) jobs->push_back(VhJob{seg, (uint32_t)f, (uint32_t)std::min<uint64_t>(VH_JOB_ROWS, b - f), (uint32_t)t->seg_rows[seg]});
-  }
+#define VH_NO_ROOM 9002         // (internal) derived_refresh of a layout that starts over when the table grew: no room for an arena it cannot do without
+static uint64_t rows_padded_256(const vh_table* t) { return (t->segment_rows + 255) / 256 * 256; }      // rows a projection's stride has room for
+// What layout `L` has to re-derive, as jobs for its kernel (vh_cut_jobs): the journal's ranges since it was current, or whole segments.
+static void derived_jobs(const vh_table* t, const VhLayout& L, uint64_t row_limit, bool whole_tiles, std::vector<VhJob>* jobs) {
+  const VhCutTable T{t->journal.data(), t->journal.size(), t->journal_floor, t->seg_mod.data(), t->seg_rows.data(), t->nseg};
+  vh_cut_jobs(T, VhCutLayout{L.seg_mod.data(), L.seg_mod.size(), L.applied_epoch, row_limit}, whole_tiles, jobs);
 }
-// The jobs in pinned memory the kernels read them from (they are 16 bytes each; a list lives until the stream has been waited for).
-static int derived_upload(vh_table* t, const std::vector<VhJob>& jobs, const VhJob** out) {
+// The jobs in pinned memory the kernels read them from. Lists are appended while earlier ones may still be read; when the staging is full
+// and *pending says so, the library's stream — the reader — is waited for first.
+static int derived_upload(VhJobStage* S, bool* pending, const std::vector<VhJob>& jobs, const VhJob** out) {
   const size_t bytes = jobs.size() * sizeof(VhJob);
-  if (t->h_jobs_used + bytes > t->h_jobs_bytes) {
-    if (t->derived_pending) { HIP_TRY(hipStreamSynchronize(g_ctx.stream)); t->derived_pending = false; }      // (earlier lists are still being read)
-    t->h_jobs_used = 0;
-    if (bytes > t->h_jobs_bytes) {
-      if (t->h_jobs) { HIP_TRY(hipHostFree(t->h_jobs)); t->h_jobs = nullptr; t->h_jobs_bytes = 0; }
+  if (S->used + bytes > S->bytes) {
+    if (*pending) { HIP_TRY(hipStreamSynchronize(g_ctx.stream)); *pending = false; }      // (earlier lists are still being read)
+    S->used = 0;
+    if (bytes > S->bytes) {
+      if (S->buf) { HIP_TRY(hipHostFree(S->buf)); S->buf = nullptr; S->bytes = 0; }
       const size_t nb = std::max<size_t>(bytes * 2, 1u << 16);
-      HIP_TRY(hipHostMalloc((void**)&t->h_jobs, nb, hipHostMallocCoherent));
-      t->h_jobs_bytes = nb;
+      HIP_TRY(hipHostMalloc((void**)&S->buf, nb, hipHostMallocCoherent));
+      S->bytes = nb;
     }
   }
-  memcpy(t->h_jobs + t->h_jobs_used, jobs.data(), bytes);
-  *out = reinterpret_cast<const VhJob*>(t->h_jobs + t->h_jobs_used);
-  t->h_jobs_used += (bytes + 255) / 256 * 256;
+  memcpy(S->buf + S->used, jobs.data(), bytes);
+  *out = reinterpret_cast<const VhJob*>(S->buf + S->used);
+  S->used += (bytes + 255) / 256 * 256;
   return VH_OK;
 }
 static int derived_enqueued(vh_table* t) {       // a refresh kernel went onto g_ctx.stream: queries launched from now on wait for it (QueryBuild::launch)
@@ -61,7 +47,10 @@ static int derived_enqueued(vh_table* t) {       // a refresh kernel went onto g
   t->derived_pending = true;
   return VH_OK;
 }
-static int derived_waited(vh_table* t);
+static int derived_waited(vh_table* t) {         // the host waited for g_ctx.stream: nothing pending, the job lists are free
+  t->derived_pending = false; t->jobs.used = 0;
+  return VH_OK;
+}
 // Work about to go onto a query's own stream reads derived layouts (and arenas): it is ordered behind the refreshes enqueued on g_ctx.stream.
 static int derived_fence(vh_table* t, hipStream_t st) {
   if (!t->derived_pending) return VH_OK;
@@ -69,180 +58,131 @@ static int derived_fence(vh_table* t, hipStream_t st) {
   HIP_TRY(hipStreamWaitEvent(st, t->derived_ev, 0));
   return VH_OK;
 }
-static int derived_waited(vh_table* t) {         // the host waited for g_ctx.stream: nothing pending, the job lists are free
-  t->derived_pending = false; t->h_jobs_used = 0;
-  return VH_OK;
+// Before an arena of a layout is freed or replaced (t->mu held): no launched query reads it, no refresh writes it, the job lists are free.
+static int derived_idle(vh_table* t) {
+  table_quiesce(t);
+  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+  return derived_waited(t);
 }
 
-// One launch of the projection's build kernel over a list of jobs (pinned memory), on `st`; `flag`: the "a value outgrew its stored width" word.
+// ------------------------------------------------------- the build kernels' launches: over a list of jobs (pinned memory), on `st`
+template <class Args> static void args_sources(const vh_table* t, const std::vector<int>& cols, Args* A) {      // the source columns' arenas
+  for (size_t c = 0; c < cols.size(); ++c) {
+    const VhColumn& col = t->cols[cols[c]];
+    A->src[c] = col.base; A->src_stride[c] = col.stride; A->esize[c] = (uint32_t)col.esize;
+  }
+}
+static void pack_bits_args(const vh_table* t, const VhPack* pk, char* dst, const VhJob* d_jobs, unsigned int* flag, VhPackBitsArgs* B) {
+  B->ncols = (int32_t)pk->cols.size(); B->rec_bytes = pk->rec_bytes;
+  args_sources(t, pk->cols, B);
+  for (size_t c = 0; c < pk->cols.size(); ++c) { B->bitoff[c] = pk->bitoff[c]; B->bitw[c] = pk->bitw[c]; }
+  B->overflow = flag; B->dst = dst; B->dst_stride = pk->rec.stride; B->jobs = d_jobs;
+}
+// `flag`: the "a value outgrew its stored width" word.
 static void pack_launch(const vh_table* t, const VhPack* pk, const VhJob* d_jobs, size_t njobs, unsigned int* flag, hipStream_t st) {
   if (pk->bits) {
     VhPackBitsArgs B{};
-    B.ncols = (int32_t)pk->cols.size(); B.rec_bytes = pk->rec_bytes;
-    for (size_t c = 0; c < pk->cols.size(); ++c) {
-      const VhColumn& col = t->cols[pk->cols[c]];
-      B.src[c] = col.base; B.src_stride[c] = col.stride; B.esize[c] = (uint32_t)col.esize; B.bitoff[c] = pk->bitoff[c]; B.bitw[c] = pk->bitw[c];
-    }
-    B.overflow = flag; B.dst = pk->base; B.dst_stride = pk->stride; B.jobs = d_jobs;
+    pack_bits_args(t, pk, pk->rec.ptr, d_jobs, flag, &B);
     hipLaunchKernelGGL(pack_bits_kernel, dim3((unsigned)njobs), dim3(256), 0, st, B);
   } else {
     VhPackArgs A{};
     A.ncols = (int32_t)pk->cols.size(); A.rec_bytes = pk->rec_bytes;
+    args_sources(t, pk->cols, &A);
     for (size_t c = 0; c < pk->cols.size(); ++c) {
-      const VhColumn& col = t->cols[pk->cols[c]];
-      A.src[c] = col.base; A.src_stride[c] = col.stride; A.esize[c] = (uint32_t)col.esize; A.off[c] = pk->off[c];
-      A.wbytes[c] = pk->width[c];
-      if (col.elem == VH_I8 || col.elem == VH_I16 || col.elem == VH_I32 || col.elem == VH_I64) A.sgn_mask |= 1u << c;
+      A.off[c] = pk->off[c]; A.wbytes[c] = pk->width[c];
+      if (vh_elem_signed(t->cols[pk->cols[c]].elem)) A.sgn_mask |= 1u << c;
     }
-    A.overflow = flag; A.dst = pk->base; A.dst_stride = pk->stride; A.jobs = d_jobs;
+    A.overflow = flag; A.dst = pk->rec.ptr; A.dst_stride = pk->rec.stride; A.jobs = d_jobs;
     hipLaunchKernelGGL(pack_kernel, dim3((unsigned)njobs), dim3(256), 256 * pk->rec_bytes, st, A);
   }
 }
-// ---- the grouped form of a bit-record projection (VhGrouped): built and refreshed with its projection, tile by tile
-static void grouped_drop(vh_table* t, VhPack* pk) {      // (the caller quiesced the table)
-  VhGrouped* gr = pk->grouped.get();
-  if (!gr) return;
-  if (gr->base) { (void)hipFree(gr->base); t->device_bytes -= gr->bytes(pk->stride); }
-  if (gr->hdr) { (void)hipFree(gr->hdr); t->device_bytes -= gr->hdr_bytes(); }
-  if (gr->planes) { (void)hipFree(gr->planes); t->device_bytes -= gr->planes_bytes(); }
-  pk->grouped.reset();
-}
-// The clustered planes' fields: those of bit-sliced predicate projection `pp` without the grouping column's. false: `pp` has nothing to cluster
-// (it lacks the grouping column, or holds no other).
-static bool grouped_planes_describe(const vh_table* t, VhGrouped* gr, const VhPredPack* pp) {
-  if (!pp || !pp->sliced) return false;
-  const size_t at = (size_t)(std::find(pp->cols.begin(), pp->cols.end(), gr->col) - pp->cols.begin());
-  if (at >= pp->cols.size() || pp->bitw[at] != gr->bits || pp->bits <= gr->bits || pp->bits > 32) return false;
-  gr->G = vh_gplanes_group(pp->bits - gr->bits); gr->goff = pp->bitoff[at];
-  gr->planes_stride = vh_gplanes_seg_bytes(t->segment_rows, gr->G);
-  gr->pp_serial = pp->serial; gr->pp_cols = pp->cols; gr->pp_bitoff = pp->bitoff; gr->pp_bitw = pp->bitw;
-  return true;
-}
-// Re-derive the tiles that hold a row journalled since the grouped form was last current: derived_jobs' ranges widened to whole tiles (one
-// changed row moves the places of its tile's rows behind it), one block per tile. A projection that grew starts over in new buffers.
-static int grouped_refresh(vh_table* t, VhPack* pk) {
-  VhGrouped* gr = pk->grouped.get();
-  if (!gr || !t->nseg) return VH_OK;
-  if (gr->cap_seg < t->cap_seg) {
-    table_quiesce(t);
-    HIP_TRY(hipStreamSynchronize(g_ctx.stream)); derived_waited(t);
-    if (gr->base) { (void)hipFree(gr->base); t->device_bytes -= gr->bytes(pk->stride); gr->base = nullptr; }
-    if (gr->hdr) { (void)hipFree(gr->hdr); t->device_bytes -= gr->hdr_bytes(); gr->hdr = nullptr; }
-    if (gr->planes) { (void)hipFree(gr->planes); t->device_bytes -= gr->planes_bytes(); gr->planes = nullptr; }
-    gr->cap_seg = t->cap_seg;
-    if (hipMalloc(&gr->base, gr->bytes(pk->stride)) != hipSuccess || hipMalloc(&gr->hdr, gr->hdr_bytes()) != hipSuccess) {      // no room: the ungrouped records answer
-      (void)hipGetLastError();
-      if (gr->base) (void)hipFree(gr->base);
-      if (gr->hdr) (void)hipFree(gr->hdr);
-      pk->grouped.reset();
-      return VH_OK;
+// The grouped form of `pk`: records, headers and — where it has them — the clustered planes out of one launch, one block per tile.
+static void grouped_launch(const vh_table* t, const VhPack* pk, const VhJob* d_jobs, size_t njobs, unsigned int* flag, hipStream_t st) {
+  const VhGrouped* gr = pk->grouped.get();
+  VhGroupArgs A{};
+  pack_bits_args(t, pk, gr->rec.ptr, d_jobs, flag, &A.B);
+  const VhColumn& gc = t->cols[gr->col];
+  A.gsrc = gc.base; A.gsrc_stride = gc.stride; A.gesize = (uint32_t)gc.esize; A.gbits = gr->bits;
+  A.hdr = gr->hdr.ptr; A.hdr_stride = gr->hdr.stride;
+  if (gr->planes.ptr) {
+    A.pncols = (int32_t)gr->pp_cols.size(); A.goff = gr->goff; A.G = gr->G;
+    for (size_t c = 0; c < gr->pp_cols.size(); ++c) {
+      const VhColumn& col = t->cols[gr->pp_cols[c]];
+      A.psrc[c] = col.base; A.psrc_stride[c] = col.stride; A.pesize[c] = (uint32_t)col.esize; A.pbitoff[c] = gr->pp_bitoff[c];
     }
-    trace_alloc("grouped projection", gr->base, gr->bytes(pk->stride));
-    t->device_bytes += gr->bytes(pk->stride) + gr->hdr_bytes();
-    if (gr->G) {          // the clustered planes, where there is room for them; the grouped records alone otherwise
-      if (hipMalloc(&gr->planes, gr->planes_bytes()) != hipSuccess) { (void)hipGetLastError(); gr->planes = nullptr; gr->G = 0; gr->pp_serial = 0; }
-      else { trace_alloc("clustered planes", gr->planes, gr->planes_bytes()); t->device_bytes += gr->planes_bytes(); }
-    }
-    gr->seg_mod.assign(t->cap_seg, 0);
-    gr->applied_epoch = 0;
+    A.planes = gr->planes.ptr; A.planes_stride = gr->planes.stride;
   }
-  if (gr->applied_epoch == t->sync_epoch) return VH_OK;
-  std::vector<VhJob> ranges, jobs;
-  const uint64_t row_limit = (t->segment_rows + 255) / 256 * 256;
-  derived_jobs(t, gr->applied_epoch, gr->seg_mod, row_limit, &ranges);
-  std::vector<uint64_t> tiles;      // seg << 32 | tile
-  for (const VhJob& j : ranges)
-    for (uint64_t b = (uint64_t)j.first / VH_GROUP_TILE; b * VH_GROUP_TILE < (uint64_t)j.first + j.count; ++b) tiles.push_back(((uint64_t)j.seg << 32) | b);
-  std::sort(tiles.begin(), tiles.end());
-  tiles.erase(std::unique(tiles.begin(), tiles.end()), tiles.end());
-  for (uint64_t k : tiles) { const uint32_t seg = (uint32_t)(k >> 32); jobs.push_back(VhJob{seg, (uint32_t)(k & 0xFFFFFFFFull) * VH_GROUP_TILE, VH_GROUP_TILE, (uint32_t)t->seg_rows[seg]}); }
-  if (!jobs.empty()) {
-    const VhJob* d_jobs = nullptr;
-    if (int rc = derived_upload(t, jobs, &d_jobs)) return rc;
-    if (!t->d_packflag) { HIP_TRY(hipMalloc((void**)&t->d_packflag, 256)); HIP_TRY(hipMemsetAsync(t->d_packflag, 0, 256, g_ctx.stream)); }
-    VhGroupArgs A{};
-    A.B.ncols = (int32_t)pk->cols.size(); A.B.rec_bytes = pk->rec_bytes;
-    for (size_t c = 0; c < pk->cols.size(); ++c) {
-      const VhColumn& col = t->cols[pk->cols[c]];
-      A.B.src[c] = col.base; A.B.src_stride[c] = col.stride; A.B.esize[c] = (uint32_t)col.esize; A.B.bitoff[c] = pk->bitoff[c]; A.B.bitw[c] = pk->bitw[c];
-    }
-    A.B.overflow = t->d_packflag; A.B.dst = gr->base; A.B.dst_stride = pk->stride; A.B.jobs = d_jobs;
-    const VhColumn& gc = t->cols[gr->col];
-    A.gsrc = gc.base; A.gsrc_stride = gc.stride; A.gesize = (uint32_t)gc.esize; A.gbits = gr->bits;
-    A.hdr = gr->hdr; A.hdr_stride = gr->hdr_stride;
-    if (gr->planes) {
-      A.pncols = (int32_t)gr->pp_cols.size(); A.goff = gr->goff; A.G = gr->G;
-      for (size_t c = 0; c < gr->pp_cols.size(); ++c) {
-        const VhColumn& col = t->cols[gr->pp_cols[c]];
-        A.psrc[c] = col.base; A.psrc_stride[c] = col.stride; A.pesize[c] = (uint32_t)col.esize; A.pbitoff[c] = gr->pp_bitoff[c];
-      }
-      A.planes = gr->planes; A.planes_stride = gr->planes_stride;
-    }
-    hipLaunchKernelGGL(group_bits_kernel, dim3((unsigned)jobs.size()), dim3(256), 0, g_ctx.stream, A);
-    HIP_TRY(hipGetLastError());
-    if (int rc = derived_enqueued(t)) return rc;
-  }
-  for (uint32_t s = 0; s < t->nseg; ++s) gr->seg_mod[s] = t->seg_mod[s];
-  gr->applied_epoch = t->sync_epoch;
+  hipLaunchKernelGGL(group_bits_kernel, dim3((unsigned)njobs), dim3(256), 0, st, A);
+}
+static void narrow_launch(const vh_table* t, const VhNarrow* nw, const VhJob* d_jobs, size_t njobs, hipStream_t st) {
+  const VhColumn& c = t->cols[nw->col];
+  if (nw->width == 1)
+    hipLaunchKernelGGL((narrow_kernel<uint8_t>), dim3((unsigned)njobs), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(c.base), c.stride / 4,
+                       reinterpret_cast<uint8_t*>(nw->copy.ptr), nw->copy.stride, d_jobs);
+  else
+    hipLaunchKernelGGL((narrow_kernel<uint16_t>), dim3((unsigned)njobs), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(c.base), c.stride / 4,
+                       reinterpret_cast<uint16_t*>(nw->copy.ptr), nw->copy.stride / 2, d_jobs);
+}
+static void predpack_launch(const vh_table* t, const VhPredPack* pp, const VhJob* d_jobs, size_t njobs, hipStream_t st) {
+  VhPredPackArgs A{};
+  A.ncols = (int32_t)pp->cols.size(); A.nplanes = pp->nplanes;
+  args_sources(t, pp->cols, &A);
+  for (size_t c = 0; c < pp->cols.size(); ++c) A.bitoff[c] = pp->bitoff[c];
+  for (int q = 0; q < pp->nplanes; ++q) { A.plane[q] = pp->plane[q].ptr; A.plane_stride[q] = pp->plane[q].stride; A.plane_width[q] = (uint32_t)pp->pwidth[q]; A.plane_pos[q] = (uint32_t)pp->ppos[q]; }
+  A.jobs = d_jobs;
+  if (pp->sliced) hipLaunchKernelGGL(predslice_kernel, dim3((unsigned)njobs), dim3(256), 0, st, A, pp->bits, pp->pitch);
+  else hipLaunchKernelGGL(predpack_kernel, dim3((unsigned)njobs), dim3(256), 0, st, A);
+}
+static int packflag_ready(vh_table* t) {       // the projection kernels' overflow word
+  if (!t->d_packflag) { HIP_TRY(hipMalloc((void**)&t->d_packflag, 256)); HIP_TRY(hipMemsetAsync(t->d_packflag, 0, 256, g_ctx.stream)); }
   return VH_OK;
 }
-// The grouped form of `pk` by column `col`, whose field in the bit-sliced planes has `bits` bits: built (or built again for another column or
-// width) and brought up to date. Bit-field records of 4 bytes only; nullptr and VH_OK where there is no room for it.
-// `pp`: the bit-sliced predicate projection whose other columns' bits are kept clustered beside the records (nullptr: records alone — no such
-// projection, or no room). A form whose planes belong to another projection than `pp` starts over: records, headers and planes are one launch.
-static int grouped_build(vh_table* t, VhPack* pk, int col, uint32_t bits, const VhPredPack* pp = nullptr) {
-  if (!pk->bits || pk->rec_bytes != 4 || bits == 0 || bits > VH_GROUP_MAX_BITS || col < 0 || (size_t)col >= t->cols.size()) return VH_OK;
-  if (pk->grouped && (pk->grouped->col != col || pk->grouped->bits != bits || (pp && (!pk->grouped->planes || pk->grouped->pp_serial != pp->serial)))) {
-    table_quiesce(t);
-    HIP_TRY(hipStreamSynchronize(g_ctx.stream)); derived_waited(t);
-    grouped_drop(t, pk);
-  }
-  if (!pk->grouped) {
-    pk->grouped.reset(new VhGrouped());
-    pk->grouped->col = col; pk->grouped->bits = bits;
-    const uint64_t tiles = (t->segment_rows + VH_GROUP_TILE - 1) / VH_GROUP_TILE;
-    pk->grouped->hdr_stride = (tiles * vh_grouped_hdr_bytes(bits) + 63) / 64 * 64;
-    (void)grouped_planes_describe(t, pk->grouped.get(), pp);
-  }
-  return grouped_refresh(t, pk);
-}
 
-// Bring the projection up to date with the arenas: re-pack what changed since it was last packed (derived_jobs) in ONE launch.
-static int pack_refresh_records(vh_table* t, VhPack* pk);
-static int pack_refresh(vh_table* t, VhPack* pk, uint32_t first, uint32_t n) {
-  (void)first; (void)n;
-  if (int rc = pack_refresh_records(t, pk)) return rc;
-  return grouped_refresh(t, pk);          // (its grouped form follows in the same call: a plan finds both, and the planes, at one epoch)
-}
-static int pack_refresh_records(vh_table* t, VhPack* pk) {
+// ------------------------------------------------------- the refresh path
+// What differs between the layouts when they follow the table.
+struct VhRefresh {
+  VhBuf* bufs[4] = {}; const char* what[4] = {}; int nbufs = 0;
+  uint64_t row_limit = 0;        // rows a segment of the layout has room for: padded to 256 (projections, the grouped form) or vh_table::padded_rows
+  bool whole_tiles = false;      // the ranges widened to whole 2048-row tiles
+  bool restart = false;          // when the table grew: true — the arenas are made anew and everything is derived again (arenas of stride 0 are not
+  int required = 0;              //   made; no room for one of the first `required`: VH_NO_ROOM, for a later one: it stays away); false — contents copied
+  bool overflow_wait = false;    // wait for the kernel's overflow word: VH_PACK_STALE when a value outgrew its stored width
+};
+// Nothing to do — the test every query of a packed plan makes before anything else of a refresh exists.
+static inline bool derived_current(const vh_table* t, const VhLayout& L) { return L.cap_seg >= t->cap_seg && L.applied_epoch == t->sync_epoch; }
+// Bring a layout up to date with the arenas: re-derive what changed since it was last current in ONE launch on the library's stream, no
+// host wait (but the overflow word's). launch(d_jobs, njobs) enqueues the layout's kernel.
+template <class Launch> static int derived_refresh(vh_table* t, VhLayout* L, const VhRefresh& R, Launch&& launch) {
   if (!t->nseg) return VH_OK;
-  if (pk->cap_seg < t->cap_seg) {                      // the table grew: move the arena
-    table_quiesce(t);
-    HIP_TRY(hipStreamSynchronize(g_ctx.stream)); derived_waited(t);
-    char* nb = nullptr;
-    const size_t bytes = (size_t)t->cap_seg * pk->stride + 256;
-    HIP_TRY(hipMalloc(&nb, bytes));
-    trace_alloc("projection", nb, bytes);
-    if (pk->base) {
-      HIP_TRY(hipMemcpyAsync(nb, pk->base, (size_t)pk->cap_seg * pk->stride, hipMemcpyDeviceToDevice, g_ctx.stream));
-      HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-      HIP_TRY(hipFree(pk->base));
-      t->device_bytes -= (size_t)pk->cap_seg * pk->stride + 256;
+  if (L->cap_seg < t->cap_seg) {                        // the table grew
+    if (int rc = derived_idle(t)) return rc;
+    if (R.restart) for (int i = 0; i < R.nbufs; ++i) buf_free(t, R.bufs[i]);
+    for (int i = 0; i < R.nbufs; ++i) {
+      VhBuf old = *R.bufs[i], *b = R.bufs[i];
+      if (R.restart) {
+        if (b->stride && buf_alloc(t, b, t->cap_seg, R.what[i], true) != VH_OK && i < R.required) return VH_NO_ROOM;
+        continue;
+      }
+      if (int rc = buf_alloc(t, b, t->cap_seg, R.what[i])) { *b = old; return rc; }
+      if (old.ptr) {
+        HIP_TRY(hipMemcpyAsync(b->ptr, old.ptr, (size_t)L->cap_seg * old.stride, hipMemcpyDeviceToDevice, g_ctx.stream));
+        HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+        buf_free(t, &old);
+      }
     }
-    pk->base = nb; pk->cap_seg = t->cap_seg;
-    pk->seg_mod.resize(t->cap_seg, 0);
-    t->device_bytes += bytes;
+    L->cap_seg = t->cap_seg;
+    if (R.restart) { L->seg_mod.assign(t->cap_seg, 0); L->applied_epoch = 0; }
+    else L->seg_mod.resize(t->cap_seg, 0);
   }
-  if (pk->applied_epoch == t->sync_epoch) return VH_OK;
+  if (L->applied_epoch == t->sync_epoch) return VH_OK;
   std::vector<VhJob> jobs;
-  derived_jobs(t, pk->applied_epoch, pk->seg_mod, (t->segment_rows + 255) / 256 * 256, &jobs);
+  derived_jobs(t, *L, R.row_limit, R.whole_tiles, &jobs);
   if (!jobs.empty()) {
     const VhJob* d_jobs = nullptr;
-    if (int rc = derived_upload(t, jobs, &d_jobs)) return rc;
-    if (!t->d_packflag) { HIP_TRY(hipMalloc((void**)&t->d_packflag, 256)); HIP_TRY(hipMemsetAsync(t->d_packflag, 0, 256, g_ctx.stream)); }
-    pack_launch(t, pk, d_jobs, jobs.size(), t->d_packflag, g_ctx.stream);
+    if (int rc = derived_upload(&t->jobs, &t->derived_pending, jobs, &d_jobs)) return rc;
+    if (int rc = launch(d_jobs, jobs.size())) return rc;
     HIP_TRY(hipGetLastError());
-    if (pk->compressed) {                               // did every value survive its stored width? (the one host wait of a refresh)
+    if (R.overflow_wait) {                              // did every value survive its stored width? (the one host wait of a refresh)
       unsigned int ovf = 0;
       HIP_TRY(hipMemcpyAsync(&ovf, t->d_packflag, sizeof(ovf), hipMemcpyDeviceToHost, g_ctx.stream));
       HIP_TRY(hipStreamSynchronize(g_ctx.stream));
@@ -253,32 +193,37 @@ static int pack_refresh_records(vh_table* t, VhPack* pk) {
       }
     } else if (int rc = derived_enqueued(t)) return rc;
   }
-  for (uint32_t s = 0; s < t->nseg; ++s) pk->seg_mod[s] = t->seg_mod[s];
-  pk->applied_epoch = t->sync_epoch;
+  for (uint32_t s = 0; s < t->nseg; ++s) L->seg_mod[s] = t->seg_mod[s];
+  L->applied_epoch = t->sync_epoch;
   return VH_OK;
 }
-static void pack_drop(vh_table* t, VhPack* pk) {
-  table_quiesce(t);
-  (void)hipStreamSynchronize(g_ctx.stream);
-  for (size_t k = 0; k < t->packs.size(); ++k) {
-    if (t->packs[k].get() != pk) continue;
-    if (pk->base) { (void)hipFree(pk->base); t->device_bytes -= (size_t)pk->cap_seg * pk->stride + 256; }
-    grouped_drop(t, pk);
-    t->packs.erase(t->packs.begin() + (long)k);
+// ------------------------------------------------------- the drop path
+// `x` leaves `list`: nobody reads or writes its arenas any more, free_arenas() gives them back through the ledger, the layout is erased.
+template <class T, class Free> static void derived_drop(vh_table* t, std::vector<std::unique_ptr<T>>* list, T* x, Free&& free_arenas) {
+  (void)derived_idle(t);
+  for (size_t k = 0; k < list->size(); ++k) {
+    if ((*list)[k].get() != x) continue;
+    free_arenas();
+    list->erase(list->begin() + (long)k);
     return;
   }
 }
 
-// Bytes the values of an integer column need over every mirrored segment (1, 2, 4 or 8; the element size for floating point): dimensions
-// from their SegmentStats, metrics from a min / max pass of their own (they keep no stats).
+// ------------------------------------------------------- value ranges of the columns (the recorded stats; arithmetic: vhh_layout_math.h)
+// The range of a column's values over every mirrored segment; false: no stats for it.
+static bool column_range(const vh_table* t, int col, VhRange* r) {
+  if ((size_t)col >= t->stats.size() || t->stats[col].size() < t->nseg) return false;
+  *r = vh_range_over(t->stats[col].data(), t->nseg);
+  return true;
+}
+// Bytes the values of an integer column need over every mirrored segment (1, 2, 4 or 8; the element size for floating point): from the
+// recorded stats, or from a min / max pass of its own where there are none.
 static int column_stored_width(vh_table* t, int col, int* width_out) {
   const VhColumn& c = t->cols[col];
   *width_out = (int)c.esize;
-  if (c.elem == VH_F32 || c.elem == VH_F64 || c.esize == 1 || !t->nseg) return VH_OK;
-  uint64_t lo = ~0ull, hi = 0;
-  if ((size_t)col < t->stats.size() && t->stats[col].size() >= t->nseg) {      // (refresh_stats keeps min / max of every fixed-width column, metrics included)
-    for (uint32_t s = 0; s < t->nseg; ++s) { const VhSegStat& st = t->stats[col][s]; if (st.lo > st.hi) continue; lo = std::min(lo, st.lo); hi = std::max(hi, st.hi); }
-  } else {
+  if (vh_elem_float(c.elem) || c.esize == 1 || !t->nseg) return VH_OK;
+  VhRange r;
+  if (!column_range(t, col, &r)) {      // (refresh_stats keeps min / max of every fixed-width column, metrics included)
     const uint32_t n = t->nseg;
     char* tmp = nullptr;
     HIP_TRY(hipMalloc(&tmp, (size_t)n * 16 + (size_t)n * 4 + 256));
@@ -302,18 +247,113 @@ static int column_stored_width(vh_table* t, int col, int* width_out) {
     if (he == hipSuccess) he = hipStreamSynchronize(g_ctx.stream);
     (void)hipFree(tmp);
     if (he != hipSuccess) return vh_fail(VH_E_DEVICE, "min / max pass over column %d: %s", col, hipGetErrorString(he));
-    for (uint32_t s = 0; s < n; ++s) { if (init[2 * s] > init[2 * s + 1]) continue; lo = std::min<uint64_t>(lo, init[2 * s]); hi = std::max<uint64_t>(hi, init[2 * s + 1]); }
+    for (uint32_t s = 0; s < n; ++s) if (init[2 * s] <= init[2 * s + 1]) r.add(init[2 * s], init[2 * s + 1]);
   }
-  if (lo > hi) { *width_out = 1; return VH_OK; }       // no rows yet: anything fits (a later value that does not voids the projection)
-  int w = (int)c.esize;
-  if (c.elem == VH_I16 || c.elem == VH_I32 || c.elem == VH_I64) {
-    const int64_t a = (int64_t)(lo ^ (1ull << 63)), b = (int64_t)(hi ^ (1ull << 63));       // (order key of a signed integer: the value with its sign bit flipped)
-    w = (a >= INT8_MIN && b <= INT8_MAX) ? 1 : (a >= INT16_MIN && b <= INT16_MAX) ? 2 : (a >= INT32_MIN && b <= INT32_MAX) ? 4 : 8;
-  } else {
-    w = hi < 256 ? 1 : hi < 65536 ? 2 : hi <= 0xFFFFFFFFull ? 4 : 8;
-  }
-  *width_out = std::min(w, (int)c.esize);
+  *width_out = vh_range_stored_bytes(c.elem, (int)c.esize, r);
   return VH_OK;
+}
+// Width of a narrow copy of the column: 1, 2, or 0 (not an unsigned 32-bit column, no rows, or its values need more than 16 bits).
+static int narrow_width_for(const vh_table* t, int col) {
+  VhRange r;
+  return column_range(t, col, &r) ? vh_range_narrow_width(t->cols[col].elem, r) : 0;
+}
+// Bits the values of a column need in a predicate projection (0: not an integer column, negative values, no rows, or no stats).
+static int predpack_bits_for(const vh_table* t, int col) {
+  VhRange r;
+  return column_range(t, col, &r) ? vh_range_bits(t->cols[col].elem, r) : 0;
+}
+
+// ------------------------------------------------------- the grouped form of a bit-record projection (VhGrouped): built and refreshed with its projection, tile by tile
+static void grouped_drop(vh_table* t, VhPack* pk) {      // (the caller made the table idle: derived_idle)
+  VhGrouped* gr = pk->grouped.get();
+  if (!gr) return;
+  buf_free(t, &gr->rec); buf_free(t, &gr->hdr); buf_free(t, &gr->planes);
+  pk->grouped.reset();
+}
+static void grouped_no_planes(vh_table* t, VhGrouped* gr) {      // the grouped records alone answer from now on
+  buf_free(t, &gr->planes);
+  gr->planes.stride = 0; gr->G = 0; gr->pp_serial = 0;
+}
+// The clustered planes' fields: those of bit-sliced predicate projection `pp` without the grouping column's. false: `pp` has nothing to cluster
+// (it lacks the grouping column, or holds no other).
+static bool grouped_planes_describe(const vh_table* t, VhGrouped* gr, const VhPredPack* pp) {
+  if (!pp || !pp->sliced) return false;
+  const size_t at = (size_t)(std::find(pp->cols.begin(), pp->cols.end(), gr->col) - pp->cols.begin());
+  if (at >= pp->cols.size() || pp->bitw[at] != gr->bits || pp->bits <= gr->bits || pp->bits > 32) return false;
+  gr->G = vh_gplanes_group(pp->bits - gr->bits); gr->goff = pp->bitoff[at];
+  gr->planes.stride = vh_gplanes_seg_bytes(t->segment_rows, gr->G);
+  gr->pp_serial = pp->serial; gr->pp_cols = pp->cols; gr->pp_bitoff = pp->bitoff; gr->pp_bitw = pp->bitw;
+  return true;
+}
+// Re-derive the tiles that hold a row journalled since the grouped form was last current: whole tiles (one changed row moves the places of
+// its tile's rows behind it), one block per tile. When the table grew it starts over in new arenas; no room for records and headers: the
+// form is dropped and the ungrouped records answer; no room for the planes: the grouped records alone.
+static int grouped_refresh(vh_table* t, VhPack* pk) {
+  VhGrouped* gr = pk->grouped.get();
+  if (!gr || derived_current(t, *gr)) return VH_OK;
+  VhRefresh R;
+  R.bufs[0] = &gr->rec; R.bufs[1] = &gr->hdr; R.bufs[2] = &gr->planes; R.nbufs = 3; R.required = 2;
+  R.what[0] = VL_NAME[VL_GROUPED]; R.what[1] = VL_NAME[VL_GHDR]; R.what[2] = VL_NAME[VL_GPLANES];
+  R.row_limit = rows_padded_256(t); R.whole_tiles = true; R.restart = true;
+  const int rc = derived_refresh(t, gr, R, [&](const VhJob* d_jobs, size_t njobs) {
+    if (int frc = packflag_ready(t)) return frc;
+    grouped_launch(t, pk, d_jobs, njobs, t->d_packflag, g_ctx.stream);
+    return (int)VH_OK;
+  });
+  if (rc == VH_NO_ROOM) { grouped_drop(t, pk); return VH_OK; }
+  if (gr->G && !gr->planes.ptr) grouped_no_planes(t, gr);      // (there was no room for the planes)
+  return rc;
+}
+// The grouped form of `pk` by column `col`, whose field in the bit-sliced planes has `bits` bits: built (or built again for another column or
+// width) and brought up to date. Bit-field records of 4 bytes only; nullptr and VH_OK where there is no room for it.
+// `pp`: the bit-sliced predicate projection whose other columns' bits are kept clustered beside the records (nullptr: records alone — no such
+// projection, or no room). A form whose planes belong to another projection than `pp` starts over: records, headers and planes are one launch.
+static int grouped_build(vh_table* t, VhPack* pk, int col, uint32_t bits, const VhPredPack* pp = nullptr) {
+  if (!pk->bits || pk->rec_bytes != 4 || bits == 0 || bits > VH_GROUP_MAX_BITS || col < 0 || (size_t)col >= t->cols.size()) return VH_OK;
+  if (pk->grouped && (pk->grouped->col != col || pk->grouped->bits != bits || (pp && (!pk->grouped->planes.ptr || pk->grouped->pp_serial != pp->serial)))) {
+    if (int rc = derived_idle(t)) return rc;
+    grouped_drop(t, pk);
+  }
+  if (!pk->grouped) {
+    VhGrouped* gr = new VhGrouped();
+    pk->grouped.reset(gr);
+    gr->col = col; gr->bits = bits; gr->serial = pk->serial; gr->automatic = pk->automatic;
+    const uint64_t tiles = (t->segment_rows + VH_GROUP_TILE - 1) / VH_GROUP_TILE;
+    gr->rec.stride = pk->rec.stride;
+    gr->hdr.stride = (tiles * vh_grouped_hdr_bytes(bits) + 63) / 64 * 64;
+    (void)grouped_planes_describe(t, gr, pp);
+  }
+  return grouped_refresh(t, pk);
+}
+
+// ------------------------------------------------------- payload projections (vh_table_pack)
+static int pack_refresh_records(vh_table* t, VhPack* pk) {
+  if (derived_current(t, *pk)) return VH_OK;
+  VhRefresh R;
+  R.bufs[0] = &pk->rec; R.what[0] = VL_NAME[VL_PACK]; R.nbufs = 1;
+  R.row_limit = rows_padded_256(t); R.overflow_wait = pk->compressed;
+  return derived_refresh(t, pk, R, [&](const VhJob* d_jobs, size_t njobs) {
+    if (int frc = packflag_ready(t)) return frc;
+    pack_launch(t, pk, d_jobs, njobs, t->d_packflag, g_ctx.stream);
+    return (int)VH_OK;
+  });
+}
+// Bring the projection up to date with the arenas; its grouped form follows in the same call: a plan finds both, and the planes, at one epoch.
+static int pack_refresh(vh_table* t, VhPack* pk) {
+  if (int rc = pack_refresh_records(t, pk)) return rc;
+  return grouped_refresh(t, pk);
+}
+static void pack_drop(vh_table* t, VhPack* pk) {
+  derived_drop(t, &t->packs, pk, [&] { buf_free(t, &pk->rec); grouped_drop(t, pk); });
+}
+// The projection of exactly these columns (ascending) in this form, or nullptr.
+static VhPack* pack_find(const vh_table* t, const std::vector<int>& sorted_cols, bool compressed) {
+  for (auto& pk : t->packs) {
+    std::vector<int> have = pk->cols;
+    std::sort(have.begin(), have.end());
+    if (have == sorted_cols && pk->compressed == compressed) return pk.get();
+  }
+  return nullptr;
 }
 
 // The record layout of a projection of `order` (distinct columns): widths (compressed: what the recorded values need), offsets, bit fields.
@@ -339,15 +379,11 @@ static int pack_describe(vh_table* t, const std::vector<int>& order, bool automa
   uint32_t used = 0;
   for (int c : ord) {
     if (!bits) break;
-    const VhColumn& col = t->cols[c];
-    if (col.elem == VH_F32 || col.elem == VH_F64 || (size_t)c >= t->stats.size() || t->stats[c].size() < t->nseg) { bits = false; break; }
-    uint64_t lo = ~0ull, hi = 0;
-    for (uint32_t sg = 0; sg < t->nseg; ++sg) { const VhSegStat& st = t->stats[c][sg]; if (st.lo > st.hi) continue; lo = std::min(lo, st.lo); hi = std::max(hi, st.hi); }
-    if (lo > hi) lo = hi = order_key_of_bits(col.elem, 0);
-    const bool sgn = col.elem == VH_I8 || col.elem == VH_I16 || col.elem == VH_I32 || col.elem == VH_I64;
-    if (sgn && (int64_t)(lo ^ (1ull << 63)) < 0) { bits = false; break; }
-    const uint64_t vmax = sgn ? (hi ^ (1ull << 63)) : bits_of_order_key(col.elem, hi);
-    int b = 1; while (b < 64 && (vmax >> b)) ++b;
+    VhRange r;
+    if (!column_range(t, c, &r)) { bits = false; break; }
+    if (r.empty()) r = vh_range_of_zero(t->cols[c].elem);      // no rows yet: as if they held 0 (a later value that needs more voids the projection)
+    const int b = vh_range_bits(t->cols[c].elem, r);
+    if (!b) { bits = false; break; }
     bitoff.push_back((uint8_t)used); bitw.push_back((uint8_t)b); used += (uint32_t)b;
     if (used > 64) { bits = false; break; }
   }
@@ -357,7 +393,7 @@ static int pack_describe(vh_table* t, const std::vector<int>& order, bool automa
   pk.reset(new VhPack());
   pk->cols = ord; pk->off = off; pk->width = width; pk->rec_bytes = rec; pk->automatic = automatic; pk->compressed = compress;
   if (bits) { pk->bits = true; pk->bitoff = bitoff; pk->bitw = bitw; pk->rec_bytes = rec = rec_bits; for (auto& o : pk->off) o = 0; }
-  pk->stride = (t->segment_rows + 255) / 256 * 256 * (uint64_t)rec;
+  pk->rec.stride = rows_padded_256(t) * (uint64_t)rec;
   return VH_OK;
 }
 
@@ -371,14 +407,10 @@ static int table_pack_locked(vh_table* t, const int32_t* cols, int32_t ncols, bo
   }
   std::vector<int> sorted_cols = order;
   std::sort(sorted_cols.begin(), sorted_cols.end());
-  for (auto& pk : t->packs) {
-    std::vector<int> have = pk->cols;
-    std::sort(have.begin(), have.end());
-    if (have != sorted_cols || pk->compressed != compress) continue;
-    const int rc = pack_refresh(t, pk.get(), 0, t->nseg);
-    if (rc == VH_PACK_STALE) { pack_drop(t, pk.get()); break; }      // built again below, at the widths the values need now
-    if (out) *out = pk.get();
-    return rc;
+  if (VhPack* pk = pack_find(t, sorted_cols, compress)) {
+    const int rc = pack_refresh(t, pk);
+    if (rc != VH_PACK_STALE) { if (out) *out = pk; return rc; }
+    pack_drop(t, pk);      // built again below, at the widths the values need now
   }
   for (int attempt = 0; attempt < 2; ++attempt) {
     std::unique_ptr<VhPack> pk;
@@ -386,7 +418,7 @@ static int table_pack_locked(vh_table* t, const int32_t* cols, int32_t ncols, bo
     pk->serial = ++t->layout_serial;
     VhPack* raw = pk.get();
     t->packs.push_back(std::move(pk));
-    const int rc = pack_refresh(t, raw, 0, t->nseg);
+    const int rc = pack_refresh(t, raw);
     if (rc == VH_PACK_STALE && attempt == 0) { pack_drop(t, raw); continue; }      // (a metric changed between the min / max pass and the copy)
     if (rc) { pack_drop(t, raw); return rc == VH_PACK_STALE ? vh_fail(VH_E_DEVICE, "vh_table_pack: values keep outgrowing their stored widths") : rc; }
     if (out) *out = raw;
@@ -396,184 +428,80 @@ static int table_pack_locked(vh_table* t, const int32_t* cols, int32_t ncols, bo
 }
 
 // ------------------------------------------------------- narrow predicate copies (vh_table_narrow)
-// Width the column's values fit over segments [0, nseg): 1, 2, or 0 (not an unsigned 32-bit column, or its values need all 32 bits).
-static int narrow_width_for(const vh_table* t, int col, uint32_t nseg) {
-  const VhColumn& c = t->cols[col];
-  if (c.elem != VH_U32 || (size_t)col >= t->stats.size()) return 0;
-  uint64_t hi = 0;
-  bool any = false;
-  for (uint32_t s = 0; s < nseg && s < t->stats[col].size(); ++s) {
-    const VhSegStat& st = t->stats[col][s];
-    if (st.lo > st.hi) continue;          // empty segment
-    hi = std::max(hi, st.hi); any = true;
-  }
-  if (!any) return 0;
-  return hi < 256 ? 1 : hi < 65536 ? 2 : 0;
-}
-static void narrow_launch(const vh_table* t, const VhNarrow* nw, const VhJob* d_jobs, size_t njobs, hipStream_t st) {
-  const VhColumn& c = t->cols[nw->col];
-  if (nw->width == 1)
-    hipLaunchKernelGGL((narrow_kernel<uint8_t>), dim3((unsigned)njobs), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(c.base), c.stride / 4,
-                       reinterpret_cast<uint8_t*>(nw->base), nw->stride, d_jobs);
-  else
-    hipLaunchKernelGGL((narrow_kernel<uint16_t>), dim3((unsigned)njobs), dim3(256), 0, st, reinterpret_cast<const uint32_t*>(c.base), c.stride / 4,
-                       reinterpret_cast<uint16_t*>(nw->base), nw->stride / 2, d_jobs);
-}
-// Bring the narrow copy up to date with its column: the ranges that changed since it was last copied, ONE launch, no host wait.
-static int narrow_refresh(vh_table* t, VhNarrow* nw, uint32_t first, uint32_t n) {
-  (void)first; (void)n;
-  if (!t->nseg) return VH_OK;
-  if (nw->cap_seg < t->cap_seg) {
-    table_quiesce(t);
-    HIP_TRY(hipStreamSynchronize(g_ctx.stream)); derived_waited(t);
-    char* nb = nullptr;
-    const size_t bytes = (size_t)t->cap_seg * nw->stride + 256;
-    HIP_TRY(hipMalloc(&nb, bytes));
-    trace_alloc("narrow", nb, bytes);
-    if (nw->base) {
-      HIP_TRY(hipMemcpyAsync(nb, nw->base, (size_t)nw->cap_seg * nw->stride, hipMemcpyDeviceToDevice, g_ctx.stream));
-      HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-      HIP_TRY(hipFree(nw->base));
-      t->device_bytes -= (size_t)nw->cap_seg * nw->stride + 256;
-    }
-    nw->base = nb; nw->cap_seg = t->cap_seg;
-    nw->seg_mod.resize(t->cap_seg, 0);
-    t->device_bytes += bytes;
-  }
-  if (nw->applied_epoch == t->sync_epoch) return VH_OK;
-  std::vector<VhJob> jobs;
-  derived_jobs(t, nw->applied_epoch, nw->seg_mod, t->padded_rows, &jobs);
-  if (!jobs.empty()) {
-    const VhJob* d_jobs = nullptr;
-    if (int rc = derived_upload(t, jobs, &d_jobs)) return rc;
-    narrow_launch(t, nw, d_jobs, jobs.size(), g_ctx.stream);
-    HIP_TRY(hipGetLastError());
-    if (int rc = derived_enqueued(t)) return rc;
-  }
-  for (uint32_t s = 0; s < t->nseg; ++s) nw->seg_mod[s] = t->seg_mod[s];
-  nw->applied_epoch = t->sync_epoch;
-  return VH_OK;
-}
-static void narrow_drop(vh_table* t, size_t k) {
-  table_quiesce(t);
-  VhNarrow* nw = t->narrows[k].get();
-  if (nw->base) { (void)hipFree(nw->base); t->device_bytes -= (size_t)nw->cap_seg * nw->stride + 256; }
-  t->narrows.erase(t->narrows.begin() + (long)k);
-}
-// The narrow copy of `col`, fresh for segments [0, nseg), or nullptr (none, or the values no longer fit: the copy is dropped).
-static VhNarrow* narrow_usable(vh_table* t, int col, uint32_t nseg) {
-  for (size_t k = 0; k < t->narrows.size(); ++k) {
-    VhNarrow* nw = t->narrows[k].get();
-    if (nw->col != col) continue;
-    const int w = narrow_width_for(t, col, t->nseg);
-    if (w == 0 || w > nw->width) { narrow_drop(t, k); return nullptr; }
-    if (narrow_refresh(t, nw, 0, nseg) != VH_OK) return nullptr;
-    return nw;
-  }
+static VhNarrow* narrow_find(const vh_table* t, int col) {
+  for (auto& nw : t->narrows) if (nw->col == col) return nw.get();
   return nullptr;
+}
+// The narrow copy `col` would get; *out stays empty when there is nothing to gain (narrow_width_for).
+static void narrow_describe(const vh_table* t, int col, bool automatic, std::unique_ptr<VhNarrow>* out) {
+  out->reset();
+  const int w = narrow_width_for(t, col);
+  if (!w) return;
+  out->reset(new VhNarrow());
+  (*out)->col = col; (*out)->width = w; (*out)->automatic = automatic;
+  (*out)->copy.stride = t->padded_rows * (uint64_t)w;
+}
+static int narrow_refresh(vh_table* t, VhNarrow* nw) {
+  if (derived_current(t, *nw)) return VH_OK;
+  VhRefresh R;
+  R.bufs[0] = &nw->copy; R.what[0] = VL_NAME[VL_NARROW]; R.nbufs = 1; R.row_limit = t->padded_rows;
+  return derived_refresh(t, nw, R, [&](const VhJob* d_jobs, size_t njobs) { narrow_launch(t, nw, d_jobs, njobs, g_ctx.stream); return (int)VH_OK; });
+}
+static void narrow_drop(vh_table* t, VhNarrow* nw) {
+  derived_drop(t, &t->narrows, nw, [&] { buf_free(t, &nw->copy); });
+}
+// The narrow copy of `col`, fresh, or nullptr (none, or the values no longer fit: the copy is dropped).
+static VhNarrow* narrow_usable(vh_table* t, int col) {
+  VhNarrow* nw = narrow_find(t, col);
+  if (!nw) return nullptr;
+  const int w = narrow_width_for(t, col);
+  if (w == 0 || w > nw->width) { narrow_drop(t, nw); return nullptr; }
+  return narrow_refresh(t, nw) == VH_OK ? nw : nullptr;
 }
 static int table_narrow_locked(vh_table* t, int col, bool automatic) {
   if (col < 0 || (size_t)col >= t->cols.size()) return vh_fail(VH_E_INVALID, "vh_table_narrow: column %d", col);
-  for (auto& nw : t->narrows) if (nw->col == col) return narrow_usable(t, col, t->nseg) ? VH_OK : VH_OK;
-  const int w = narrow_width_for(t, col, t->nseg);
-  if (!w) return VH_OK;                          // nothing to gain: not an unsigned 32-bit column, or it uses its bits
-  std::unique_ptr<VhNarrow> nw(new VhNarrow());
-  nw->col = col; nw->width = w; nw->automatic = automatic;
-  nw->stride = t->padded_rows * (uint64_t)w;
+  if (narrow_find(t, col)) { (void)narrow_usable(t, col); return VH_OK; }
+  std::unique_ptr<VhNarrow> nw;
+  narrow_describe(t, col, automatic, &nw);
+  if (!nw) return VH_OK;                         // nothing to gain: not an unsigned 32-bit column, or it uses its bits
+  nw->serial = ++t->layout_serial;
   VhNarrow* raw = nw.get();
   t->narrows.push_back(std::move(nw));
-  const int rc = narrow_refresh(t, raw, 0, t->nseg);
-  if (rc) { narrow_drop(t, t->narrows.size() - 1); return rc; }
-  return VH_OK;
+  const int rc = narrow_refresh(t, raw);
+  if (rc) narrow_drop(t, raw);
+  return rc;
 }
 
 // ------------------------------------------------------- bit-packed predicate projections (vh_table_predpack)
-// Bits the values of a column need over every mirrored segment, from its recorded min / max (0: not an integer column, negative values, or no stats).
-static int predpack_bits_for(const vh_table* t, int col) {
-  const VhColumn& c = t->cols[col];
-  if (c.elem == VH_F32 || c.elem == VH_F64 || is_bitset_elem(c.elem) || (size_t)col >= t->stats.size() || t->stats[col].size() < t->nseg) return 0;
-  uint64_t lo = ~0ull, hi = 0;
-  for (uint32_t s = 0; s < t->nseg; ++s) { const VhSegStat& st = t->stats[col][s]; if (st.lo > st.hi) continue; lo = std::min(lo, st.lo); hi = std::max(hi, st.hi); }
-  if (lo > hi) return 0;
-  const bool sgn = c.elem == VH_I8 || c.elem == VH_I16 || c.elem == VH_I32 || c.elem == VH_I64;
-  if (sgn && (int64_t)(lo ^ (1ull << 63)) < 0) return 0;
-  const uint64_t vmax = sgn ? (hi ^ (1ull << 63)) : hi;
-  int b = 1;
-  while (b < 64 && (vmax >> b)) ++b;
-  return b;
-}
-static void predpack_drop(vh_table* t, size_t k) {
-  table_quiesce(t);
-  (void)hipStreamSynchronize(g_ctx.stream); derived_waited(t);
-  VhPredPack* pp = t->predpacks[k].get();
-  for (int q = 0; q < pp->nplanes; ++q) if (pp->pbase[q]) { (void)hipFree(pp->pbase[q]); t->device_bytes -= (size_t)pp->cap_seg * pp->pstride[q] + 256; }
-  for (auto& pk : t->packs) {       // clustered planes derived from it go with it (the grouped records stay)
-    VhGrouped* gr = pk->grouped.get();
-    if (!gr || gr->pp_serial != pp->serial) continue;
-    if (gr->planes) { (void)hipFree(gr->planes); t->device_bytes -= gr->planes_bytes(); gr->planes = nullptr; }
-    gr->G = 0; gr->pp_serial = 0;
-  }
-  t->predpacks.erase(t->predpacks.begin() + (long)k);
-}
-static void predpack_launch(const vh_table* t, const VhPredPack* pp, const VhJob* d_jobs, size_t njobs, hipStream_t st) {
-  VhPredPackArgs A{};
-  A.ncols = (int32_t)pp->cols.size(); A.nplanes = pp->nplanes;
-  for (size_t c = 0; c < pp->cols.size(); ++c) {
-    const VhColumn& col = t->cols[pp->cols[c]];
-    A.src[c] = col.base; A.src_stride[c] = col.stride; A.esize[c] = (uint32_t)col.esize; A.bitoff[c] = pp->bitoff[c];
-  }
-  for (int q = 0; q < pp->nplanes; ++q) { A.plane[q] = pp->pbase[q]; A.plane_stride[q] = pp->pstride[q]; A.plane_width[q] = (uint32_t)pp->pwidth[q]; A.plane_pos[q] = (uint32_t)pp->ppos[q]; }
-  A.jobs = d_jobs;
-  if (pp->sliced) hipLaunchKernelGGL(predslice_kernel, dim3((unsigned)njobs), dim3(256), 0, st, A, pp->bits, pp->pitch);
-  else hipLaunchKernelGGL(predpack_kernel, dim3((unsigned)njobs), dim3(256), 0, st, A);
+static void predpack_drop(vh_table* t, VhPredPack* pp) {
+  derived_drop(t, &t->predpacks, pp, [&] {
+    for (int q = 0; q < pp->nplanes; ++q) buf_free(t, &pp->plane[q]);
+    for (auto& pk : t->packs)        // clustered planes derived from it go with it (the grouped records stay)
+      if (pk->grouped && pk->grouped->pp_serial == pp->serial) grouped_no_planes(t, pk->grouped.get());
+  });
 }
 static int predpack_refresh(vh_table* t, VhPredPack* pp) {
-  if (!t->nseg) return VH_OK;
-  if (pp->cap_seg < t->cap_seg) {
-    table_quiesce(t);
-    HIP_TRY(hipStreamSynchronize(g_ctx.stream)); derived_waited(t);
-    for (int q = 0; q < pp->nplanes; ++q) {
-      char* nb = nullptr;
-      const size_t bytes = (size_t)t->cap_seg * pp->pstride[q] + 256;
-      HIP_TRY(hipMalloc(&nb, bytes));
-      trace_alloc("predicate plane", nb, bytes);
-      if (pp->pbase[q]) {
-        HIP_TRY(hipMemcpyAsync(nb, pp->pbase[q], (size_t)pp->cap_seg * pp->pstride[q], hipMemcpyDeviceToDevice, g_ctx.stream));
-        HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-        HIP_TRY(hipFree(pp->pbase[q]));
-        t->device_bytes -= (size_t)pp->cap_seg * pp->pstride[q] + 256;
-      }
-      pp->pbase[q] = nb;
-      t->device_bytes += bytes;
-    }
-    pp->cap_seg = t->cap_seg;
-    pp->seg_mod.resize(t->cap_seg, 0);
-  }
-  if (pp->applied_epoch == t->sync_epoch) return VH_OK;
-  std::vector<VhJob> jobs;
-  derived_jobs(t, pp->applied_epoch, pp->seg_mod, t->padded_rows, &jobs);
-  if (!jobs.empty()) {
-    const VhJob* d_jobs = nullptr;
-    if (int rc = derived_upload(t, jobs, &d_jobs)) return rc;
-    predpack_launch(t, pp, d_jobs, jobs.size(), g_ctx.stream);
-    HIP_TRY(hipGetLastError());
-    if (int rc = derived_enqueued(t)) return rc;
-  }
-  for (uint32_t s = 0; s < t->nseg; ++s) pp->seg_mod[s] = t->seg_mod[s];
-  pp->applied_epoch = t->sync_epoch;
-  return VH_OK;
+  if (derived_current(t, *pp)) return VH_OK;
+  VhRefresh R;
+  for (int q = 0; q < pp->nplanes; ++q) { R.bufs[q] = &pp->plane[q]; R.what[q] = VL_NAME[VL_PLANE]; }
+  R.nbufs = pp->nplanes; R.row_limit = t->padded_rows;
+  return derived_refresh(t, pp, R, [&](const VhJob* d_jobs, size_t njobs) { predpack_launch(t, pp, d_jobs, njobs, g_ctx.stream); return (int)VH_OK; });
+}
+// The projection of exactly `cols` (ascending) in this form, or nullptr.
+static VhPredPack* predpack_find(const vh_table* t, const std::vector<int>& cols, bool sliced) {
+  for (auto& pp : t->predpacks) if (pp->cols == cols && pp->sliced == sliced) return pp.get();
+  return nullptr;
 }
 // The projection that holds every column of `cols` (ascending), fresh, or nullptr. One whose fields no longer hold the recorded values is dropped.
 static VhPredPack* predpack_usable(vh_table* t, const std::vector<int>& cols, int want_sliced = -1) {
-  for (size_t k = 0; k < t->predpacks.size(); ++k) {
-    VhPredPack* pp = t->predpacks[k].get();
+  for (auto& q : t->predpacks) {
+    VhPredPack* pp = q.get();
     if (!std::includes(pp->cols.begin(), pp->cols.end(), cols.begin(), cols.end())) continue;
     if (want_sliced >= 0 && (int)pp->sliced != want_sliced) continue;
     bool fits = true;
     for (size_t c = 0; c < pp->cols.size(); ++c) { const int b = predpack_bits_for(t, pp->cols[c]); fits &= b > 0 && b <= (int)pp->bitw[c]; }
-    if (!fits) { predpack_drop(t, k); return nullptr; }
-    if (predpack_refresh(t, pp) != VH_OK) return nullptr;
-    return pp;
+    if (!fits) { predpack_drop(t, pp); return nullptr; }
+    return predpack_refresh(t, pp) == VH_OK ? pp : nullptr;
   }
   return nullptr;
 }
@@ -588,19 +516,19 @@ static int predpack_describe(vh_table* t, const std::vector<int>& cols, bool aut
     if (!b) return VH_OK;
     pp->cols.push_back(c); pp->bitoff.push_back((uint8_t)used); pp->bitw.push_back((uint8_t)b);
     used += (uint32_t)b;
-    const int nwid = narrow_width_for(t, c, t->nseg);
+    const int nwid = narrow_width_for(t, c);
     plain += nwid ? (uint32_t)nwid : (uint32_t)t->cols[c].esize;
   }
   if (used > 32) return VH_OK;
   if (sliced) {          // `used` planes of one bit per row; a plane's share of a segment padded to whole 256-byte blocks
     pp->sliced = true; pp->bits = used;
     pp->pitch = (t->padded_rows / 8 + 255) / 256 * 256;
-    pp->nplanes = 1; pp->pwidth[0] = 0; pp->ppos[0] = 0; pp->pstride[0] = pp->pitch * used;
+    pp->nplanes = 1; pp->pwidth[0] = 0; pp->ppos[0] = 0; pp->plane[0].stride = pp->pitch * used;
     if (used >= plain * 8u) return VH_OK;
   } else {
     for (uint32_t left = used, pos = 0; left > 0;) {
       const int w = left > 8 ? 2 : 1;
-      pp->pwidth[pp->nplanes] = w; pp->ppos[pp->nplanes] = (int)pos; pp->pstride[pp->nplanes] = t->padded_rows * (uint64_t)w;
+      pp->pwidth[pp->nplanes] = w; pp->ppos[pp->nplanes] = (int)pos; pp->plane[pp->nplanes].stride = t->padded_rows * (uint64_t)w;
       ++pp->nplanes;
       pos += 8u * w; left = left > 8u * w ? left - 8u * w : 0;
     }
@@ -615,7 +543,7 @@ static int predpack_describe(vh_table* t, const std::vector<int>& cols, bool aut
 static int table_predpack_locked(vh_table* t, const std::vector<int>& cols, bool automatic, VhPredPack** built, bool sliced) {
   if (built) *built = nullptr;
   if (cols.empty() || cols.size() > VH_PACK_MAX_COLS || cols.size() > VJ_MAX_PRED) return VH_OK;
-  for (auto& pp : t->predpacks) if (pp->cols == cols && pp->sliced == sliced) { if (built) *built = predpack_usable(t, cols, sliced ? 1 : 0); return VH_OK; }
+  if (predpack_find(t, cols, sliced)) { if (built) *built = predpack_usable(t, cols, sliced ? 1 : 0); return VH_OK; }
   std::unique_ptr<VhPredPack> pp;
   if (int drc = predpack_describe(t, cols, automatic, sliced, &pp)) return drc;
   if (!pp) return VH_OK;
@@ -623,7 +551,7 @@ static int table_predpack_locked(vh_table* t, const std::vector<int>& cols, bool
   VhPredPack* raw = pp.get();
   t->predpacks.push_back(std::move(pp));
   const int rc = predpack_refresh(t, raw);
-  if (rc) { predpack_drop(t, t->predpacks.size() - 1); return rc; }
+  if (rc) { predpack_drop(t, raw); return rc; }
   if (built) *built = raw;
   return VH_OK;
 }
@@ -669,38 +597,44 @@ extern "C" int vh_table_pack_ex(vh_table* t, const int32_t* cols, int32_t ncols,
 }
 extern "C" int vh_table_pack(vh_table* t, const int32_t* cols, int32_t ncols) { return vh_table_pack_ex(t, cols, ncols, VH_PACK_AUTO); }
 
+// Room for `need` more bytes under the rule every automatic layout is built by: a quarter of the device stays free. device_mem: the two
+// figures, for the sites that weigh something else against them (false: the device does not say).
+static bool device_mem(size_t* free_b, size_t* total_b) {
+  if (hipMemGetInfo(free_b, total_b) == hipSuccess) return true;
+  (void)hipGetLastError();
+  return false;
+}
+static bool device_room(size_t need) {
+  size_t free_b = 0, total_b = 0;
+  return device_mem(&free_b, &total_b) && free_b > need + total_b / 4;
+}
+
 // WHERE the derived layouts lie. The same records and planes read by the same kernel take 1.07 or 1.23 ms per 1 B rows depending on the physical
 // pages they were given (profiles/r06/NOTES.md, "Placement": six execution contexts with six scratch allocations agree within 0.5 %, the
 // projection alone moved twenty-three times changes nothing, projection AND planes re-built behind 3 GB spacers spread over 15 % — all at
 // 2 MB-aligned virtual addresses, so it is nothing a process can compute). What a process can do is try: derived_move copies every layout `which`
 // names (1: projections, 2: predicate planes) to FRESH allocations while the old ones are still held — so that the new ones are other pages —
 // and swaps the pointers (kernels take addresses as arguments); the caller measures and keeps or gives back (vh_table_prepare, vh_table_relocate).
-struct VhMoved {       // kind 1: a projection's records, 2: plane `plane` of a predicate projection, 3: a projection's grouped records (its headers stay: 32 bytes a tile), 4: the clustered planes beside them; `serial` and `applied_epoch` of the layout at the move
+struct VhMoved {       // an arena of derived_each's `kind` (the grouped headers stay: 32 bytes a tile), `plane` of its layout; `serial` and `applied_epoch` of the layout at the move
   int kind; uint64_t serial, applied_epoch; int plane; char* old_ptr; char* new_ptr; size_t bytes;
 };
-static size_t derived_bytes(const vh_table* t, uint32_t which) {
+static size_t derived_bytes(vh_table* t, uint32_t which) {
   size_t b = 0;
-  if (which & 1u) for (auto& pk : t->packs) { if (pk->base) b += (size_t)pk->cap_seg * pk->stride + 256; if (pk->grouped && pk->grouped->base) b += pk->grouped->bytes(pk->stride); if (pk->grouped && pk->grouped->planes) b += pk->grouped->planes_bytes(); }
-  if (which & 2u) for (auto& pp : t->predpacks) for (int q = 0; q < pp->nplanes; ++q) if (pp->pbase[q]) b += (size_t)pp->cap_seg * pp->pstride[q] + 256;
+  derived_each(t, which & 3u, [&](int, VhLayout&, int, VhBuf& buf) { b += buf.held; });
   return b;
 }
 static int derived_move(vh_table* t, uint32_t which, std::vector<VhMoved>* moved) {      // (t->mu held)
-  table_quiesce(t);
-  HIP_TRY(hipStreamSynchronize(g_ctx.stream)); derived_waited(t);
-  auto move = [&](int kind, uint64_t serial, uint64_t applied_epoch, int plane, char*& base, size_t bytes, const char* what) -> int {
-    char* nb = nullptr;
-    if (hipMalloc(&nb, bytes) != hipSuccess) { (void)hipGetLastError(); return VH_E_NOMEM; }
-    trace_alloc(what, nb, bytes);
-    if (hipMemcpyAsync(nb, base, bytes, hipMemcpyDeviceToDevice, g_ctx.stream) != hipSuccess) { (void)hipFree(nb); return vh_fail(VH_E_DEVICE, "moving a derived layout"); }
-    moved->push_back(VhMoved{kind, serial, applied_epoch, plane, base, nb, bytes});
-    base = nb;
-    return VH_OK;
-  };
+  if (int irc = derived_idle(t)) return irc;
   int rc = VH_OK;
-  if (which & 1u) for (auto& pk : t->packs) if (pk->base && !rc) rc = move(1, pk->serial, pk->applied_epoch, 0, pk->base, (size_t)pk->cap_seg * pk->stride + 256, "projection");
-  if (which & 1u) for (auto& pk : t->packs) if (pk->grouped && pk->grouped->base && !rc) rc = move(3, pk->serial, pk->grouped->applied_epoch, 0, pk->grouped->base, pk->grouped->bytes(pk->stride), "grouped projection");
-  if (which & 1u) for (auto& pk : t->packs) if (pk->grouped && pk->grouped->planes && !rc) rc = move(4, pk->serial, pk->grouped->applied_epoch, 0, pk->grouped->planes, pk->grouped->planes_bytes(), "clustered planes");
-  if (which & 2u) for (auto& pp : t->predpacks) for (int q = 0; q < pp->nplanes && !rc; ++q) if (pp->pbase[q]) rc = move(2, pp->serial, pp->applied_epoch, q, pp->pbase[q], (size_t)pp->cap_seg * pp->pstride[q] + 256, "predicate plane");
+  derived_each(t, which & 3u, [&](int kind, VhLayout& L, int plane, VhBuf& buf) {
+    if (rc) return;
+    char* nb = nullptr;
+    if (hipMalloc(&nb, buf.held) != hipSuccess) { (void)hipGetLastError(); rc = VH_E_NOMEM; return; }
+    trace_alloc(VL_NAME[kind], nb, buf.held);
+    if (hipMemcpyAsync(nb, buf.ptr, buf.held, hipMemcpyDeviceToDevice, g_ctx.stream) != hipSuccess) { (void)hipFree(nb); rc = vh_fail(VH_E_DEVICE, "moving a derived layout"); return; }
+    moved->push_back(VhMoved{kind, L.serial, L.applied_epoch, plane, buf.ptr, nb, buf.held});
+    buf.ptr = nb;
+  });
   HIP_TRY(hipStreamSynchronize(g_ctx.stream));
   return rc == VH_E_NOMEM ? VH_OK : rc;          // (out of memory: what could be moved was moved)
 }
@@ -715,15 +649,13 @@ static int derived_move(vh_table* t, uint32_t which, std::vector<VhMoved>* moved
 // Exactly one of the two buffers is ours to free: new_ptr where the layout goes back, old_ptr otherwise — where the layout was dropped, grew
 // or moved on, whoever replaced new_ptr owns it (and freed it, or will settle it).
 static void derived_settle(vh_table* t, std::vector<VhMoved>& moved, bool keep, std::vector<char*>* out) {      // (t->mu held)
-  table_quiesce(t);
-  (void)hipStreamSynchronize(g_ctx.stream);
+  (void)derived_idle(t);
   for (const VhMoved& m : moved) {
     char** slot = nullptr;
     uint64_t applied = 0;
-    if (m.kind == 1) { for (auto& pk : t->packs) if (pk->serial == m.serial && pk->base == m.new_ptr) { slot = &pk->base; applied = pk->applied_epoch; } }
-    else if (m.kind == 3) { for (auto& pk : t->packs) if (pk->serial == m.serial && pk->grouped && pk->grouped->base == m.new_ptr) { slot = &pk->grouped->base; applied = pk->grouped->applied_epoch; } }
-    else if (m.kind == 4) { for (auto& pk : t->packs) if (pk->serial == m.serial && pk->grouped && pk->grouped->planes == m.new_ptr) { slot = &pk->grouped->planes; applied = pk->grouped->applied_epoch; } }
-    else { for (auto& pp : t->predpacks) if (pp->serial == m.serial && pp->pbase[m.plane] == m.new_ptr) { slot = &pp->pbase[m.plane]; applied = pp->applied_epoch; } }
+    derived_each(t, 3u, [&](int kind, VhLayout& L, int plane, VhBuf& buf) {
+      if (kind == m.kind && L.serial == m.serial && plane == m.plane && buf.ptr == m.new_ptr) { slot = &buf.ptr; applied = L.applied_epoch; }
+    });
     if (slot && !keep && applied == m.applied_epoch) { *slot = m.old_ptr; out->push_back(m.new_ptr); }
     else out->push_back(m.old_ptr);
   }
@@ -750,17 +682,10 @@ extern "C" int vh_table_unpack(vh_table* t) {
   build_cancel_table(t, false);      // (before the lock: the running job needs it to finish; what it publishes meanwhile is dropped below)
   std::lock_guard<std::mutex> lk(t->mu);
   if (int src = sync_resolve(t)) return src;
-  table_quiesce(t);
-  HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-  for (auto& pk : t->packs) { if (pk->base) { (void)hipFree(pk->base); t->device_bytes -= (size_t)pk->cap_seg * pk->stride + 256; } grouped_drop(t, pk.get()); }
-  t->packs.clear();
-  t->gather_seen.clear();
-  for (auto& nw : t->narrows) if (nw->base) { (void)hipFree(nw->base); t->device_bytes -= (size_t)nw->cap_seg * nw->stride + 256; }
-  t->narrows.clear();
-  t->pred_seen.clear();
-  for (auto& pp : t->predpacks) for (int q = 0; q < pp->nplanes; ++q) if (pp->pbase[q]) { (void)hipFree(pp->pbase[q]); t->device_bytes -= (size_t)pp->cap_seg * pp->pstride[q] + 256; }
-  t->predpacks.clear();
-  t->ppred_seen.clear();
+  if (int rc = derived_idle(t)) return rc;
+  derived_each(t, VL_ALL, [&](int, VhLayout&, int, VhBuf& b) { buf_free(t, &b); });
+  t->packs.clear(); t->gather_seen.clear();
+  t->narrows.clear(); t->pred_seen.clear();
+  t->predpacks.clear(); t->ppred_seen.clear();
   return VH_OK;
 }
-

@@ -573,7 +573,7 @@ static int place_layouts(vh_table* t, const vh_plan* plan, vh_result_info* info_
         moved_epoch = t->sync_epoch;
         size_t free_b = 0, total_b = 0;
         const size_t spacer = (size_t)(1 + k % 3) << 30;
-        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || free_b < derived_bytes(t, which) + spacer + total_b / 4) break;
+        if (!device_mem(&free_b, &total_b) || free_b < derived_bytes(t, which) + spacer + total_b / 4) break;
         char* sp = nullptr;
         if (hipMalloc(&sp, spacer) == hipSuccess) held.push_back(sp); else (void)hipGetLastError();
         if (int rc = derived_move(t, which, &moved)) { derived_settle(t, moved, false, &held); for (char* p : held) (void)hipFree(p); return rc; }

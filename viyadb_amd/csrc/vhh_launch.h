@@ -28,15 +28,14 @@ void QueryBuild::predpack_auto(bool want_sliced) {
   for (uint32_t sgi = 0; sgi < t->nseg; ++sgi) rows += t->seg_rows[sgi];
   if (!(vh_jit_policy() == VH_JIT_FORCE || (p->flags & VH_PLAN_FORCE_JIT) || rows >= vh_jit_min_rows())) return;
   const bool sliced = want_sliced && !knobs().predpack_bytes;
-  for (auto& q : t->predpacks) if (q->cols == pp_cols && q->sliced == sliced) return;
+  if (predpack_find(t, pp_cols, sliced)) return;
   std::string key = sliced ? "s:" : "b:";
   for (int c : pp_cols) { key += std::to_string(c); key.push_back(','); }
   if (++t->ppred_seen[key] < (uint32_t)auto_after) return;
   if (build_background(t)) { build_pending |= build_request_layout(t, VB_PREDPACK, pp_cols, sliced, true, key, p); return; }      // (the worker builds it and evaluates the guard)
-  size_t free_b = 0, total_b = 0;
   const size_t need = (size_t)t->cap_seg * t->padded_rows * 4;
   const size_t had = t->predpacks.size();
-  if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > need + total_b / 4) { (void)table_predpack_locked(t, pp_cols, true, nullptr, sliced); t->inline_builds += t->predpacks.size() > had; }
+  if (device_room(need)) { (void)table_predpack_locked(t, pp_cols, true, nullptr, sliced); t->inline_builds += t->predpacks.size() > had; }
   else t->ppred_seen[key] = 0;
 }
 
@@ -85,7 +84,7 @@ void QueryBuild::choose_grouped() {
   // the form is built where it is missing, is another column's, or lacks the clustered planes of the bit-sliced projection this plan reads
   // (that projection was dropped and described again since): records, headers and planes come out of one launch, so it starts over
   const bool other = gr && (gr->col != gcol || gr->bits != gbits);
-  const bool bare = gr && !other && sliced_use->bits > gbits && (!gr->planes || gr->pp_serial != sliced_use->serial);
+  const bool bare = gr && !other && sliced_use->bits > gbits && (!gr->planes.ptr || gr->pp_serial != sliced_use->serial);
   auto build = [&]() {
     const int auto_after = g_preparing ? 1 : knobs().auto_pack;
     if (auto_after <= 0) return;
@@ -110,9 +109,9 @@ void QueryBuild::choose_grouped() {
     if (!gr || gr->col != gcol || gr->bits != gbits) return;
   }
   // as current as the planes whose bits give the places, and as the table: anything else is a stale layout
-  if (!gr->base || !gr->hdr || gr->applied_epoch != t->sync_epoch || sliced_use->applied_epoch != t->sync_epoch || packed_use->applied_epoch != t->sync_epoch) return;
-  for (int s = 0; s < P.nslots; ++s) if (slot_rec[s] == 0 && slot_bits[s] == 4) P.colbase[s] = gr->base;      // (a bit record's members all start at the record)
-  P.colbase[P.nslots] = gr->hdr; P.colstride[P.nslots] = gr->hdr_stride; P.colpitch[P.nslots] = vh_grouped_hdr_bytes(gbits);
+  if (!gr->rec.ptr || !gr->hdr.ptr || gr->applied_epoch != t->sync_epoch || sliced_use->applied_epoch != t->sync_epoch || packed_use->applied_epoch != t->sync_epoch) return;
+  for (int s = 0; s < P.nslots; ++s) if (slot_rec[s] == 0 && slot_bits[s] == 4) P.colbase[s] = gr->rec.ptr;      // (a bit record's members all start at the record)
+  P.colbase[P.nslots] = gr->hdr.ptr; P.colstride[P.nslots] = gr->hdr.stride; P.colpitch[P.nslots] = vh_grouped_hdr_bytes(gbits);
   js.pp_group = gp; js.pp_group_hdr = P.nslots++; js.pp_group_lit = (int)g[leaf_of[gp]].lit();
   grouped = true;
   // The CLUSTERED planes beside the grouped records (vh_grouped.h): the scan reads only the words that cover the run [start[literal], end) of
@@ -122,12 +121,12 @@ void QueryBuild::choose_grouped() {
   //   * every segment's snapshot is the rows the form was built with or a multiple of the tile (0 included): places have lost their row
   //     numbers, so a snapshot that cuts into a built tile cannot be honoured — such a plan keeps the row-order planes, as before.
   // VH_PLAN_NO_GPLANES keeps the row-order planes: an A/B inside one process.
-  if ((p->flags & VH_PLAN_NO_GPLANES) || !gr->planes || !gr->G || gr->pp_serial != sliced_use->serial || P.nslots >= VH_MAX_SLOTS) return;
+  if ((p->flags & VH_PLAN_NO_GPLANES) || !gr->planes.ptr || !gr->G || gr->pp_serial != sliced_use->serial || P.nslots >= VH_MAX_SLOTS) return;
   int reads = 0;
   for (const VhProgOp& o : g) if (o.kind() != VH_F_AND && o.kind() != VH_F_OR && o.kind() != VH_F_TRUE && (int)o.pslot() == gp) ++reads;
   if (reads != 1) return;
   for (uint32_t s = 0; s < nseg; ++s) if (x->h_segrows[s] != (uint32_t)t->seg_rows[s] && x->h_segrows[s] % VH_GROUP_TILE != 0) return;
-  P.colbase[P.nslots] = gr->planes; P.colstride[P.nslots] = gr->planes_stride; P.colpitch[P.nslots] = 4u * gr->G;
+  P.colbase[P.nslots] = gr->planes.ptr; P.colstride[P.nslots] = gr->planes.stride; P.colpitch[P.nslots] = 4u * gr->G;
   js.gp_slot = P.nslots++; js.gp_G = (int)gr->G; js.gp_goff = (int)gr->goff;
   gplanes = true;
 }
@@ -140,7 +139,6 @@ int vh_jit_drain_depth(const VhJitShape& s) {
 }
 
 int QueryBuild::compile_kernel() {
-  int rc = VH_OK; (void)rc;
   // ---------------- the scan kernel compiled for this plan shape (vh_jit.hip), when there is to be one
   // the no-compaction kernels are pre-built, except DENSE_LDS's over plain 4- / 8-byte arena columns (C2's shape), which has a compiled form
   if (jit_try && lanes && (mode != VH_MODE_DENSE_LDS || test_env("VH_TEST_NO_JIT_LANES"))) jit_try = false;
@@ -311,7 +309,6 @@ void QueryBuild::scan_dispatch(int grid_, int* occ) {
 }
 
 int QueryBuild::decompose_work() {
-  int rc = VH_OK; (void)rc;
   // ---------------- work decomposition
   // The lanes kernels expose the latency of their payload loads (issued and consumed inside a sub-step), so they gain
   // from every extra resident wave: 256-thread blocks, as many per CU as registers and LDS allow (asked of the runtime
@@ -386,7 +383,7 @@ int QueryBuild::decompose_work() {
 }
 
 int QueryBuild::layout_scratch() {
-  int rc = VH_OK; (void)rc;
+  int rc = VH_OK;
   // ---------------- scratch layout
   ScratchPlan sp;
   // [counters | out_count | output key arrays | output state arrays] is one region: it is read back with a
@@ -647,7 +644,7 @@ int QueryBuild::layout_scratch() {
 }
 
 int QueryBuild::launch() {
-  int rc = VH_OK; (void)rc;
+  int rc = VH_OK;
   // ---------------- init + launch
   hipStream_t st = x->stream();
   if (int frc = derived_fence(t, st)) return frc;      // derived layouts refreshed for this query are still on the table's stream

@@ -328,7 +328,6 @@ int QueryBuild::slot(int col) {
 }
 
 int QueryBuild::shape_filter() {
-  int rc = VH_OK; (void)rc;
   // ---------------- validate
   if (p->nfilter < 0 || p->nlits < 0 || p->ngroups < 0 || p->nmetrics < 0 || p->nhaving < 0)
     return vh_fail(VH_E_INVALID, "plan has a negative count");
@@ -533,7 +532,7 @@ int QueryBuild::shape_filter() {
     if (pb && P.nslots + pb->nplanes <= VH_MAX_SLOTS) {
       jshape.pp_nplanes = pb->nplanes;
       for (int q = 0; q < pb->nplanes; ++q) {
-        P.colbase[P.nslots] = pb->pbase[q]; P.colstride[P.nslots] = pb->pstride[q]; P.colpitch[P.nslots] = (uint32_t)pb->pwidth[q];
+        P.colbase[P.nslots] = pb->plane[q].ptr; P.colstride[P.nslots] = pb->plane[q].stride; P.colpitch[P.nslots] = (uint32_t)pb->pwidth[q];
         jshape.pp_plane[q].slot = P.nslots++; jshape.pp_plane[q].width = pb->pwidth[q]; jshape.pp_plane[q].pos = pb->ppos[q];
       }
       for (int k = 0; k < jshape.npred; ++k) {
@@ -543,7 +542,7 @@ int QueryBuild::shape_filter() {
       jit_predpack = true;
     }
     if (ps && P.nslots < VH_MAX_SLOTS) {
-      P.colbase[P.nslots] = ps->pbase[0]; P.colstride[P.nslots] = ps->pstride[0]; P.colpitch[P.nslots] = (uint32_t)ps->pitch;
+      P.colbase[P.nslots] = ps->plane[0].ptr; P.colstride[P.nslots] = ps->plane[0].stride; P.colpitch[P.nslots] = (uint32_t)ps->pitch;
       jshape.pp_sliced = 1; jshape.pp_slot = P.nslots++;
       sliced_use = ps;
       for (int k = 0; k < jshape.npred; ++k) {
@@ -561,22 +560,20 @@ int QueryBuild::shape_filter() {
     auto narrow_for = [&](int col) -> int {
       auto hit = narrow_slot.find(col);
       if (hit != narrow_slot.end()) return hit->second;
-      bool have = false;
-      for (auto& nw : t->narrows) have |= nw->col == col;
+      const bool have = narrow_find(t, col) != nullptr;
       if (jit_predpack && !have) return narrow_slot[col] = -1;       // (the compiled kernel reads the predicate projection: no copy of its own for this column)
-      const int nwidth = have ? 0 : narrow_width_for(t, col, t->nseg);
+      const int nwidth = have ? 0 : narrow_width_for(t, col);
       // (every query that filters on the column reads it in full, whatever passes: the copy pays from the first query that uses it on)
       if (!have && auto_after > 0 && nwidth && !g_build_quiet && ++t->pred_seen[col] >= (uint32_t)auto_after) {
-        size_t free_b = 0, total_b = 0;
         const size_t need = (size_t)t->cap_seg * ((t->segment_rows + 255) / 256 * 256) * (size_t)nwidth;
         if (build_background(t)) build_pending |= build_request_layout(t, VB_NARROW, std::vector<int>{col}, false, true, std::string(), plan_only ? nullptr : p);      // (the worker builds it; the guard is its to evaluate)
-        else if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && free_b > need + total_b / 4) { const size_t had = t->narrows.size(); (void)table_narrow_locked(t, col, true); t->inline_builds += t->narrows.size() > had; }
+        else if (device_room(need)) { const size_t had = t->narrows.size(); (void)table_narrow_locked(t, col, true); t->inline_builds += t->narrows.size() > had; }
         else t->pred_seen[col] = 0;
       }
       int ns = -1;
-      VhNarrow* nw = narrow_usable(t, col, nseg);
+      VhNarrow* nw = narrow_usable(t, col);
       if (nw && P.nslots < VH_MAX_SLOTS) {
-        P.colbase[P.nslots] = nw->base; P.colstride[P.nslots] = nw->stride; P.colpitch[P.nslots] = (uint32_t)nw->width;
+        P.colbase[P.nslots] = nw->copy.ptr; P.colstride[P.nslots] = nw->copy.stride; P.colpitch[P.nslots] = (uint32_t)nw->width;
         ns = P.nslots++;
       }
       return narrow_slot[col] = ns;
@@ -602,7 +599,7 @@ int QueryBuild::shape_filter() {
 }
 
 int QueryBuild::snapshot_segments() {
-  int rc = VH_OK; (void)rc;
+  int rc = VH_OK;
   // ---------------- segments: snapshot + skip
   // one pinned staging block [segment snapshot | program | literals | sets] -> one upload per query
   const size_t seg_words = ((size_t)std::max<uint32_t>(nseg, 1) + 1) / 2 * 2;
@@ -661,7 +658,7 @@ int QueryBuild::probed_selectivity(double* sel) {
 }
 
 int QueryBuild::shape_groups() {
-  int rc = VH_OK; (void)rc;
+  int rc = VH_OK;
   // ---------------- group columns
   P.ngroup = p->ngroups;
   if (summary_out) for (int i = 0; i < VH_MAX_GROUP; ++i) { summary_out->klo[i] = ~0ull; summary_out->khi[i] = 0; }
@@ -746,7 +743,6 @@ int QueryBuild::shape_groups() {
 }
 
 int QueryBuild::shape_metrics() {
-  int rc = VH_OK; (void)rc;
   // ---------------- metrics
   P.nmetric = 0;
   bool has_avg = false, has_count = false;
@@ -871,7 +867,7 @@ int QueryBuild::shape_metrics() {
 }
 
 int QueryBuild::choose_organisation() {
-  int rc = VH_OK; (void)rc;
+  int rc = VH_OK;
   // ---------------- choose the table organisation
   size_t state_bytes_per_group = 1;  // presence byte
   for (int j = 0; j < P.nmetric; ++j) state_bytes_per_group += vh_sop_bytes(P.m[j].sop());
@@ -1180,7 +1176,7 @@ int QueryBuild::choose_organisation() {
 }
 
 int QueryBuild::plan_hashed_partitioning() {
-  int rc = VH_OK; (void)rc;
+  int rc = VH_OK;
   // ---------------- hashed partitioning (HASH organisation with MANY groups: hash_part_agg_kernel, vh_kernels.h)
   // With tens of millions of groups every survivor costs the plain hash table 2-5 read-modify-writes at random addresses of a
   // table no cache holds — the device does ~20 G of those per second (C5: 312 M per 125 M rows = 15.9 ms) — and a count-distinct
@@ -1316,7 +1312,7 @@ int QueryBuild::plan_hashed_partitioning() {
 }
 
 int QueryBuild::choose_projection() {
-  int rc = VH_OK; (void)rc;
+  int rc = VH_OK;
   // ---------------- payload projection: when few rows pass, a survivor's group / metric values come out of ONE packed
   // record (vh_table_pack) instead of one line per column arena. Only the compacting kernels gather by row; the lanes
   // kernels read whole column ranges and keep the arenas.
@@ -1370,8 +1366,7 @@ int QueryBuild::choose_projection() {
           uint32_t bytes = 0; for (int c : gcols) bytes += (uint32_t)t->cols[c].esize;
           uint32_t rec = 8; while (rec < bytes) rec <<= 1;
           const size_t need = (size_t)t->cap_seg * ((t->segment_rows + 255) / 256 * 256) * rec;
-          size_t free_b = 0, total_b = 0;
-          build = bytes <= 64 && hipMemGetInfo(&free_b, &total_b) == hipSuccess && need <= t->device_bytes && free_b > need + total_b / 4;
+          build = bytes <= 64 && need <= t->device_bytes && device_room(need);
           if (!build) t->gather_seen[sig] = 0;
         }
         if (build && table_pack_locked(t, gcols.data(), (int32_t)gcols.size(), !forced, &use, jit_try && !knobs().pack_plain) != VH_OK) use = nullptr;
@@ -1379,7 +1374,7 @@ int QueryBuild::choose_projection() {
       }
     }
     if (use) {
-      rc = pack_refresh(t, use, 0, nseg);   // on the table's main stream, complete when it returns
+      rc = pack_refresh(t, use);   // on the table's main stream, complete when it returns
       if (rc == VH_PACK_STALE) {            // a synced value outgrew its stored width: rebuilt at the widths the values need now
         const bool was_auto = use->automatic;
         pack_drop(t, use);
@@ -1397,8 +1392,8 @@ int QueryBuild::choose_projection() {
       auto pslot = [&](int col) {
         if (pslot_of[col] >= 0) return pslot_of[col];
         const int k = use->col_index(col);
-        P.colbase[P.nslots] = use->base + use->off[k];
-        P.colstride[P.nslots] = use->stride;
+        P.colbase[P.nslots] = use->rec.ptr + use->off[k];
+        P.colstride[P.nslots] = use->rec.stride;
         P.colpitch[P.nslots] = use->rec_bytes;
         slot_rec[P.nslots] = 0; slot_recoff[P.nslots] = (int)use->off[k]; slot_stored[P.nslots] = (int)use->width[k];
         if (use->bits) { slot_bits[P.nslots] = (int)use->rec_bytes; slot_recoff[P.nslots] = (int)use->bitoff[k]; slot_stored[P.nslots] = (int)use->bitw[k]; }

@@ -1,5 +1,6 @@
 // vhh_table.h — host side of libviya_hip, part of viya_hip.hip's translation unit (included there, in order; not a stand-alone header):
-// the table mirror: column arenas, per-segment stats, execution contexts (stream, scratch, staging, events); vh_table_create / vh_table_destroy.
+// the table mirror: column arenas, per-segment stats, execution contexts (stream, scratch, staging, events), the derived layouts' types, their
+// arenas' ledger (buf_alloc / buf_free) and enumeration (derived_each); vh_table_create / vh_table_destroy.
 // -------------------------------------------------------------------- table
 struct VhColumn {
   int kind = 0, elem = 0, esize = 0;
@@ -12,9 +13,6 @@ struct VhColumn {
   std::vector<uint32_t*> bs_offsets32;  // the same offsets as 32-bit words when the segment holds < 2^32 ids (nullptr otherwise): what the compiled
                                         // scan of the hashed partitioning reads — 4 instead of 8 bytes per row of a stream every query of the set takes in full
   std::vector<uint64_t> bs_maxid;      // an upper bound of the segment's ids (what the packed tuples of the hashed partitioning are sized from)
-};
-struct VhSegStat {          // order keys as produced by seg_minmax_kernel
-  uint64_t lo = ~0ull, hi = 0;
 };
 // Execution context: everything ONE in-flight query needs besides the table's columns — a stream, device scratch,
 // pinned staging, events. A table keeps a pool of them; a vh_result owns one from launch until vh_result_free, so
@@ -41,29 +39,40 @@ struct VhExec {
   hipStream_t stream() const { return g_ctx.stream != g_ctx.own_stream ? g_ctx.stream : own_stream; }
 };
 
+// A per-segment arena of a derived layout: `stride` bytes per segment for as many segments as it was made for, and a tail pad. The pad lives
+// in bytes() alone; `held` is what alloc() took and the table's byte ledger (vh_table::device_bytes) was charged — what free() gives back.
+struct VhBuf {
+  char* ptr = nullptr; uint64_t stride = 0; size_t held = 0;
+  static size_t bytes(uint32_t cap_seg, uint64_t stride) { return (size_t)cap_seg * stride + 256; }
+  size_t bytes(uint32_t cap_seg) const { return bytes(cap_seg, stride); }
+};
+// What every derived layout keeps about itself, and all the refresh path (derived_refresh, vhh_derived.h) needs to know of one.
+struct VhLayout {
+  uint32_t cap_seg = 0;             // segments its arenas have room for
+  std::vector<uint64_t> seg_mod;    // value of vh_table::seg_mod[s] the segment was derived at (0: never)
+  uint64_t applied_epoch = 0;       // every change of the table's journal up to this epoch is in the arenas
+  uint64_t serial = 0;              // vh_table::layout_serial when it was built: which layout this is (derived_settle; addresses get reused). A grouped form carries its projection's
+  bool automatic = false;
+};
 // The GROUPED form of a 4-byte bit-record projection (vh_grouped.h, group_bits_kernel): a second copy of the records in which every tile of
 // 2048 rows is stable-sorted by the field a bit-sliced predicate projection keeps of column `col` (`bits` bits, at most VH_GROUP_MAX_BITS),
 // and the tiles' headers. It belongs to its projection (same stride, dropped and grown with it) but follows the journal by itself: its jobs are
 // whole tiles. A plan reads it only while it is as current as the planes whose bits give the places (QueryBuild::choose_grouped).
-struct VhGrouped {
+struct VhGrouped : VhLayout {
   int col = -1; uint32_t bits = 0;
-  char* base = nullptr;             // records: VhPack::stride bytes per segment
-  char* hdr = nullptr; uint64_t hdr_stride = 0;      // headers: (2 << bits) bytes per tile, hdr_stride per segment
-  uint32_t cap_seg = 0;
-  std::vector<uint64_t> seg_mod; uint64_t applied_epoch = 0;
-  size_t bytes(uint64_t stride) const { return (size_t)cap_seg * stride + 256; }
-  size_t hdr_bytes() const { return (size_t)cap_seg * hdr_stride + 256; }
+  VhBuf rec;                        // records: the projection's stride
+  VhBuf hdr;                        // headers: (2 << bits) bytes per tile
   // CLUSTERED predicate planes (vh_grouped.h): the other columns' bits of the bit-sliced predicate projection `pp_serial`, in the tiles' grouped
   // order, word-major, G dwords a word. Written by the launch that writes records and headers (one epoch, one refresh path). The fields the
   // launch reads are copied from the projection when the arena is made; a plan pairs the two by serial, so a projection that was dropped or
-  // re-described never meets planes of other fields. nullptr: none (no room, or no projection yet) — the grouped records alone answer.
-  char* planes = nullptr; uint64_t planes_stride = 0; uint32_t G = 0;
+  // re-described never meets planes of other fields. planes.ptr == nullptr: none (no room, or no projection yet) — the grouped records alone
+  // answer; planes.stride, G and pp_serial are then 0.
+  VhBuf planes; uint32_t G = 0;
   uint64_t pp_serial = 0; uint32_t goff = 0;
   std::vector<int> pp_cols; std::vector<uint8_t> pp_bitoff, pp_bitw;
-  size_t planes_bytes() const { return (size_t)cap_seg * planes_stride + 256; }
 };
 // Payload projection (vh_table_pack): a row-major copy of a few columns, see pack_kernel.
-struct VhPack {
+struct VhPack : VhLayout {
   std::vector<int> cols;            // table column indices, in record order (widest first)
   std::vector<uint32_t> off;        // byte offset of each column inside a record
   std::vector<uint8_t> width;       // bytes the column's values take in a record (compressed: fewer than its element size)
@@ -73,45 +82,35 @@ struct VhPack {
   bool bits = false;
   std::vector<uint8_t> bitoff, bitw;
   uint32_t rec_bytes = 0;           // power of two, 8..64 (bit-field records: 4 or 8)
-  char* base = nullptr; uint64_t stride = 0; uint32_t cap_seg = 0;
-  std::vector<uint64_t> seg_mod;    // value of vh_table::seg_mod[s] the segment was packed at (0: never)
-  uint64_t applied_epoch = 0;       // every change of the table's journal up to this epoch is in the records
-  uint64_t serial = 0;              // vh_table::layout_serial when it was built: which projection this is (derived_settle; addresses get reused)
-  bool automatic = false;
+  VhBuf rec;                        // the records: rows padded to 256 per segment
   std::unique_ptr<VhGrouped> grouped;      // its grouped form, if one was built (bit-field records of 4 bytes only)
   int col_index(int col) const { for (size_t i = 0; i < cols.size(); ++i) if (cols[i] == col) return (int)i; return -1; }
 };
 // Narrow copy of a predicate column (vh_table_narrow): an unsigned 32-bit column whose values fit 8 or 16 bits, kept a second time
 // at that width. The register-resident scan kernels stream the copy instead of the arena — a predicate column is read in full by
 // every query that filters on it, so its bytes are the floor of the scan (C3: 12 of 18.75 GB per query).
-struct VhNarrow {
+struct VhNarrow : VhLayout {
   int col = -1, width = 0;          // bytes per element: 1 or 2
-  char* base = nullptr; uint64_t stride = 0; uint32_t cap_seg = 0;
-  std::vector<uint64_t> seg_mod;    // vh_table::seg_mod[s] the segment was copied at (0: never)
-  uint64_t applied_epoch = 0;
-  bool automatic = false;
+  VhBuf copy;
 };
 // Bit-packed predicate projection (vh_table_predpack): the predicate columns of a query shape as bit fields of one word per row (each at
 // the bits its recorded min / max need), kept as byte planes — what the per-query compiled scan streams instead of the columns or their
 // narrow copies. C3: d2 (2 bits) + d3 (10) + d4 (10) = 22 bits -> a 2-byte and a 1-byte plane: 3 bytes per row instead of 5 (12 from the arenas).
-struct VhPredPack {
+struct VhPredPack : VhLayout {
   std::vector<int> cols;             // table columns, ascending
   std::vector<uint8_t> bitoff, bitw; // each column's field in the row word
   int nplanes = 0;
   int pwidth[4] = {}, ppos[4] = {};  // bytes per row of plane q, first bit of the word it holds
-  char* pbase[4] = {}; uint64_t pstride[4] = {};
-  uint32_t cap_seg = 0;
-  std::vector<uint64_t> seg_mod; uint64_t applied_epoch = 0;
-  uint64_t serial = 0;               // vh_table::layout_serial when it was built (derived_settle)
-  bool automatic = false;
-  // BIT-SLICED form: one plane per BIT of the word, one bit per row (32 rows = one 4-byte word of a plane); pbase[0] is the whole arena,
-  // pstride[0] the bytes between segments, `pitch` the bytes between planes inside a segment; `bits` planes.
+  VhBuf plane[4];
+  // BIT-SLICED form: one plane per BIT of the word, one bit per row (32 rows = one 4-byte word of a plane); plane[0] is the whole arena,
+  // plane[0].stride the bytes between segments, `pitch` the bytes between planes inside a segment; `bits` planes.
   bool sliced = false; uint32_t bits = 0; uint64_t pitch = 0;
   uint32_t bytes_per_row() const { uint32_t b = 0; for (int q = 0; q < nplanes; ++q) b += (uint32_t)pwidth[q]; return b; }
   uint32_t bits_per_row() const { return sliced ? bits : 8u * bytes_per_row(); }
 };
-// What a sync did to a segment's columns: rows [first, last) at sync epoch `epoch` (the table's journal; derived layouts replay it).
-struct VhChange { uint64_t epoch; uint32_t seg, first, last; };
+// Pinned staging for the job lists the derived-layout kernels read (16 bytes a job; a list lives until its reader's stream has been waited
+// for). The table owns one for the refreshes on the library's stream, the build worker one for its own stream; derived_upload fills both.
+struct VhJobStage { char* buf = nullptr; size_t bytes = 0, used = 0; };
 struct vh_table {
   std::vector<VhColumn> cols;
   uint64_t segment_rows = 0;
@@ -142,7 +141,7 @@ struct vh_table {
   std::vector<std::unique_ptr<VhPack>> packs;
   std::vector<std::unique_ptr<VhNarrow>> narrows;
   std::vector<std::unique_ptr<VhPredPack>> predpacks;
-  uint64_t layout_serial = 0;                             // the last serial given to a projection or predicate projection built
+  uint64_t layout_serial = 0;                             // the last serial given to a layout built
   std::map<std::string, uint32_t> ppred_seen;             // predicate column set -> compiled-kernel queries that filtered on it (automatic predicate projections)
   std::map<int, uint32_t> pred_seen;                     // column -> queries that filtered on it (automatic narrow copies)
   std::vector<uint64_t> seg_mod;                          // sync_epoch of the last change to a segment's columns
@@ -150,7 +149,7 @@ struct vh_table {
   // ranges journalled since — one launch over a list of jobs — instead of every segment whose stamp moved (an upsert batch dirties hundreds
   // of segments by a few rows each). Entries older than `journal_floor` were dropped: a layout behind that re-derives whole segments.
   std::vector<VhChange> journal; uint64_t journal_floor = 0;
-  char* h_jobs = nullptr; size_t h_jobs_bytes = 0, h_jobs_used = 0;     // pinned: the job lists of the refreshes enqueued since the stream was last waited for
+  VhJobStage jobs;                                                       // pinned: the job lists of the refreshes enqueued since the stream was last waited for
   hipEvent_t derived_ev = nullptr; bool derived_pending = false;         // a refresh is enqueued on g_ctx.stream: the next query's stream waits for it
   unsigned int* d_packflag = nullptr;                      // pack_kernel's "a value outgrew its stored width" word
   std::map<std::string, uint32_t> gather_seen;            // payload column set -> low-selectivity queries seen (automatic packs)
@@ -175,6 +174,41 @@ static void trace_alloc(const char* what, const void* p, size_t bytes) {     // 
   if (knobs().trace_alloc) fprintf(stderr, "vh alloc %s %p %zu\n", what, p, bytes);
 }
 
+// THE LEDGER of the derived layouts: these two are the only code that allocates or frees one of their arenas and the only code that moves
+// vh_table::device_bytes for them (t == nullptr: the build worker's buffers before their layout belongs to a table — its publish step adds
+// what they hold). soft: no room is the caller's to handle (VH_E_NOMEM, no message, no HIP error left behind).
+static int buf_alloc(vh_table* t, VhBuf* b, uint32_t cap_seg, const char* what, bool soft = false) {
+  const size_t bytes = b->bytes(cap_seg);
+  if (soft) { if (hipMalloc(&b->ptr, bytes) != hipSuccess) { (void)hipGetLastError(); b->ptr = nullptr; return VH_E_NOMEM; } }
+  else HIP_TRY(hipMalloc(&b->ptr, bytes));
+  trace_alloc(what, b->ptr, bytes);
+  b->held = bytes;
+  if (t) t->device_bytes += bytes;
+  return VH_OK;
+}
+static void buf_free(vh_table* t, VhBuf* b) {
+  if (!b->ptr) return;
+  (void)hipFree(b->ptr);
+  if (t) t->device_bytes -= b->held;
+  b->ptr = nullptr; b->held = 0;
+}
+// Every arena of every derived layout of the table, kind by kind: f(kind, layout, plane, arena). `which`: bit 0 what belongs to the
+// projections (kinds 1, 3, 4), bit 1 the predicate projections' planes (kind 2) — vh_table_relocate's bits —, VL_ALL the rest as well.
+enum { VL_PACK = 1, VL_PLANE = 2, VL_GROUPED = 3, VL_GPLANES = 4, VL_GHDR = 5, VL_NARROW = 6, VL_ALL = ~0u };
+static const char* const VL_NAME[] = {"", "projection", "predicate plane", "grouped projection", "clustered planes", "grouped headers", "narrow"};
+template <class F> static void derived_each(vh_table* t, uint32_t which, F&& f) {
+  if (which & 1u) {
+    for (auto& pk : t->packs) if (pk->rec.ptr) f(VL_PACK, *pk, 0, pk->rec);
+    for (auto& pk : t->packs) if (pk->grouped && pk->grouped->rec.ptr) f(VL_GROUPED, *pk->grouped, 0, pk->grouped->rec);
+    for (auto& pk : t->packs) if (pk->grouped && pk->grouped->planes.ptr) f(VL_GPLANES, *pk->grouped, 0, pk->grouped->planes);
+  }
+  if (which & 2u) for (auto& pp : t->predpacks) for (int q = 0; q < pp->nplanes; ++q) if (pp->plane[q].ptr) f(VL_PLANE, *pp, q, pp->plane[q]);
+  if (which == VL_ALL) {
+    for (auto& pk : t->packs) if (pk->grouped && pk->grouped->hdr.ptr) f(VL_GHDR, *pk->grouped, 0, pk->grouped->hdr);
+    for (auto& nw : t->narrows) if (nw->copy.ptr) f(VL_NARROW, *nw, 0, nw->copy);
+  }
+}
+
 static int table_grow(vh_table* t, uint32_t need_seg) {
   if (need_seg <= t->cap_seg) return VH_OK;
   uint32_t ncap = std::max<uint32_t>(need_seg, std::max<uint32_t>(4, t->cap_seg * 2));
@@ -185,14 +219,14 @@ static int table_grow(vh_table* t, uint32_t need_seg) {
       continue;
     }
     char* nb = nullptr;
-    const size_t bytes = (size_t)ncap * c.stride + 256;
+    const size_t bytes = VhBuf::bytes(ncap, c.stride);
     HIP_TRY(hipMalloc(&nb, bytes));
     trace_alloc("column", nb, bytes);
     if (c.base && t->nseg) {
       HIP_TRY(hipMemcpyAsync(nb, c.base, (size_t)t->nseg * c.stride, hipMemcpyDeviceToDevice, g_ctx.stream));
       HIP_TRY(hipStreamSynchronize(g_ctx.stream));
     }
-    if (c.base) { HIP_TRY(hipFree(c.base)); t->device_bytes -= (size_t)t->cap_seg * c.stride + 256; }
+    if (c.base) { HIP_TRY(hipFree(c.base)); t->device_bytes -= VhBuf::bytes(t->cap_seg, c.stride); }
     c.base = nb;
     t->device_bytes += bytes;
   }
@@ -325,10 +359,8 @@ extern "C" void vh_table_destroy(vh_table* t) {
   if (t->h_sync) (void)hipHostFree(t->h_sync);
   if (t->h_stage) (void)hipHostFree(t->h_stage);
   if (t->d_packflag) (void)hipFree(t->d_packflag);
-  for (auto& pk : t->packs) { if (pk->base) (void)hipFree(pk->base); if (pk->grouped) { (void)hipFree(pk->grouped->base); (void)hipFree(pk->grouped->hdr); if (pk->grouped->planes) (void)hipFree(pk->grouped->planes); } }
-  for (auto& nw : t->narrows) if (nw->base) (void)hipFree(nw->base);
-  for (auto& pp : t->predpacks) for (char* b : pp->pbase) if (b) (void)hipFree(b);
-  if (t->h_jobs) (void)hipHostFree(t->h_jobs);
+  derived_each(t, VL_ALL, [&](int, VhLayout&, int, VhBuf& b) { buf_free(t, &b); });
+  if (t->jobs.buf) (void)hipHostFree(t->jobs.buf);
   if (t->derived_ev) (void)hipEventDestroy(t->derived_ev);
   delete t;
 }
