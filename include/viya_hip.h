@@ -296,7 +296,8 @@ typedef struct vh_result_info {
                                 bit 22: the filter's VH_F_INSET leaves were evaluated by set lookup;
                                 bit 23: ... at least one of them by binary search in a sorted array (the others, or all: one bit of a bitmap);
                                 bit 19: (VH_BUILD_BACKGROUND tables) a kernel compile or a layout build for this query's shape is queued or running:
-                                        this query ran on what existed (the pre-built kernels, the arenas, layouts already there) */
+                                        this query ran on what existed (the pre-built kernels, the arenas, layouts already there);
+                                bit 24: (tables with a layout budget) planning this query evicted at least one derived layout */
   uint64_t returned_groups;  /* rows vh_result_copy delivers (= ngroups without HAVING) */
 } vh_result_info;
 
@@ -468,6 +469,37 @@ VH_API int vh_segment_read(vh_table* t, uint32_t seg, int32_t col, uint64_t nrow
                            void* dst);
 VH_API int vh_table_info(vh_table* t, uint32_t* nseg, uint64_t* segment_rows,
                          uint64_t* device_bytes);
+
+/* LIFETIME of the derived layouts (projections with their grouped form and clustered planes, predicate projections, narrow copies). They are
+ * built unasked, so a table can be given a BYTE BUDGET for them: the sum of every layout's arenas plus those of a background build in flight
+ * (the column arenas are not part of it). Every plan stamps the layouts it reads with the table's query tick. An automatic build that would
+ * pass the budget evicts unpinned layouts first, least recently used first (ties: the older serial), and is declined — nothing evicted,
+ * the query answers from what exists — when even all of them would not make room. A layout read by the plan being made is never its victim.
+ * An evicted shape is counted from zero again (VH_AUTO_PACK / VH_AUTO_NARROW new sightings before it is rebuilt). PINNED layouts never leave
+ * this way: those built by vh_table_pack* / vh_table_narrow / vh_table_predpack*, and everything the plan of a successful vh_table_prepare
+ * reads. Explicit builds and vh_table_prepare are never refused for the budget; pinned bytes may exceed it (the listing shows that).
+ * The rule that a quarter of the device stays free holds beside the budget, unchanged. No budget (the default): nothing is ever evicted. */
+enum vh_layout_kind { VH_LAYOUT_PROJECTION = 1, VH_LAYOUT_PRED_BYTES = 2, VH_LAYOUT_PRED_SLICED = 3, VH_LAYOUT_NARROW = 4 };
+#define VH_LAYOUT_COLS 32
+typedef struct vh_layout_info {
+  uint64_t serial;            /* identity: names the layout in the calls below; a rebuilt layout has a new one */
+  int32_t kind, ncols;        /* ncols may exceed VH_LAYOUT_COLS; cols holds the first VH_LAYOUT_COLS, in the layout's own order */
+  int32_t cols[VH_LAYOUT_COLS];
+  uint64_t bytes;             /* every arena, its grouped form included */
+  uint64_t grouped_bytes;     /* of which grouped records + headers + clustered planes */
+  uint32_t flags;             /* bit 0 automatic, 1 pinned, 2 current (applied_epoch == the table's sync epoch), 3 compressed, 4 bit-field records,
+                                 5 has a grouped form, 6 ... with clustered planes */
+  uint32_t reserved;
+  uint64_t uses, last_use;    /* plans that read it; the table's query tick at the last of them (0: never) */
+} vh_layout_info;
+typedef struct vh_layout_summary {      /* bytes + reserved_bytes is the figure the budget bounds */
+  uint64_t budget, bytes, pinned_bytes, reserved_bytes, tick, evictions, evicted_bytes, declined;
+} vh_layout_summary;
+VH_API int vh_table_set_layout_budget(vh_table* t, uint64_t bytes);  /* 0: none (the default; VH_LAYOUT_BUDGET sets what tables start with). Lowering it evicts at once, LRU first; pinned layouts stay */
+VH_API int vh_table_layouts(vh_table* t, vh_layout_info* out, uint32_t cap, uint32_t* n, vh_layout_summary* sum);
+                                              /* *n = layouts that exist (may exceed cap); out / sum may be NULL; ascending serial */
+VH_API int vh_table_layout_pin(vh_table* t, uint64_t serial, int32_t pinned);   /* VH_E_INVALID: no such layout */
+VH_API int vh_table_layout_drop(vh_table* t, uint64_t serial);                  /* whatever its pin; VH_E_INVALID: no such layout */
 /* Per-segment min/max of a column as mirrored (SegmentStats). */
 VH_API int vh_segment_stats(vh_table* t, uint32_t seg, int32_t col,
                             vh_anynum* min_out, vh_anynum* max_out);

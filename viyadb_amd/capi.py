@@ -144,6 +144,7 @@ INFO_GROUPED_PAYLOAD = 1 << 20    # vh_result_info.reserved bit 20
 INFO_GROUPED_PLANES = 1 << 21     # vh_result_info.reserved bit 21
 INFO_INSET = 1 << 22              # vh_result_info.reserved bit 22: the filter's set leaves were evaluated by lookup
 INFO_INSET_SEARCH = 1 << 23       # ... bit 23: at least one of them by binary search in a sorted array
+INFO_EVICTED = 1 << 24            # ... bit 24: planning this query evicted at least one derived layout (tables with a layout budget)
 
 
 class BuildInfo(C.Structure):
@@ -153,6 +154,25 @@ class BuildInfo(C.Structure):
                 ("kernels_cached", C.c_uint64), ("layouts_built", C.c_uint64), ("inline_builds", C.c_uint64),
                 ("compile_ms", C.c_double), ("layout_ms", C.c_double), ("lock_ms", C.c_double),
                 ("jobs_declined", C.c_uint64), ("layout_restarts", C.c_uint64), ("warm_queries", C.c_uint64), ("warm_ms", C.c_double)]
+
+
+LAYOUT_PROJECTION, LAYOUT_PRED_BYTES, LAYOUT_PRED_SLICED, LAYOUT_NARROW = 1, 2, 3, 4      # enum vh_layout_kind
+LAYOUT_COLS = 32                  # VH_LAYOUT_COLS
+# vh_layout_info.flags
+LAYOUT_AUTOMATIC, LAYOUT_PINNED, LAYOUT_CURRENT, LAYOUT_COMPRESSED, LAYOUT_BITS, LAYOUT_GROUPED, LAYOUT_GPLANES = 1, 2, 4, 8, 16, 32, 64
+
+
+class LayoutInfo(C.Structure):
+    """vh_layout_info: one derived layout of a table (vh_table_layouts)."""
+    _fields_ = [("serial", C.c_uint64), ("kind", C.c_int32), ("ncols", C.c_int32), ("cols", C.c_int32 * LAYOUT_COLS),
+                ("bytes", C.c_uint64), ("grouped_bytes", C.c_uint64), ("flags", C.c_uint32), ("reserved", C.c_uint32),
+                ("uses", C.c_uint64), ("last_use", C.c_uint64)]
+
+
+class LayoutSummary(C.Structure):
+    """vh_layout_summary: bytes + reserved_bytes is the figure the budget bounds."""
+    _fields_ = [("budget", C.c_uint64), ("bytes", C.c_uint64), ("pinned_bytes", C.c_uint64), ("reserved_bytes", C.c_uint64),
+                ("tick", C.c_uint64), ("evictions", C.c_uint64), ("evicted_bytes", C.c_uint64), ("declined", C.c_uint64)]
 
 
 
@@ -189,6 +209,10 @@ SYMBOLS = {
     "vh_segment_read": (C.c_int, [_VP, C.c_uint32, C.c_int32, C.c_uint64, _VP]),
     "vh_device_read": (C.c_int, [_VP, _VP, C.c_uint64]),
     "vh_table_info": (C.c_int, [_VP, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "vh_table_set_layout_budget": (C.c_int, [_VP, C.c_uint64]),
+    "vh_table_layouts": (C.c_int, [_VP, C.POINTER(LayoutInfo), C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(LayoutSummary)]),
+    "vh_table_layout_pin": (C.c_int, [_VP, C.c_uint64, C.c_int32]),
+    "vh_table_layout_drop": (C.c_int, [_VP, C.c_uint64]),
     "vh_segment_stats": (C.c_int, [_VP, C.c_uint32, C.c_int32, C.POINTER(AnyNum), C.POINTER(AnyNum)]),
     "vh_query_agg": (C.c_int, [_VP, C.POINTER(Plan), C.POINTER(_VP)]),
     "vh_query_launch": (C.c_int, [_VP, C.POINTER(Plan), C.POINTER(_VP)]),

@@ -12,7 +12,8 @@
 // by the next query and reported as in the inline mode.
 //
 // LAYOUTS (payload projections, predicate projections, narrow copies) are built beside queries and syncs in three steps:
-//   (a) under t->mu: the free-memory guard (evaluated NOW, not when the job was queued), the layout's description from the recorded stats,
+//   (a) under t->mu: the table's layout budget (derived_make_room: it may evict other layouts; the arenas count as vh_table::build_reserved
+//       from here to the publish) and the free-memory guard (both evaluated NOW, not when the job was queued), the layout's description from the recorded stats,
 //       its buffers, the journal epoch E and the arena generation it builds against, and the build kernels ENQUEUED on the worker's stream
 //       (behind an event on the library's stream: every sync up to E has landed when they start);
 //   (b) t->mu released: the kernels run; the worker waits for its stream;
@@ -58,6 +59,17 @@
 static thread_local int g_build_quiet = 0;        // this thread's queries count towards no automatic layout and queue none (a pending query's second plan, the worker's own queries)
 static thread_local bool g_build_inline = false;  // this thread's queries treat every table as inline (sharded queries)
 static thread_local bool g_build_worker = false;  // this thread is the worker (its build_warm queries build a projection's grouped form themselves: choose_grouped)
+// The plan being made on this thread reads layout `L` (t->mu held): stamped with the table's query tick, once per query however often the plan
+// starts over, and before any automatic build site of the same plan runs — what a plan reads is never its own victim (derived_make_room).
+// A quiet plan holds what it reads but counts as no use. vh_table_prepare remembers what its query read: pinned when it ends.
+static void layout_use(vh_table* t, VhLayout* L) {
+  L->held_tick = t->use_tick;
+  if (g_build_quiet || g_plan_unstamped || L->last_use == t->use_tick) return;
+  L->last_use = t->use_tick; ++L->uses;
+  if (!g_preparing) return;
+  g_prepare_reads.push_back(L->serial);
+  if (!L->pinned) { L->pinned = true; g_prepare_pinned.push_back(L->serial); }      // (at once, under the lock the stamp is made under: no query between two rounds of the prepare evicts it)
+}
 static bool build_background(const vh_table* t) { return t->build_mode == VH_BUILD_BACKGROUND && !g_preparing && !g_build_inline; }
 
 struct VhPlanCopy {        // a plan that outlives its caller's arrays (segment snapshot dropped: the rows of the last sync)
@@ -93,6 +105,7 @@ struct VhBuildJob {
   uint32_t gbits = 0; uint64_t serial = 0;      // VB_GROUPED: the grouping column's field bits, and VhPack::serial of the projection the form belongs to
   uint64_t pp_serial = 0;              // ... and VhPredPack::serial of the bit-sliced predicate projection whose other columns' bits it keeps clustered (0: none)
   bool form = false, automatic = true; // VB_PACK: compressed records; VB_PREDPACK: bit-sliced planes
+  bool pinned = false;                 // the layout it replaces was pinned (a compressed projection a value outgrew): so is this one
   std::string seen;                    // the sightings counter that asked (reset when the job comes to nothing)
   std::atomic<bool> cancel{false};
 };
@@ -154,7 +167,7 @@ static bool build_request_kernel(vh_table* t, const VhJitShape& s) {
   return build_queue(t, VB_KERNEL, "k:" + s.key(), [&](VhBuildJob& j) { j.shape = s; }, nullptr);
 }
 // `plan`: the aggregate plan that asked (nullptr: none to run again afterwards)
-static bool build_request_layout(vh_table* t, int kind, const std::vector<int>& cols, bool form, bool automatic, const std::string& seen, const vh_plan* plan) {
+static bool build_request_layout(vh_table* t, int kind, const std::vector<int>& cols, bool form, bool automatic, const std::string& seen, const vh_plan* plan, bool pinned = false) {
   std::string key = kind == VB_PACK ? "p:" : kind == VB_PREDPACK ? "q:" : "n:";
   key += form ? "1:" : "0:";
   std::vector<int> sorted_cols = cols;
@@ -162,7 +175,7 @@ static bool build_request_layout(vh_table* t, int kind, const std::vector<int>& 
   for (int c : sorted_cols) { key += std::to_string(c); key.push_back(','); }
   auto no = t->build_nothing.find(key);
   if (no != t->build_nothing.end()) { if (no->second == t->sync_epoch) return false; t->build_nothing.erase(no); }      // (judged "nothing to gain" at this very state of the table)
-  return build_queue(t, kind, key, [&](VhBuildJob& j) { j.cols = cols; j.form = form; j.automatic = automatic; j.seen = seen; }, plan);
+  return build_queue(t, kind, key, [&](VhBuildJob& j) { j.cols = cols; j.form = form; j.automatic = automatic; j.seen = seen; j.pinned = pinned; }, plan);
 }
 
 // The grouped form (VhGrouped) of projection `serial` by column `col`. It is no layout of its own but a second form of a projection that
@@ -268,15 +281,28 @@ static int build_run_kernel(VhBuildJob* j) {
 // (t->mu held) Room for the grouped form of `pk` under the rule every automatic layout is built by: a quarter of the device stays free.
 // 0: none; 1: for the grouped records; 2: for the clustered planes of `pp` (gbits of whose bits are the grouping column's) as well. What a form
 // that is about to be replaced holds counts as free.
-static int grouped_room(const vh_table* t, const VhPack* pk, const VhPredPack* pp = nullptr, uint32_t gbits = 0) {
+// Under a layout budget the same two questions are put to it first, planes included and then without (derived_make_room: it may evict other
+// layouts, never `pk` or `pp`); a no counts in vh_table::declined unless this is vh_table_prepare, which the budget never refuses.
+static int grouped_room(vh_table* t, const VhPack* pk, const VhPredPack* pp = nullptr, uint32_t gbits = 0) {
   size_t free_b = 0, total_b = 0;
   const size_t need = (size_t)t->cap_seg * pk->rec.stride;
+  const bool with_planes = pp && pp->sliced && pp->bits > gbits;
+  const size_t planes = with_planes ? (size_t)t->cap_seg * vh_gplanes_seg_bytes(t->segment_rows, vh_gplanes_group(pp->bits - gbits)) : 0;
+  int budget = 2;
+  if (t->layout_budget && !g_preparing) {
+    const VhGrouped* gr = pk->grouped.get();
+    const uint64_t credit = gr ? gr->rec.held + gr->hdr.held + gr->planes.held : 0;
+    const uint64_t tiles = (t->segment_rows + VH_GROUP_TILE - 1) / VH_GROUP_TILE;
+    const uint64_t base = VhBuf::bytes(t->cap_seg, pk->rec.stride) + VhBuf::bytes(t->cap_seg, (tiles * vh_grouped_hdr_bytes(gbits) + 63) / 64 * 64);
+    if (with_planes && derived_make_room(t, base + VhBuf::bytes(t->cap_seg, vh_gplanes_seg_bytes(t->segment_rows, vh_gplanes_group(pp->bits - gbits))), pk, pp, credit)) budget = 2;
+    else if (derived_make_room(t, base, pk, pp, credit)) budget = 1;
+    else { ++t->declined; return 0; }
+  }
   if (!device_mem(&free_b, &total_b)) return 0;
   if (const VhGrouped* gr = pk->grouped.get()) free_b += gr->rec.held + gr->planes.held;
   if (free_b <= need + total_b / 4) return 0;
-  if (!pp || !pp->sliced || pp->bits <= gbits) return 1;
-  const size_t planes = (size_t)t->cap_seg * vh_gplanes_seg_bytes(t->segment_rows, vh_gplanes_group(pp->bits - gbits));
-  return free_b > need + planes + total_b / 4 ? 2 : 1;
+  if (!with_planes) return 1;
+  return std::min(budget, free_b > need + planes + total_b / 4 ? 2 : 1);
 }
 static int build_run_grouped(VhBuildJob* j) {
   vh_table* t = j->t;
@@ -359,11 +385,14 @@ static int build_run_layout(VhBuildJob* j) {
         L = nw.get(); bufs.push_back(&nw->copy);
         launch = [&](const VhJob* d_jobs, size_t n) { narrow_launch(t, nw.get(), d_jobs, n, g_build.stream); };
       }
-      L->cap_seg = t->cap_seg; L->seg_mod.assign(t->cap_seg, 0);
+      L->cap_seg = t->cap_seg; L->seg_mod.assign(t->cap_seg, 0); L->pinned = j->pinned;
       for (VhBuf* b : bufs) bytes += b->bytes(t->cap_seg);
+      // the layout budget first (it may evict; a no evicts nothing), then the device's own guard
+      if (!j->pinned && !derived_make_room(t, bytes)) { ++t->declined; return nothing(false); }
       // room: a quarter of the device stays free, and a projection does not outgrow the table
       if (!device_room(bytes) || (pk && bytes > t->device_bytes + 256)) return nothing(false);
       for (VhBuf* b : bufs) if (buf_alloc(nullptr, b, t->cap_seg, "background layout", true)) { drop(); return nothing(false); }
+      t->build_reserved = bytes;      // real bytes that the ledger takes over at the publish: the budget counts them from now on
       E = t->sync_epoch; gen = t->arena_gen; nseg_a = t->nseg; mod_a = t->seg_mod;
       std::vector<VhJob> jobs;
       derived_jobs(t, *L, row_limit, false, &jobs);
@@ -372,7 +401,7 @@ static int build_run_layout(VhBuildJob* j) {
         const VhJob* d_jobs = nullptr;
         bool pending = false;                        // (the worker waited for its stream after the last list: the staging is free)
         g_build.jobs.used = 0;
-        if (derived_upload(&g_build.jobs, &pending, jobs, &d_jobs)) { (void)hipGetLastError(); drop(); return 1; }
+        if (derived_upload(&g_build.jobs, &pending, jobs, &d_jobs)) { (void)hipGetLastError(); drop(); t->build_reserved = 0; return 1; }
         he = hipEventRecord(g_build.ev, g_ctx.stream);                       // every sync up to E has landed before the build kernels read
         if (he == hipSuccess) he = hipStreamWaitEvent(g_build.stream, g_build.ev, 0);
         if (he == hipSuccess && pk) he = hipMemsetAsync(g_build.d_flag, 0, 256, g_build.stream);
@@ -401,6 +430,7 @@ static int build_run_layout(VhBuildJob* j) {
       struct Timer { double& acc; std::chrono::steady_clock::time_point t0; ~Timer() { acc += build_ms_since(t0); } } timer{lock_ms, c0};
       const bool moved = t->arena_gen != gen || t->cap_seg != L->cap_seg || (E && E < t->journal_floor);
       const bool again = !j->cancel && he == hipSuccess && (moved || (ovf && pk && pk->compressed));
+      t->build_reserved = 0;      // (published below, or dropped)
       if (j->cancel || he != hipSuccess || moved || ovf || exists()) {
         lk.unlock();
         drop();
@@ -415,6 +445,7 @@ static int build_run_layout(VhBuildJob* j) {
       if (pk) t->packs.push_back(std::move(pk));
       else if (pp) t->predpacks.push_back(std::move(pp));
       else t->narrows.push_back(std::move(nw));
+      if (j->pinned) derived_trim(t, false);      // (the budget never refuses a pinned layout's rebuild; what is unpinned makes room afterwards)
     }
     const double ms = build_ms_since(t_begin);
     build_count(t, [&](vh_build_info& i) { ++i.layouts_built; i.layout_ms += ms; i.lock_ms += lock_ms; });

@@ -14,8 +14,12 @@
 //     order queries behind the launch, stamp. The background build (vhh_build.h) uses the same describe / launch / upload pieces off the lock;
 //   * derived_drop — quiesce the table, wait for the library's stream, free through the ledger, erase;
 //   * derived_move / derived_settle — try other places for the arenas (vh_table_prepare, vh_table_relocate).
+//   * derived_make_room / derived_trim — how long a layout lives: the table's byte budget, use stamps, LRU eviction through the drop
+//     functions, pins, and the listing (vh_table_layouts) — see "lifetimes" below.
 #define VH_PACK_STALE 9001      // (internal) pack_refresh: a value no longer fits its stored width, the projection must go
 #define VH_NO_ROOM 9002         // (internal) derived_refresh of a layout that starts over when the table grew: no room for an arena it cannot do without
+// Over the byte budget (vh_table::layout_budget): unpinned layouts leave, least recently used first (defined below, after the drop functions).
+static void derived_trim(vh_table* t, bool in_plan);
 static uint64_t rows_padded_256(const vh_table* t) { return (t->segment_rows + 255) / 256 * 256; }      // rows a projection's stride has room for
 // What layout `L` has to re-derive, as jobs for its kernel (vh_cut_jobs): the journal's ranges since it was current, or whole segments.
 static void derived_jobs(const vh_table* t, const VhLayout& L, uint64_t row_limit, bool whole_tiles, std::vector<VhJob>* jobs) {
@@ -407,15 +411,17 @@ static int table_pack_locked(vh_table* t, const int32_t* cols, int32_t ncols, bo
   }
   std::vector<int> sorted_cols = order;
   std::sort(sorted_cols.begin(), sorted_cols.end());
+  bool was_pinned = false;
   if (VhPack* pk = pack_find(t, sorted_cols, compress)) {
     const int rc = pack_refresh(t, pk);
     if (rc != VH_PACK_STALE) { if (out) *out = pk; return rc; }
-    pack_drop(t, pk);      // built again below, at the widths the values need now
+    was_pinned = pk->pinned;
+    pack_drop(t, pk);      // built again below, at the widths the values need now (a pin is carried over)
   }
   for (int attempt = 0; attempt < 2; ++attempt) {
     std::unique_ptr<VhPack> pk;
     if (int drc = pack_describe(t, order, automatic, compress, &pk)) return drc;
-    pk->serial = ++t->layout_serial;
+    pk->serial = ++t->layout_serial; pk->pinned = was_pinned;
     VhPack* raw = pk.get();
     t->packs.push_back(std::move(pk));
     const int rc = pack_refresh(t, raw);
@@ -566,7 +572,11 @@ extern "C" int vh_table_predpack_ex(vh_table* t, const int32_t* cols, int32_t nc
   std::vector<int> set(cols, cols + ncols);
   std::sort(set.begin(), set.end());
   set.erase(std::unique(set.begin(), set.end()), set.end());
-  return table_predpack_locked(t, set, false, nullptr, form == VH_PREDPACK_AUTO ? !knobs().predpack_bytes : form == VH_PREDPACK_SLICED);
+  const bool sliced = form == VH_PREDPACK_AUTO ? !knobs().predpack_bytes : form == VH_PREDPACK_SLICED;
+  const int rc = table_predpack_locked(t, set, false, nullptr, sliced);
+  if (VhPredPack* pp = rc ? nullptr : predpack_find(t, set, sliced)) pp->pinned = true;      // asked for by name: the budget never evicts it
+  derived_trim(t, false);
+  return rc;
 }
 
 extern "C" int vh_table_narrow(vh_table* t, const int32_t* cols, int32_t ncols) {
@@ -574,9 +584,13 @@ extern "C" int vh_table_narrow(vh_table* t, const int32_t* cols, int32_t ncols) 
   VH_ENTER();
   std::lock_guard<std::mutex> lk(t->mu);
   if (int src = sync_resolve(t)) return src;
-  for (int i = 0; i < ncols; ++i)
-    if (int rc = table_narrow_locked(t, cols[i], false)) return rc;
-  return VH_OK;
+  int rc = VH_OK;
+  for (int i = 0; i < ncols && !rc; ++i) {
+    rc = table_narrow_locked(t, cols[i], false);
+    if (VhNarrow* nw = rc ? nullptr : narrow_find(t, cols[i])) nw->pinned = true;
+  }
+  derived_trim(t, false);
+  return rc;
 }
 
 extern "C" int vh_table_pack_ex(vh_table* t, const int32_t* cols, int32_t ncols, uint32_t form) {
@@ -593,7 +607,11 @@ extern "C" int vh_table_pack_ex(vh_table* t, const int32_t* cols, int32_t ncols,
     for (uint32_t s = 0; s < t->nseg; ++s) rows += t->seg_rows[s];
     compress = !knobs().pack_plain && (vh_jit_policy() == VH_JIT_FORCE || (vh_jit_policy() == VH_JIT_AUTO && rows >= vh_jit_min_rows()));
   }
-  return table_pack_locked(t, cols, ncols, false, nullptr, compress);
+  VhPack* built = nullptr;
+  const int rc = table_pack_locked(t, cols, ncols, false, &built, compress);
+  if (!rc && built) built->pinned = true;
+  derived_trim(t, false);
+  return rc;
 }
 extern "C" int vh_table_pack(vh_table* t, const int32_t* cols, int32_t ncols) { return vh_table_pack_ex(t, cols, ncols, VH_PACK_AUTO); }
 
@@ -609,6 +627,182 @@ static bool device_room(size_t need) {
   return device_mem(&free_b, &total_b) && free_b > need + total_b / 4;
 }
 
+// ------------------------------------------------------- lifetimes: a byte budget, LRU eviction, pins, the listing
+// The layouts above are built unasked and nothing but staleness ever dropped them: a workload of many query shapes filled the device to the
+// 3/4 mark of device_room and every later shape stayed on the arenas. vh_table::layout_budget bounds what they hold together —
+// "layout bytes": every arena derived_each(VL_ALL) visits plus the background job's arenas in flight (build_reserved); the column arenas
+// are not part of it. Every plan stamps what it reads (layout_use, vhh_build.h); an automatic build that would pass the budget first evicts
+// unpinned layouts, least recently used first (derived_make_room), or is declined when even all of them would not make room. Pinned
+// layouts — built by an explicit call or read by a prepared plan — never leave this way and may exceed the budget by themselves. An eviction
+// is the kind's own drop function: derived_drop waits until nobody reads the arenas. With no budget none of this does anything.
+static thread_local int g_plan_depth = 0;                       // query_launch_locked calls on this thread's stack (a plan that starts over is the same query)
+static thread_local bool g_plan_evicted = false;                // this thread's query evicted a layout while it was planned (vh_result_info.reserved bit 24)
+static thread_local bool g_plan_carry = false;                  // ... in a pass that belongs to a query whose result comes later (a sharded query's summary pass): carried to that result
+static thread_local bool g_plan_unstamped = false;              // the plan being made is a further pass of a query already counted (summary pass, heavy second pass): it holds what it reads, `uses` do not move
+static thread_local std::vector<uint64_t> g_prepare_reads;      // vh_table_prepare: serials of the layouts its last query read
+static thread_local std::vector<uint64_t> g_prepare_pinned;     // ... and of the layouts it pinned itself, as its queries stamped them (unpinned again where it fails, or where its last query no longer reads them)
+struct VhLayoutRef {         // one layout as the policy and the listing see it: a projection with its grouped form, a predicate projection with all planes, a narrow copy
+  int kind; VhLayout* L; VhPack* pk; VhPredPack* pp; VhNarrow* nw; uint64_t bytes, grouped_bytes;
+};
+static void layout_refs(vh_table* t, std::vector<VhLayoutRef>* out) {
+  for (auto& q : t->packs) {
+    const VhGrouped* gr = q->grouped.get();
+    const uint64_t g = gr ? gr->rec.held + gr->hdr.held + gr->planes.held : 0;
+    out->push_back(VhLayoutRef{VH_LAYOUT_PROJECTION, q.get(), q.get(), nullptr, nullptr, q->rec.held + g, g});
+  }
+  for (auto& q : t->predpacks) {
+    uint64_t b = 0;
+    for (int k = 0; k < q->nplanes; ++k) b += q->plane[k].held;
+    out->push_back(VhLayoutRef{q->sliced ? VH_LAYOUT_PRED_SLICED : VH_LAYOUT_PRED_BYTES, q.get(), nullptr, q.get(), nullptr, b, 0});
+  }
+  for (auto& q : t->narrows) out->push_back(VhLayoutRef{VH_LAYOUT_NARROW, q.get(), nullptr, nullptr, q.get(), q->copy.held, 0});
+  std::sort(out->begin(), out->end(), [](const VhLayoutRef& a, const VhLayoutRef& b) { return a.L->serial < b.L->serial; });
+}
+// Bytes the arenas `which` names hold (derived_each's sets: 1 projections, 2 predicate planes — vh_table_relocate's bits —, VL_ALL every arena:
+// the figure the layout budget bounds, with vh_table::build_reserved).
+static size_t derived_bytes(vh_table* t, uint32_t which) {
+  size_t b = 0;
+  derived_each(t, which == VL_ALL ? (uint32_t)VL_ALL : which & 3u, [&](int, VhLayout&, int, VhBuf& buf) { b += buf.held; });
+  return b;
+}
+static std::string cols_key(std::vector<int> cols) {
+  std::sort(cols.begin(), cols.end());
+  std::string k;
+  for (int c : cols) { k += std::to_string(c); k.push_back(','); }
+  return k;
+}
+// `v` leaves through its kind's drop function. `evicted`: by the budget — the shape's sightings start again (VH_AUTO_* fresh ones before it is
+// built once more: no thrashing), the counters move, VH_TIMES says what the wait for its readers and the frees took.
+static void layout_drop(vh_table* t, const VhLayoutRef& v, bool evicted) {
+  const bool timed = evicted && knobs().times;
+  const auto t0 = timed ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
+  const uint64_t serial = v.L->serial, bytes = v.bytes;
+  if (v.pk) {
+    const std::string k = cols_key(v.pk->cols), g = "g:" + std::to_string(serial) + ":";
+    t->gather_seen.erase("c:" + k); t->gather_seen.erase("p:" + k);
+    for (auto it = t->gather_seen.lower_bound(g); it != t->gather_seen.end() && it->first.compare(0, g.size(), g) == 0;) it = t->gather_seen.erase(it);
+    t->build_nothing.erase("p:0:" + k); t->build_nothing.erase("p:1:" + k);
+    pack_drop(t, v.pk);
+  } else if (v.pp) {
+    const std::string k = cols_key(v.pp->cols);
+    t->ppred_seen.erase((v.pp->sliced ? "s:" : "b:") + k);
+    t->build_nothing.erase((v.pp->sliced ? "q:1:" : "q:0:") + k);
+    predpack_drop(t, v.pp);
+  } else {
+    t->pred_seen.erase(v.nw->col);
+    t->build_nothing.erase("n:0:" + std::to_string(v.nw->col) + ",");
+    narrow_drop(t, v.nw);
+  }
+  if (!evicted) return;
+  ++t->evictions; t->evicted_bytes += bytes;
+  g_plan_evicted = true;
+  if (timed) fprintf(stderr, "vh evict: %s %llu, %llu bytes, in %.3f ms (the wait for its readers and the frees)\n", v.kind == VH_LAYOUT_PROJECTION ? "projection" : v.kind == VH_LAYOUT_NARROW ? "narrow copy" : "predicate projection",
+                     (unsigned long long)serial, (unsigned long long)bytes, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+}
+// Evict until `deficit` bytes are free. in_plan: what the plan of the current tick holds stays. all_or_nothing: where even every candidate
+// would not cover the deficit, nothing leaves and the answer is false; otherwise every candidate leaves then.
+static bool layout_evict(vh_table* t, uint64_t deficit, bool in_plan, bool all_or_nothing, const VhLayout* keep1 = nullptr, const VhLayout* keep2 = nullptr) {
+  std::vector<VhLayoutRef> refs;
+  layout_refs(t, &refs);
+  std::vector<VhEvictEntry> e;
+  uint64_t can = 0;
+  for (const VhLayoutRef& v : refs) {
+    const bool ok = !v.L->pinned && !(in_plan && v.L->held_tick == t->use_tick) && v.L != keep1 && v.L != keep2;
+    e.push_back(VhEvictEntry{v.bytes, v.L->last_use, v.L->serial, ok});
+    if (ok) can += v.bytes;
+  }
+  std::vector<size_t> victims;
+  bool fits = vh_evict_pick(e.data(), e.size(), deficit, &victims);
+  if (!fits && all_or_nothing) return false;
+  if (!fits) (void)vh_evict_pick(e.data(), e.size(), can, &victims);
+  for (size_t i : victims) layout_drop(t, refs[i], true);
+  return fits;
+}
+// (t->mu held) An automatic build is about to take `need` more bytes: true — they fit the budget, after evictions where it took some; false —
+// they do not, and nothing was evicted. keep1 / keep2: layouts the build is made for (a grouped form's projection and planes), whatever
+// their stamps; credit: bytes the build itself gives back first (the grouped form it replaces).
+static bool derived_make_room(vh_table* t, uint64_t need, const VhLayout* keep1 = nullptr, const VhLayout* keep2 = nullptr, uint64_t credit = 0) {
+  if (!t->layout_budget) return true;
+  const uint64_t have = derived_bytes(t, VL_ALL) + t->build_reserved;
+  const uint64_t after = have - std::min(have, credit) + need;
+  if (after <= t->layout_budget) return true;
+  return layout_evict(t, after - t->layout_budget, true, true, keep1, keep2);
+}
+static void derived_trim(vh_table* t, bool in_plan) {
+  if (!t->layout_budget) return;
+  const uint64_t have = derived_bytes(t, VL_ALL) + t->build_reserved;
+  if (have > t->layout_budget) (void)layout_evict(t, have - t->layout_budget, in_plan, false);
+}
+
+extern "C" int vh_table_set_layout_budget(vh_table* t, uint64_t bytes) {
+  if (!t) return vh_fail(VH_E_INVALID, "vh_table_set_layout_budget: null table");
+  if (!g_ctx.inited) return vh_fail(VH_E_INVALID, "vh_init has not been called");
+  VH_ENTER();
+  std::lock_guard<std::mutex> lk(t->mu);
+  t->layout_budget = bytes;
+  derived_trim(t, false);
+  return VH_OK;
+}
+extern "C" int vh_table_layouts(vh_table* t, vh_layout_info* out, uint32_t cap, uint32_t* n, vh_layout_summary* sum) {
+  if (!t) return vh_fail(VH_E_INVALID, "vh_table_layouts: null table");
+  if (!g_ctx.inited) return vh_fail(VH_E_INVALID, "vh_init has not been called");
+  if (!n || (cap && !out)) return vh_fail(VH_E_INVALID, "vh_table_layouts: null argument");
+  std::lock_guard<std::mutex> lk(t->mu);
+  std::vector<VhLayoutRef> refs;
+  layout_refs(t, &refs);
+  *n = (uint32_t)refs.size();
+  uint64_t pinned_bytes = 0;
+  for (size_t i = 0; i < refs.size(); ++i) {
+    const VhLayoutRef& v = refs[i];
+    if (v.L->pinned) pinned_bytes += v.bytes;
+    if (!out || i >= cap) continue;
+    vh_layout_info& o = out[i];
+    o = vh_layout_info{};
+    o.serial = v.L->serial; o.kind = v.kind;
+    const std::vector<int> one = v.nw ? std::vector<int>{v.nw->col} : std::vector<int>();
+    const std::vector<int>& cols = v.pk ? v.pk->cols : v.pp ? v.pp->cols : one;
+    o.ncols = (int32_t)cols.size();
+    for (size_t c = 0; c < cols.size() && c < VH_LAYOUT_COLS; ++c) o.cols[c] = cols[c];
+    o.bytes = v.bytes; o.grouped_bytes = v.grouped_bytes;
+    const VhGrouped* gr = v.pk ? v.pk->grouped.get() : nullptr;
+    o.flags = (v.L->automatic ? 1u : 0) | (v.L->pinned ? 2u : 0) | (v.L->applied_epoch == t->sync_epoch ? 4u : 0) | (v.pk && v.pk->compressed ? 8u : 0) |
+              (v.pk && v.pk->bits ? 16u : 0) | (gr && gr->rec.ptr ? 32u : 0) | (gr && gr->planes.ptr ? 64u : 0);
+    o.uses = v.L->uses; o.last_use = v.L->last_use;
+  }
+  if (sum) {
+    *sum = vh_layout_summary{};
+    sum->budget = t->layout_budget; sum->bytes = derived_bytes(t, VL_ALL); sum->pinned_bytes = pinned_bytes; sum->reserved_bytes = t->build_reserved;
+    sum->tick = t->use_tick; sum->evictions = t->evictions; sum->evicted_bytes = t->evicted_bytes; sum->declined = t->declined;
+  }
+  return VH_OK;
+}
+static bool layout_by_serial(vh_table* t, uint64_t serial, VhLayoutRef* out) {
+  std::vector<VhLayoutRef> refs;
+  layout_refs(t, &refs);
+  for (const VhLayoutRef& v : refs) if (v.L->serial == serial) { *out = v; return true; }
+  return false;
+}
+extern "C" int vh_table_layout_pin(vh_table* t, uint64_t serial, int32_t pinned) {
+  if (!t) return vh_fail(VH_E_INVALID, "vh_table_layout_pin: null table");
+  if (!g_ctx.inited) return vh_fail(VH_E_INVALID, "vh_init has not been called");
+  VH_ENTER();
+  std::lock_guard<std::mutex> lk(t->mu);
+  VhLayoutRef v;
+  if (!layout_by_serial(t, serial, &v)) return vh_fail(VH_E_INVALID, "vh_table_layout_pin: no layout %llu", (unsigned long long)serial);
+  v.L->pinned = pinned != 0;      // (unpinned over the budget, it is the next query's to evict: nothing leaves inside this call)
+  return VH_OK;
+}
+extern "C" int vh_table_layout_drop(vh_table* t, uint64_t serial) {
+  if (!t) return vh_fail(VH_E_INVALID, "vh_table_layout_drop: null table");
+  if (!g_ctx.inited) return vh_fail(VH_E_INVALID, "vh_init has not been called");
+  VH_ENTER();
+  std::lock_guard<std::mutex> lk(t->mu);
+  VhLayoutRef v;
+  if (!layout_by_serial(t, serial, &v)) return vh_fail(VH_E_INVALID, "vh_table_layout_drop: no layout %llu", (unsigned long long)serial);
+  layout_drop(t, v, false);
+  return VH_OK;
+}
+
 // WHERE the derived layouts lie. The same records and planes read by the same kernel take 1.07 or 1.23 ms per 1 B rows depending on the physical
 // pages they were given (profiles/r06/NOTES.md, "Placement": six execution contexts with six scratch allocations agree within 0.5 %, the
 // projection alone moved twenty-three times changes nothing, projection AND planes re-built behind 3 GB spacers spread over 15 % — all at
@@ -618,11 +812,6 @@ static bool device_room(size_t need) {
 struct VhMoved {       // an arena of derived_each's `kind` (the grouped headers stay: 32 bytes a tile), `plane` of its layout; `serial` and `applied_epoch` of the layout at the move
   int kind; uint64_t serial, applied_epoch; int plane; char* old_ptr; char* new_ptr; size_t bytes;
 };
-static size_t derived_bytes(vh_table* t, uint32_t which) {
-  size_t b = 0;
-  derived_each(t, which & 3u, [&](int, VhLayout&, int, VhBuf& buf) { b += buf.held; });
-  return b;
-}
 static int derived_move(vh_table* t, uint32_t which, std::vector<VhMoved>* moved) {      // (t->mu held)
   if (int irc = derived_idle(t)) return irc;
   int rc = VH_OK;

@@ -27,6 +27,7 @@ static int heavy_pass_enqueue(vh_result* r, VhHeavyRun& H) {
   g_heavy.tuples_of = H.from_tuples ? r : nullptr; g_heavy.epoch = r->launch_epoch;
   const int rc = query_launch_locked(t, H.x2, &H.p2, &H.r2, H.cap, true, 0, false, false, nullptr, nullptr, false, 0, true);
   g_heavy = VhHeavyCtx{};
+  if (g_plan_carry) { r->info.reserved |= 1u << 24; g_plan_carry = false; }      // (what the pass evicted is the query's to report)
   if (rc) H.r2 = nullptr; else H.r2->exec = H.x2;
   return rc;
 }
@@ -619,21 +620,37 @@ static int place_layouts(vh_table* t, const vh_plan* plan, vh_result_info* info_
 // query shape is first seen (src/codegen/compiler.cc:97-144, QueryStats::compile_time); a caller that knows its hot shapes at table-load
 // time runs them through here. The plan is executed (up to three times: a narrow copy, then a projection can appear) and
 // the last attempt's info is returned, so the caller sees what a steady-state query of this shape will run on.
+static int table_prepare(vh_table* t, const vh_plan* plan, vh_result_info* info_out);
+// What the prepared plan reads stays, whatever the budget: its queries pin every layout as they stamp it (layout_use, under the table lock, so no
+// query of another thread evicts it between two rounds). When the prepare ends, the pins it made itself are taken back where it failed or
+// where its last query no longer read the layout (a narrow copy a predicate projection replaced); what is unpinned then makes room.
 extern "C" int vh_table_prepare(vh_table* t, const vh_plan* plan, vh_result_info* info_out) {
   if (!t || !plan) return vh_fail(VH_E_INVALID, "null argument");
+  g_prepare_reads.clear(); g_prepare_pinned.clear();
+  const int rc = table_prepare(t, plan, info_out);
+  {
+    std::lock_guard<std::mutex> lk(t->mu);
+    VhLayoutRef v;
+    for (uint64_t serial : g_prepare_pinned)
+      if ((rc || std::find(g_prepare_reads.begin(), g_prepare_reads.end(), serial) == g_prepare_reads.end()) && layout_by_serial(t, serial, &v)) v.L->pinned = false;
+    derived_trim(t, false);
+  }
+  g_prepare_reads.clear(); g_prepare_pinned.clear();
+  return rc;
+}
+static int table_prepare(vh_table* t, const vh_plan* plan, vh_result_info* info_out) {
   (void)build_wait(t, 0, nullptr);      // (background build mode: a job of this table that is queued or running is joined, not duplicated)
   struct Guard { Guard() { g_preparing = true; } ~Guard() { g_preparing = false; } } guard;
   uint32_t last = ~0u;
   for (int round = 0; round < 3; ++round) {
     vh_result* r = nullptr;
     if (int rc = vh_query_agg(t, plan, &r)) return rc;
-    const uint32_t now = r->info.reserved;
+    const uint32_t now = r->info.reserved & ~(1u << 24);      // (whether the round evicted something is no property of the plan)
     if (info_out) *info_out = r->info;
     vh_result_free(r);
     if (now == last) break;
     last = now;
   }
-  if (last & (8u | 2048u)) return place_layouts(t, plan, info_out, 1000.0);
-  return VH_OK;
+  return last & (8u | 2048u) ? place_layouts(t, plan, info_out, 1000.0) : VH_OK;
 }
 

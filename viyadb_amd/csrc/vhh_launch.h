@@ -35,7 +35,12 @@ void QueryBuild::predpack_auto(bool want_sliced) {
   if (build_background(t)) { build_pending |= build_request_layout(t, VB_PREDPACK, pp_cols, sliced, true, key, p); return; }      // (the worker builds it and evaluates the guard)
   const size_t need = (size_t)t->cap_seg * t->padded_rows * 4;
   const size_t had = t->predpacks.size();
-  if (device_room(need)) { (void)table_predpack_locked(t, pp_cols, true, nullptr, sliced); t->inline_builds += t->predpacks.size() > had; }
+  uint64_t exact = 0;
+  if (t->layout_budget) {      // the budget is asked for the bytes the planes will really take (nothing to gain: nothing is built, nothing asked)
+    std::unique_ptr<VhPredPack> d;
+    if (predpack_describe(t, pp_cols, true, sliced, &d) == VH_OK && d) for (int q = 0; q < d->nplanes; ++q) exact += VhBuf::bytes(t->cap_seg, d->plane[q].stride);
+  }
+  if ((!exact || budget_room(exact)) && device_room(need)) { (void)table_predpack_locked(t, pp_cols, true, nullptr, sliced); t->inline_builds += t->predpacks.size() > had; }
   else t->ppred_seen[key] = 0;
 }
 
@@ -185,6 +190,7 @@ int QueryBuild::compile_kernel() {
     {   // which predicate projection, if any (shape_filter noted what exists): rows -> byte planes, everything else -> bit-sliced planes
       const bool rows_form = lanes || js.qpay != 0;
       const bool have_sliced = js.pp_sliced != 0, have_bytes = js.pp_nplanes != 0;
+      if (VhPredPack* settled = have_sliced && !rows_form && !(p->flags & VH_PLAN_NO_SLICED) ? sliced_use : have_bytes ? bytes_use : nullptr) layout_use(t, settled);
       if (have_sliced && !rows_form && !(p->flags & VH_PLAN_NO_SLICED)) { js.pp_nplanes = 0; for (int k = 0; k < js.npred; ++k) { js.pp_off[k] = pp_soff[k]; js.pp_bits[k] = pp_sbits[k]; } }
       else { js.pp_sliced = 0; js.pp_slot = -1; for (int k = 0; k < js.npred; ++k) { js.pp_off[k] = pp_boff[k]; js.pp_bits[k] = pp_bbits[k]; } }
       // (a plan with a set leaf reads rows whatever its form: the automatic builder is asked for byte planes, never for planes it cannot read)
@@ -829,6 +835,30 @@ static int query_launch_locked(vh_table* t, VhExec* x, const vh_plan* p, vh_resu
                                bool plan_only = false, VhSummary* summary_out = nullptr, const VhAgreed* ag = nullptr,
                                bool device_rows = false, uint32_t hp_passes_override = 0, bool no_hpart = false) {
   if (int src = sync_resolve(t)) return src;      // a batched sync may still be on its way: its rows and its share of the stats, before anything is planned
+  // One tick per query (a plan that starts over keeps it): what the layouts this plan reads are stamped with (layout_use). When the outermost
+  // call returns, a budget that a refresh pushed past — the table grew, a projection was rebuilt wider — is restored at the cost of layouts
+  // this plan does not read, and the result says whether anything was evicted on its behalf.
+  // A sharded query's summary pass and the heavy second pass of a hashed partitioning are further passes of ONE query: they take a tick of
+  // their own (what they hold is safe from their own builds) but count as no use, and what they evict is reported on the query's result.
+  struct Tick {
+    vh_table* t; vh_result** out; bool outer, further, was_unstamped;
+    Tick(vh_table* t_, vh_result** out_, bool further_) : t(t_), out(out_), outer(g_plan_depth++ == 0), further(further_), was_unstamped(g_plan_unstamped) {
+      if (!outer) return;
+      ++t->use_tick;
+      g_plan_evicted = g_plan_carry; g_plan_carry = false;
+      g_plan_unstamped = further;
+      if (g_preparing && !further) g_prepare_reads.clear();
+    }
+    ~Tick() {
+      --g_plan_depth;
+      if (!outer) return;
+      g_plan_unstamped = was_unstamped;
+      if (!t->layout_budget) return;
+      derived_trim(t, true);
+      if (further) g_plan_carry = g_plan_evicted;
+      else if (g_plan_evicted && out && *out) (*out)->info.reserved |= 1u << 24;
+    }
+  } tick(t, out, summary_out != nullptr || g_heavy.only != nullptr);
   QueryBuild b(t, x, p, out, hash_capacity_override, force_hash, part_tuples_override, no_part, plan_only, summary_out, ag, device_rows,
                hp_passes_override, no_hpart);
   int (QueryBuild::* const steps[])() = {&QueryBuild::shape_filter, &QueryBuild::snapshot_segments, &QueryBuild::shape_groups, &QueryBuild::shape_metrics,

@@ -122,3 +122,28 @@ static inline int vh_range_narrow_width(int elem, const VhRange& r) {
   if (elem != VH_U32 || r.empty()) return 0;
   return r.hi < 256 ? 1 : r.hi < 65536 ? 2 : 0;
 }
+
+// ---------------------------------------------------------------- which layouts leave when a byte budget is short (derived_make_room, vhh_derived.h)
+// One entry per layout: every arena it holds (a projection's grouped form counted with it), the table's query tick at the last plan that read
+// it (0: never), its serial, and whether it may leave at all — not pinned, and no plan of the current tick reads it.
+struct VhEvictEntry { uint64_t bytes, last_use, serial; bool evictable; };
+// The victims that free at least `deficit` bytes, as indices into `e`: the evictable entries by ascending (last_use, serial) — least recently
+// used first, the older layout first among equals — and of that order the shortest prefix that covers the deficit. false: impossible — every
+// evictable entry together frees less than the deficit; `victims` is then empty (nothing is evicted for a build that will not fit anyway).
+static inline bool vh_evict_pick(const VhEvictEntry* e, size_t n, uint64_t deficit, std::vector<size_t>* victims) {
+  victims->clear();
+  if (!deficit) return true;
+  std::vector<size_t> order;
+  for (size_t i = 0; i < n; ++i) if (e[i].evictable) order.push_back(i);
+  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+    return e[a].last_use != e[b].last_use ? e[a].last_use < e[b].last_use : e[a].serial != e[b].serial ? e[a].serial < e[b].serial : a < b;
+  });
+  uint64_t freed = 0;
+  for (size_t i : order) {
+    victims->push_back(i);
+    if (e[i].bytes >= deficit - freed) return true;      // (no sum that could wrap: what is still missing shrinks)
+    freed += e[i].bytes;
+  }
+  victims->clear();
+  return false;
+}

@@ -263,6 +263,9 @@ struct QueryBuild {
   int qpay = 0, qpay_slot = -1;                  // streamed payload (VhJitShape::qpay): the record's bytes, the slot the records come from
   VhPack* packed_use = nullptr;                  // the projection the plan gathers from, and the bit-sliced predicate projection shape_filter found:
   VhPredPack* sliced_use = nullptr;              // what choose_grouped pairs up
+  VhPredPack* bytes_use = nullptr;               // the byte-plane predicate projection shape_filter found (compile_kernel settles on one of the two forms and stamps it)
+  void hold_payload();                           // under a budget: the projections choose_projection may settle on are held before shape_filter's build site runs
+  bool budget_room(uint64_t need);               // an automatic build of `need` bytes fits the table's layout budget, after evictions if need be (false: declined, counted)
   bool grouped = false;                          // the records come from the projection's grouped form (vh_result_info.reserved bit 20)
   bool gplanes = false;                          // ... and the predicate bits from the clustered planes beside them (bit 21)
   void choose_grouped();                         // compile_kernel: point a qualifying plan at the grouped records (building them where the automatic layouts are built)
@@ -312,6 +315,23 @@ static int query_launch_locked(vh_table* t, VhExec* x, const vh_plan* p, vh_resu
                                bool force_hash, uint64_t part_tuples_override, bool no_part, bool plan_only, VhSummary* summary_out,
                                const VhAgreed* ag, bool device_rows, uint32_t hp_passes_override, bool no_hpart);
 
+void QueryBuild::hold_payload() {
+  if (!t->layout_budget) return;
+  for (auto& pk : t->packs) {      // (every projection that holds the plan's group and metric columns: one of them is what the plan will gather from)
+    bool all = true;
+    for (int i = 0; i < p->ngroups && all; ++i) all = pk->col_index(p->groups[i].col) >= 0;
+    for (int j = 0; j < p->nmetrics && all; ++j) {
+      const int c = p->metrics[j];
+      if (c >= 0 && (size_t)c < t->cols.size() && !is_bitset_elem(t->cols[c].elem)) all = pk->col_index(c) >= 0;
+    }
+    if (all) pk->held_tick = t->use_tick;
+  }
+}
+bool QueryBuild::budget_room(uint64_t need) {
+  if (g_preparing || derived_make_room(t, need)) return true;      // (vh_table_prepare is never refused for the budget: it trims when it ends)
+  ++t->declined;
+  return false;
+}
 int QueryBuild::slot(int col) {
   if (col < 0 || col >= ncols || col >= 256) return -1;
   if (slot_of[col] >= 0) return slot_of[col];
@@ -529,7 +549,11 @@ int QueryBuild::shape_filter() {
     if (!all_cols) pp_cols.clear();
     VhPredPack* pb = all_cols ? predpack_usable(t, pp_cols, 0) : nullptr;
     VhPredPack* ps = all_cols && !has_set ? predpack_usable(t, pp_cols, 1) : nullptr;      // (bit-serial comparisons cannot look a member up: a set leaf wants the row's value)
+    // (the plan holds pointers into both from here on: neither is a victim of the builds below, whichever form compile_kernel settles on)
+    if (pb) pb->held_tick = t->use_tick;
+    if (ps) ps->held_tick = t->use_tick;
     if (pb && P.nslots + pb->nplanes <= VH_MAX_SLOTS) {
+      bytes_use = pb;
       jshape.pp_nplanes = pb->nplanes;
       for (int q = 0; q < pb->nplanes; ++q) {
         P.colbase[P.nslots] = pb->plane[q].ptr; P.colstride[P.nslots] = pb->plane[q].stride; P.colpitch[P.nslots] = (uint32_t)pb->pwidth[q];
@@ -556,6 +580,7 @@ int QueryBuild::shape_filter() {
   // register-resident kernels — and the selectivity probe, which is one of them — stream those instead of the 4-byte arenas.
   if ((fast_ok || jit_try) && !(p->flags & VH_PLAN_NO_NARROW)) {
     const int auto_after = g_preparing ? 1 : knobs().auto_narrow;     // 0: never unasked
+    hold_payload();
     std::map<int, int> narrow_slot;          // column -> slot of its narrow copy (looked up, and counted, once per query)
     auto narrow_for = [&](int col) -> int {
       auto hit = narrow_slot.find(col);
@@ -567,12 +592,13 @@ int QueryBuild::shape_filter() {
       if (!have && auto_after > 0 && nwidth && !g_build_quiet && ++t->pred_seen[col] >= (uint32_t)auto_after) {
         const size_t need = (size_t)t->cap_seg * ((t->segment_rows + 255) / 256 * 256) * (size_t)nwidth;
         if (build_background(t)) build_pending |= build_request_layout(t, VB_NARROW, std::vector<int>{col}, false, true, std::string(), plan_only ? nullptr : p);      // (the worker builds it; the guard is its to evaluate)
-        else if (device_room(need)) { const size_t had = t->narrows.size(); (void)table_narrow_locked(t, col, true); t->inline_builds += t->narrows.size() > had; }
+        else if (budget_room(VhBuf::bytes(t->cap_seg, t->padded_rows * (uint64_t)nwidth)) && device_room(need)) { const size_t had = t->narrows.size(); (void)table_narrow_locked(t, col, true); t->inline_builds += t->narrows.size() > had; }
         else t->pred_seen[col] = 0;
       }
       int ns = -1;
       VhNarrow* nw = narrow_usable(t, col);
       if (nw && P.nslots < VH_MAX_SLOTS) {
+        layout_use(t, nw);
         P.colbase[P.nslots] = nw->copy.ptr; P.colstride[P.nslots] = nw->copy.stride; P.colpitch[P.nslots] = (uint32_t)nw->width;
         ns = P.nslots++;
       }
@@ -1366,7 +1392,13 @@ int QueryBuild::choose_projection() {
           uint32_t bytes = 0; for (int c : gcols) bytes += (uint32_t)t->cols[c].esize;
           uint32_t rec = 8; while (rec < bytes) rec <<= 1;
           const size_t need = (size_t)t->cap_seg * ((t->segment_rows + 255) / 256 * 256) * rec;
-          build = bytes <= 64 && need <= t->device_bytes && device_room(need);
+          build = bytes <= 64 && need <= t->device_bytes;
+          if (build && t->layout_budget) {      // the budget is asked for the bytes the records will really take (described from the stats, as the build will)
+            std::unique_ptr<VhPack> d;
+            const uint64_t exact = pack_describe(t, std::vector<int>(gcols.begin(), gcols.end()), true, jit_try && !knobs().pack_plain, &d) == VH_OK ? VhBuf::bytes(t->cap_seg, d->rec.stride) : need + 256;
+            build = budget_room(exact);
+          }
+          build = build && device_room(need);
           if (!build) t->gather_seen[sig] = 0;
         }
         if (build && table_pack_locked(t, gcols.data(), (int32_t)gcols.size(), !forced, &use, jit_try && !knobs().pack_plain) != VH_OK) use = nullptr;
@@ -1376,17 +1408,18 @@ int QueryBuild::choose_projection() {
     if (use) {
       rc = pack_refresh(t, use);   // on the table's main stream, complete when it returns
       if (rc == VH_PACK_STALE) {            // a synced value outgrew its stored width: rebuilt at the widths the values need now
-        const bool was_auto = use->automatic;
+        const bool was_auto = use->automatic, was_pinned = use->pinned;      // (the rebuild is what the dropped one was: automatic or asked for, pinned or not)
         pack_drop(t, use);
         use = nullptr;
-        if (build_background(t)) { if (!g_build_quiet) build_pending |= build_request_layout(t, VB_PACK, std::vector<int>(gcols.begin(), gcols.end()), true, was_auto, std::string("c:"), p); }
-        else { if (table_pack_locked(t, gcols.data(), (int32_t)gcols.size(), was_auto, &use, true) != VH_OK) use = nullptr; else ++t->inline_builds; }
+        if (build_background(t)) { if (!g_build_quiet) build_pending |= build_request_layout(t, VB_PACK, std::vector<int>(gcols.begin(), gcols.end()), true, was_auto, std::string("c:"), p, was_pinned); }
+        else { if (table_pack_locked(t, gcols.data(), (int32_t)gcols.size(), was_auto, &use, true) != VH_OK) use = nullptr; else { ++t->inline_builds; if (use) use->pinned = was_pinned; } }
         rc = VH_OK;
       }
       if (rc) { return rc; }
     }
     if (use && !want_gather && !forced && !(use->bits && use->rec_bytes == 4)) use = nullptr;      // (asked for to be streamed, and it cannot be: the arenas)
     if (use) {
+      layout_use(t, use);      // (its grouped form, if the plan takes it, is accounted with it)
       int pslot_of[256];
       for (int i = 0; i < 256; ++i) pslot_of[i] = -1;
       auto pslot = [&](int col) {

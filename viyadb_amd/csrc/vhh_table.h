@@ -53,6 +53,11 @@ struct VhLayout {
   uint64_t applied_epoch = 0;       // every change of the table's journal up to this epoch is in the arenas
   uint64_t serial = 0;              // vh_table::layout_serial when it was built: which layout this is (derived_settle; addresses get reused). A grouped form carries its projection's
   bool automatic = false;
+  // Lifetime under the table's byte budget (derived_make_room, vhh_derived.h). A grouped form is accounted with its projection: these stay 0 in it.
+  bool pinned = false;              // never evicted: built by an explicit call, read by a prepared plan, or pinned through vh_table_layout_pin
+  uint64_t uses = 0;                // plans that read the layout
+  uint64_t last_use = 0;            // vh_table::use_tick at the last of them (0: never)
+  uint64_t held_tick = 0;           // vh_table::use_tick of the last plan that took a pointer into the arenas, counted in `uses` or not (a quiet plan's is not): that plan evicts nothing it holds
 };
 // The GROUPED form of a 4-byte bit-record projection (vh_grouped.h, group_bits_kernel): a second copy of the records in which every tile of
 // 2048 rows is stable-sorted by the field a bit-sliced predicate projection keeps of column `col` (`bits` bits, at most VH_GROUP_MAX_BITS),
@@ -162,6 +167,11 @@ struct vh_table {
   uint64_t inline_builds = 0;      // compiles and layout builds that ran inside a query of this table
   std::map<std::string, uint64_t> build_nothing;   // background layout jobs that found nothing to gain -> the sync epoch they judged at (not queued again before the table changes)
   uint64_t arena_gen = 0;          // bumped whenever table_grow replaces the column arenas: a layout job that enqueued its kernels against the old ones starts over
+  // the derived layouts' byte budget (vhh_derived.h, derived_make_room)
+  uint64_t use_tick = 0;           // bumped once per planned query: what VhLayout::last_use is stamped with
+  uint64_t layout_budget = 0;      // bytes the derived layouts may hold together (0: no budget)
+  uint64_t build_reserved = 0;     // arenas of the background job between its step (a) and its publish or drop: real bytes that device_bytes does not hold yet
+  uint64_t evictions = 0, evicted_bytes = 0, declined = 0;      // layouts the budget evicted and their bytes; automatic builds it refused
 };
 static void build_arenas_moving(vh_table* t);              // (vhh_build.h) t->mu held: the arenas are about to be replaced — wait until no background job's kernels read them
 static void build_cancel_table(vh_table* t, bool forget);  // (vhh_build.h) t->mu NOT held: drop the table's queued jobs, wait for the running one
@@ -247,6 +257,7 @@ extern "C" int vh_table_create(const vh_col_desc* cols, int32_t ncols, uint64_t 
   t->segment_rows = segment_rows;
   t->padded_rows = (segment_rows + 63) / 64 * 64;
   t->build_mode = knobs().build_background ? VH_BUILD_BACKGROUND : VH_BUILD_INLINE;
+  t->layout_budget = knobs().layout_budget;
   t->cols.resize(ncols);
   t->stats.resize(ncols);
   for (int i = 0; i < ncols; ++i) {

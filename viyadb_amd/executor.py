@@ -206,6 +206,29 @@ class DeviceTable:
         capi.check(self.lib.vh_table_info(self.handle, C.byref(nseg), C.byref(srows), C.byref(dbytes)))
         return nseg.value, srows.value, dbytes.value
 
+    # ---- lifetime of the derived layouts (vh_table_set_layout_budget and its neighbours in include/viya_hip.h)
+    def set_layout_budget(self, nbytes: int) -> None:
+        """Bytes the derived layouts of this table may hold together (0: no budget). Lowering it evicts at once, least recently used first;
+        pinned layouts stay."""
+        capi.check(self.lib.vh_table_set_layout_budget(self.handle, int(nbytes)))
+
+    def layouts(self):
+        """(list of capi.LayoutInfo in ascending serial order, capi.LayoutSummary): what exists, what it costs and what is in use."""
+        n, summ = C.c_uint32(), capi.LayoutSummary()
+        capi.check(self.lib.vh_table_layouts(self.handle, None, 0, C.byref(n), None))
+        while True:
+            cap = n.value + 4          # (a background build may publish between the two calls)
+            arr = (capi.LayoutInfo * cap)()
+            capi.check(self.lib.vh_table_layouts(self.handle, arr, cap, C.byref(n), C.byref(summ)))
+            if n.value <= cap:
+                return [arr[i] for i in range(n.value)], summ
+
+    def pin_layout(self, serial: int, pinned: bool = True) -> None:
+        capi.check(self.lib.vh_table_layout_pin(self.handle, int(serial), 1 if pinned else 0))
+
+    def drop_layout(self, serial: int) -> None:
+        capi.check(self.lib.vh_table_layout_drop(self.handle, int(serial)))
+
     def segment_stats(self, seg: int, col: int):
         lo, hi = capi.AnyNum(), capi.AnyNum()
         capi.check(self.lib.vh_segment_stats(self.handle, seg, col, C.byref(lo), C.byref(hi)))
