@@ -124,8 +124,11 @@ enum vh_fkind {
                     and bitset metrics return VH_E_UNSUPPORTED (the caller keeps VH_F_IN). At most VH_MAX_SETS set leaves per plan
                     (VH_E_UNSUPPORTED beyond); a set's size is bounded by vh_plan.nlits alone (the 65535-literal limit of a filter counts REL / IN literals, not
                     set members); not valid in `having`, nor with count < 1 (VH_E_INVALID). The bit-sliced predicate planes,
-                    and the grouped records and clustered planes that rest on them, do not serve a plan with a set leaf: it reads byte
-                    planes, narrow copies or the columns. The library never rewrites a caller's VH_F_IN by itself.                      */
+                    and the grouped records and clustered planes that rest on them, serve a plan with set leaves when every such leaf's
+                    column is a field of at most 10 bits there (VH_INSET_TRUTH_BITS): the set is then a truth table of 2^bits bits,
+                    evaluated on 32 rows per lane with bitwise operations, whatever the list's length (vh_result_info.reserved bit 25).
+                    With a set leaf on a wider field the plan reads byte planes, narrow copies or the columns, one lookup per row. A set
+                    leaf is never the `==` leaf the grouped forms go by. The library never rewrites a caller's VH_F_IN by itself.        */
 };
 #define VH_MAX_SETS 4
 /* A plan whose REL / IN leaves carry more literals than this in all is answered by the generic (interpreting) scan kernel, one comparison
@@ -295,6 +298,8 @@ typedef struct vh_result_info {
                                         the run of the `==` literal in every tile (bit 20 is set too);
                                 bit 22: the filter's VH_F_INSET leaves were evaluated by set lookup;
                                 bit 23: ... at least one of them by binary search in a sorted array (the others, or all: one bit of a bitmap);
+                                bit 25: ... or, instead of a lookup per row, all of them from truth tables on the bit-sliced predicate planes
+                                        (bits 13 and 22 are set too; bit 23 still tells the form of the ordinary tables, which are uploaded all the same);
                                 bit 19: (VH_BUILD_BACKGROUND tables) a kernel compile or a layout build for this query's shape is queued or running:
                                         this query ran on what existed (the pre-built kernels, the arenas, layouts already there);
                                 bit 24: (tables with a layout budget) planning this query evicted at least one derived layout */

@@ -144,6 +144,7 @@ INFO_GROUPED_PAYLOAD = 1 << 20    # vh_result_info.reserved bit 20
 INFO_GROUPED_PLANES = 1 << 21     # vh_result_info.reserved bit 21
 INFO_INSET = 1 << 22              # vh_result_info.reserved bit 22: the filter's set leaves were evaluated by lookup
 INFO_INSET_SEARCH = 1 << 23       # ... bit 23: at least one of them by binary search in a sorted array
+INFO_INSET_SLICED = 1 << 25       # ... bit 25: all of them from truth tables on the bit-sliced predicate planes instead (no lookup per row)
 INFO_EVICTED = 1 << 24            # ... bit 24: planning this query evicted at least one derived layout (tables with a layout budget)
 
 

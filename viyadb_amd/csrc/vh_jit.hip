@@ -214,7 +214,12 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
           sst.push_back("(" + e + ")");
         } break;
         case VH_F_REL: sst.push_back(sliced_leaf(o, (int)o.op(), (int)o.lit())); break;
-        case VH_F_INSET: sst.push_back("vj_a_set_leaf_reads_rows_not_bit_planes"); break;      // (the planner never pairs the two: a compile error, not a wrong answer)
+        case VH_F_INSET: {        // the set's truth table over the field's planes (vh_inset.h): the text knows the field's bits and the set's index
+          const int p = (int)o.pslot(), k = (int)o.lit();
+          const std::string sn = vj_fmt("s%d", k);
+          lit_decl[sn] = "const uint32_t* " + sn + "|" + vj_fmt("%s(P.set[%d].truth)", sn.c_str(), k);
+          sst.push_back(vj_fmt(o.op() ? "vj_bits_inset<%d>(%s + %d, L.%s)" : "~vj_bits_inset<%d>(%s + %d, L.%s)", s.pp_bits[p], leaf_regs, leaf_base[p], sn.c_str()));
+        } break;
         default: {         // IN: OR of ==, NOT IN: AND of != (filter.cc:223-241)
           std::string e = o.op() ? "0u" : "~0u";
           for (int k = 0; k < (int)o.count(); ++k) e += std::string(o.op() ? " | " : " & ") + sliced_leaf(o, o.op() ? VH_OP_EQ : VH_OP_NE, (int)o.lit() + k);
@@ -263,7 +268,7 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
         } else if (o.kind() == VH_F_INSET) {       // membership in P.set[lit]: form, bounds and size are run-time data (vh_inset.h) — the text knows the element type only
           const int k = (int)o.lit();
           const std::string sn = vj_fmt("s%d", k);
-          if (!lit_decl.count(sn)) lit_decl[sn] = "VhSetDev " + sn + "|" + vj_fmt("%s(P.set[%d])", sn.c_str(), k);
+          if (!s.pp_sliced && !lit_decl.count(sn)) lit_decl[sn] = "VhSetDev " + sn + "|" + vj_fmt("%s(P.set[%d])", sn.c_str(), k);
           set_decl += vj_fmt("    const bool z%d = vj_inset<%s>(L.%s, %s);\n", nz, vj_ctype(ty), sn.c_str(), c.c_str());
           const std::string z = vj_fmt(o.op() ? "z%d" : "!z%d", nz);
           ++nz;
@@ -836,6 +841,16 @@ static bool vj_canonical(int which, VhJitShape* s) {
   if (depth != -1) {
     if (!vj_canonical(which, s)) return false;
     S.drain_depth = depth == -2 ? vh_jit_drain_depth(S) : vh_jit_rec_bytes(S) ? depth : 0;
+    return true;
+  }
+  // set leaves on the bit-sliced planes (vj_bits_inset: the set's truth table over the field's planes): 30 = case 14 with its d3 leaf as a set,
+  // 31 = case 22 (clustered planes) likewise, 32 = case 14 with a NOT-IN set on the 2-bit d2 field
+  if (which >= 30 && which <= 32) {
+    if (!vj_canonical(which == 31 ? 22 : 14, s)) return false;
+    const int leaf = which == 32 ? 0 : 1;
+    S.prog[(size_t)leaf] = vj_leaf(VH_F_INSET, VH_U32, which == 32 ? 0 : 1, leaf, 0, 0);
+    for (int k = 0, lit = 0; k < 3; ++k) if (k != leaf) S.prog[(size_t)k].set_lit((uint16_t)lit++);      // (members are not literals: set 0, two literals left)
+    S.nlits = 2;
     return true;
   }
   switch (which) {

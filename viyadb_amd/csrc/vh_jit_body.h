@@ -522,6 +522,10 @@ __device__ __forceinline__ uint32_t vj_bits_rel(const uint32_t* x, uint64_t c, b
     return OP == VH_OP_LT ? lt : OP == VH_OP_LE ? (lt | eq) : OP == VH_OP_GT ? ~(lt | eq) : ~lt;
   }
 }
+// A set leaf on a bit-sliced field of NB <= VH_INSET_TRUTH_BITS bits: the lane's 32 rows whose value is a member, from the set's truth table
+// (vh_inset.h: vh_inset_bits) — a look-up table over the planes, whatever the list's length. NOT IN is its complement.
+template <int NB>
+__device__ __forceinline__ uint32_t vj_bits_inset(const uint32_t* x, const uint32_t* truth) { return vh_inset_bits<NB>(x, truth); }
 // The lane's passing rows (bits of `m`, row `base` + bit) appended to the wave's queue: ranks from a prefix sum of the lanes' counts, then
 // every lane writes its own rows — as many rounds as the busiest lane has survivors. At most 1 024 rows a call (the queue's room).
 __device__ __forceinline__ void vj_push_mask(uint32_t* q, uint32_t& cnt, uint32_t m, uint32_t base, int lane) {

@@ -193,8 +193,10 @@ int QueryBuild::compile_kernel() {
       if (VhPredPack* settled = have_sliced && !rows_form && !(p->flags & VH_PLAN_NO_SLICED) ? sliced_use : have_bytes ? bytes_use : nullptr) layout_use(t, settled);
       if (have_sliced && !rows_form && !(p->flags & VH_PLAN_NO_SLICED)) { js.pp_nplanes = 0; for (int k = 0; k < js.npred; ++k) { js.pp_off[k] = pp_soff[k]; js.pp_bits[k] = pp_sbits[k]; } }
       else { js.pp_sliced = 0; js.pp_slot = -1; for (int k = 0; k < js.npred; ++k) { js.pp_off[k] = pp_boff[k]; js.pp_bits[k] = pp_bbits[k]; } }
-      // (a plan with a set leaf reads rows whatever its form: the automatic builder is asked for byte planes, never for planes it cannot read)
-      const bool want_rows = rows_form || has_set;
+      // (a plan with a set leaf reads bit planes only where every set's field is narrow enough for a truth table — by the columns' recorded
+      // ranges, as the builder would size the fields; otherwise it reads rows whatever its form: the automatic builder is asked for byte
+      // planes, never for planes the plan cannot read)
+      const bool want_rows = rows_form || (has_set && !sets_fit_planes([&](int col) { return predpack_bits_for(t, col); }));
       if (!(p->flags & (VH_PLAN_NO_NARROW | VH_PLAN_NO_PREDPACK)) && (want_rows ? !have_bytes : !have_sliced)) predpack_auto(!want_rows);
     }
     {   // (the records' registers count against the packed predicate registers' budget)
@@ -754,7 +756,7 @@ int QueryBuild::launch() {
   if (jk) { narrowed = jshape.pp_nplanes || jshape.pp_sliced; for (int k = 0; k < jshape.npred; ++k) narrowed |= jshape.pred[k].width != vh_elem_size(jshape.pred[k].type); }
   r->hpart = hpart;
   r->info.reserved = (hpart ? 64 : 0) | (fastj || jk ? 1 : 0) | (lanes ? 2 : 0) | (P.lds_hash_slots ? 4 : 0) | (packed ? 8 : 0) | (fastj && narrowed ? 16 : 0) | (jk ? 32 : 0) | (packed && packed_compressed ? 128 : 0) | (hpart && hp_pack ? 256 : 0) | (mode == VH_MODE_DENSE_PART && P.gid_bits ? 1024 : 0) | (jk && (jshape.pp_nplanes || jshape.pp_sliced) ? 2048 : 0) | (jk && jshape.qpay ? 4096 : 0) | (jk && jshape.pp_sliced ? 8192 : 0) | (mode == VH_MODE_DENSE_PART && P.gid_bits && P.tuple4 ? 16384 : 0)
-                   | (has_set ? 1u << 22 : 0) | (has_set && set_search ? 1u << 23 : 0) | (build_pending ? 1u << 19 : 0) | (jk && grouped ? 1u << 20 : 0) | (jk && grouped && gplanes ? 1u << 21 : 0) | (packed && packed_bits ? 32768 : 0) | (packed ? (uint32_t)(31 - __builtin_clz(std::max<uint32_t>(packed_rec, 2)) - 1) << 16 : 0);
+                   | (has_set ? 1u << 22 : 0) | (has_set && set_search ? 1u << 23 : 0) | (jk && has_set && set_truth && jshape.pp_sliced ? 1u << 25 : 0) | (build_pending ? 1u << 19 : 0) | (jk && grouped ? 1u << 20 : 0) | (jk && grouped && gplanes ? 1u << 21 : 0) | (packed && packed_bits ? 32768 : 0) | (packed ? (uint32_t)(31 - __builtin_clz(std::max<uint32_t>(packed_rec, 2)) - 1) << 16 : 0);
   if (r->hp_chunks) memset(x->h_chunk, 0, VH_HP_CHUNKS * sizeof(unsigned long long));      // (what the context's previous query left there)
   // a second pass over heavy level-A partitions of a hashed partitioning: from the first pass's tuples when this plan's table can take them as
   // they are (one key word laid out as the first pass's, narrow ids) — else from the table's rows behind the bitmap, like any heavy range

@@ -224,6 +224,15 @@ struct QueryBuild {
   uint64_t bytes_per_row = 0;
   bool fast_ok = false;
   bool has_set = false, set_search = false;            // the filter has VH_F_INSET leaves (r->h_sets); at least one of them in the sorted-array form
+  bool set_truth = false;                              // ... and each has its truth table over its field of the bit-sliced projection noted in jshape (vh_inset_truth_build)
+  template <typename F> bool sets_fit_planes(F bits_of_col) const {      // every set leaf's column is a bit-sliced field of at most VH_INSET_TRUTH_BITS bits (bits_of_col: 0 = no field)
+    for (const VhProgOp& o : jshape.prog) {
+      if (o.kind() != VH_F_INSET) continue;
+      const int col = (int)o.pslot() < jshape.npred ? jit_pred_col[o.pslot()] : -1, b = col >= 0 ? bits_of_col(col) : 0;
+      if (b < 1 || b > VH_INSET_TRUTH_BITS) return false;
+    }
+    return true;
+  }
   int pred_col[VH_MAX_PRED] = {-1, -1, -1, -1};        // table column behind predicate slot k of the register-resident kernels
   int pred_wide_slot[VH_MAX_PRED] = {-1, -1, -1, -1};  // its 4-byte arena's slot when the plan was pointed at a narrow copy
   VhJitShape jshape;
@@ -548,7 +557,10 @@ int QueryBuild::shape_filter() {
     pp_cols.erase(std::unique(pp_cols.begin(), pp_cols.end()), pp_cols.end());
     if (!all_cols) pp_cols.clear();
     VhPredPack* pb = all_cols ? predpack_usable(t, pp_cols, 0) : nullptr;
-    VhPredPack* ps = all_cols && !has_set ? predpack_usable(t, pp_cols, 1) : nullptr;      // (bit-serial comparisons cannot look a member up: a set leaf wants the row's value)
+    VhPredPack* ps = all_cols ? predpack_usable(t, pp_cols, 1) : nullptr;
+    // (bit-serial comparisons cannot look a member up: a set leaf on bit planes is a truth table over its field, 2^bits bits of it — narrow fields
+    // only; a plan with a set leaf on a wider one wants the row's value: byte planes, narrow copies, arenas)
+    if (ps && has_set && !sets_fit_planes([&](int col) { const size_t at = (size_t)(std::find(ps->cols.begin(), ps->cols.end(), col) - ps->cols.begin()); return at < ps->cols.size() ? (int)ps->bitw[at] : 0; })) ps = nullptr;
     // (the plan holds pointers into both from here on: neither is a victim of the builds below, whichever form compile_kernel settles on)
     if (pb) pb->held_tick = t->use_tick;
     if (ps) ps->held_tick = t->use_tick;
@@ -573,6 +585,10 @@ int QueryBuild::shape_filter() {
         const size_t at = (size_t)(std::find(ps->cols.begin(), ps->cols.end(), jit_pred_col[k]) - ps->cols.begin());
         pp_soff[k] = ps->bitoff[at]; pp_sbits[k] = ps->bitw[at];
       }
+      // the sets' truth tables over these fields, behind their ordinary tables (which every other form of the scan, the probe and the
+      // interpreting kernels still read): built here, once per query from the projection as it is now, before the plan block is sized
+      for (const VhProgOp& o : jshape.prog) if (o.kind() == VH_F_INSET) vh_inset_truth_build((int)o.type(), pp_sbits[o.pslot()], &r->h_sets[o.lit()]);
+      set_truth = has_set;
       jit_predpack = true;
     }
   }

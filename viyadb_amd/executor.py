@@ -97,6 +97,7 @@ class AggResult:
     grouped_planes: bool = False   # ... and the predicate bits read from the planes clustered in the same order (the literal's run of every tile only)
     inset: bool = False            # the filter's "inset" leaves were evaluated by set lookup
     inset_search: bool = False     # ... at least one of them by binary search in a sorted array (the others: one bit of a bitmap)
+    inset_sliced: bool = False     # ... or, instead, all of them from truth tables on the bit-sliced predicate planes (no lookup per row)
 
 
 
@@ -418,7 +419,8 @@ class DeviceTable:
                          bool(info.reserved & 16384), bool(info.reserved & 32768),
                          (2 << ((info.reserved >> 16) & 7)) if info.reserved & 8 else 0,
                          bool(info.reserved & capi.INFO_GROUPED_PAYLOAD), bool(info.reserved & capi.INFO_GROUPED_PLANES),
-                         bool(info.reserved & capi.INFO_INSET), bool(info.reserved & capi.INFO_INSET_SEARCH))
+                         bool(info.reserved & capi.INFO_INSET), bool(info.reserved & capi.INFO_INSET_SEARCH),
+                         bool(info.reserved & capi.INFO_INSET_SLICED))
 
     def query_agg(self, plan: AggPlan, copy: bool = True) -> AggResult:
         p, keep = self._build_plan(plan)
