@@ -629,7 +629,16 @@ VH_API int vh_query_agg_sharded(vh_table* t, const vh_plan* plan, vh_comm* comm,
  * column's own element type; a bitset column yields its per-row cardinality as u64).
  * Formatting stays with the caller. `limit` 0 = none. The reference's `break` leaves the tuple
  * loop only, so after the limit is reached each later segment still contributes its first
- * passing row; that is reproduced. */
+ * passing row; that is reproduced.
+ *
+ * The filter is evaluated twice, once to count the passing rows per chunk and once to emit those inside the window. Both passes read the
+ * column arenas, one compare per row and literal — or, when every leaf's column is a field of ONE usable bit-sliced predicate projection
+ * (vh_table_predpack_ex(.., VH_PREDPACK_SLICED)), the program fits the inline budget (VH_PLAN_INLINE_LITS literals), every VH_F_INSET leaf's
+ * field has at most 10 bits and none of VH_PLAN_NO_SLICED / VH_PLAN_NO_PREDPACK / VH_PLAN_NO_NARROW is set, that projection's planes:
+ * the program interpreted bit-serially on 32 rows per lane by pre-built kernels. Nothing is compiled, so VH_JIT, VH_PLAN_NO_JIT and
+ * VH_JIT_MIN_ROWS do not bear on the choice. The select stamps the projection it reads like an aggregate does (vh_layout_info.uses) and
+ * holds it against eviction while it runs; it never builds or queues a layout. The rows are the same either way; vh_rows_flags tells which
+ * kernels ran. */
 #define VH_COL_ROWID (-2)
 typedef struct vh_rows vh_rows;
 typedef struct vh_select_plan {
@@ -653,6 +662,10 @@ VH_API int vh_query_select(vh_table* t, const vh_select_plan* plan, vh_rows** ou
  * global count on root and 0 elsewhere. */
 VH_API int vh_query_select_sharded(vh_table* t, const vh_select_plan* plan, vh_comm* comm, int32_t root, vh_rows** out);
 VH_API int vh_rows_get_info(vh_rows* r, vh_rows_info* info);
+/* Which kernels answered the select, in the bits of vh_result_info.reserved: bits 4, 11 and 13 when the filter was read off the bit-sliced
+ * predicate planes (bits 22 and 25 too when it has VH_F_INSET leaves: their truth tables); otherwise bit 22, and bit 23 where it applies,
+ * for set leaves looked up per row; bit 24 as for an aggregate. After vh_query_select_sharded: this rank's path. */
+VH_API int vh_rows_flags(vh_rows* r, uint32_t* flags);
 /* cols[c] = host array (pinned, owned by the vh_rows) of nrows elements of column c. */
 VH_API int vh_rows_view(vh_rows* r, const void** cols);
 VH_API void vh_rows_free(vh_rows* r);

@@ -232,6 +232,7 @@ SYMBOLS = {
     "vh_query_select": (C.c_int, [_VP, C.POINTER(SelectPlan), C.POINTER(_VP)]),
     "vh_query_select_sharded": (C.c_int, [_VP, C.POINTER(SelectPlan), _VP, C.c_int32, C.POINTER(_VP)]),
     "vh_rows_get_info": (C.c_int, [_VP, C.POINTER(RowsInfo)]),
+    "vh_rows_flags": (C.c_int, [_VP, C.POINTER(C.c_uint32)]),
     "vh_rows_view": (C.c_int, [_VP, C.POINTER(_VP)]),
     "vh_rows_free": (None, [_VP]),
     "vh_result_get_info": (C.c_int, [_VP, C.POINTER(ResultInfo)]),

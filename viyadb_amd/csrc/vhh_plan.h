@@ -522,7 +522,10 @@ int QueryBuild::shape_filter() {
   // ---------------- per-query compiled scan kernel (vh_jit.hip): which predicate columns it would hold packed in registers
   // Eligible so far: every leaf compares a fixed-width column, the program and its literals fit the kernel arguments, the packed
   // columns fit VJ_MAX_NV registers. The table organisation decides the rest further down.
-  jit_try = vh_jit_policy() != VH_JIT_OFF && !(p->flags & (VH_PLAN_NO_JIT | VH_PLAN_NO_FAST)) && prog.size() <= VH_INLINE_PROG && r->h_lits.size() <= VH_INLINE_LITS;
+  // A select (plan_only) compiles nothing: it takes this shape only to find the bit-sliced projection its pre-built kernels interpret the
+  // program on (snapshot_segments), so neither the JIT policy nor the plan's JIT flags bear on it.
+  const bool jit_allowed = vh_jit_policy() != VH_JIT_OFF && !(p->flags & (VH_PLAN_NO_JIT | VH_PLAN_NO_FAST));
+  jit_try = (jit_allowed || plan_only) && prog.size() <= VH_INLINE_PROG && r->h_lits.size() <= VH_INLINE_LITS;
   if (jit_try) {
     jshape.prog = prog;
     int nv = 0;
@@ -594,7 +597,9 @@ int QueryBuild::shape_filter() {
   }
   // Narrow copies of predicate columns (vh_table_narrow; built unasked for a column the third query filters on): the
   // register-resident kernels — and the selectivity probe, which is one of them — stream those instead of the 4-byte arenas.
-  if ((fast_ok || jit_try) && !(p->flags & VH_PLAN_NO_NARROW)) {
+  const bool jit_cols = jit_try && jit_allowed;      // (a select under VH_JIT=off counts towards and takes the narrow copies it did before it looked for planes)
+  jit_predpack &= jit_allowed;
+  if ((fast_ok || jit_cols) && !(p->flags & VH_PLAN_NO_NARROW)) {
     const int auto_after = g_preparing ? 1 : knobs().auto_narrow;     // 0: never unasked
     hold_payload();
     std::map<int, int> narrow_slot;          // column -> slot of its narrow copy (looked up, and counted, once per query)
@@ -628,7 +633,7 @@ int QueryBuild::shape_filter() {
         P.pred_slot[k] = (uint8_t)ns;
         P.pred_width[k] = (uint8_t)P.colpitch[ns];
       }
-    if (jit_try)      // (with a predicate projection at hand these are the fallback of the kernel forms it does not serve: existing copies only, see narrow_for)
+    if (jit_cols)     // (with a predicate projection at hand these are the fallback of the kernel forms it does not serve: existing copies only, see narrow_for)
       for (int k = 0; k < jshape.npred; ++k) {
         if (jit_pred_col[k] < 0 || t->cols[jit_pred_col[k]].elem != VH_U32) continue;
         const int ns = narrow_for(jit_pred_col[k]);
@@ -670,6 +675,31 @@ int QueryBuild::snapshot_segments() {
   if (jit_try && !(p->flags & VH_PLAN_FORCE_JIT) && vh_jit_policy() != VH_JIT_FORCE && (ag ? ag->rows_max : rows_to_scan) < vh_jit_min_rows()) jit_try = false;
   if (plan_only) {   // vh_query_select: filter program, column slots and the segment snapshot are all it shares
     P.nseg = nseg;
+    // Every leaf a field of one usable bit-sliced projection (shape_filter found it: the program and its literals fit the kernel arguments, every
+    // set leaf's field has a truth table), a filter to evaluate, none of the flags that keep a plan off the planes: the select reads the planes
+    // (select_count_sliced_kernel / select_emit_sliced_kernel). It stamps the projection like an aggregate that settled on it; it builds nothing.
+    if (sliced_use && p->nfilter > 0 && !(p->flags & (VH_PLAN_NO_SLICED | VH_PLAN_NO_PREDPACK | VH_PLAN_NO_NARROW))) {
+      VhBitsProg& B = r->sel_prog;
+      B = VhBitsProg{};
+      B.nprog = (int32_t)jshape.prog.size(); B.flat = P.prog_flat;
+      bool ok = true;
+      for (size_t k = 0; k < jshape.prog.size(); ++k) {
+        const VhProgOp& o = jshape.prog[k];
+        const bool leaf = o.kind() == VH_F_REL || o.kind() == VH_F_IN || o.kind() == VH_F_INSET;
+        const int ps = leaf ? (int)o.pslot() : 0;
+        if (leaf) ok &= o.type() <= VH_I64 && pp_sbits[ps] >= 1 && pp_sbits[ps] <= VH_BITS_MAX_FIELD;
+        B.op[k] = vh_bits_op(o.kind(), o.type(), o.op(), o.count(), o.lit(), leaf ? (uint32_t)pp_soff[ps] : 0u, leaf ? (uint32_t)pp_sbits[ps] : 0u);
+      }
+      std::copy(r->h_lits.begin(), r->h_lits.end(), B.lits);
+      if (ok) {
+        r->sel_sliced = true;
+        r->sel_planes = sliced_use->plane[0].ptr; r->sel_stride = sliced_use->plane[0].stride; r->sel_pitch = sliced_use->pitch;
+        layout_use(t, sliced_use);
+      }
+    }
+    // what ran, in vh_result_info.reserved's bits (vh_rows_flags)
+    r->info.reserved = r->sel_sliced ? (1u << 4 | 1u << 11 | 1u << 13 | (has_set ? 1u << 22 | 1u << 25 : 0u))
+                                     : (has_set ? 1u << 22 | (set_search ? 1u << 23 : 0u) : 0u);
     r->info.algorithmic_bytes = rows_to_scan * bytes_per_row;
     *out = holder.release();
     done = true;

@@ -99,6 +99,11 @@ struct vh_result {
     for (size_t k = 0; k < h_sets.size(); ++k) d[k] = h_sets[k].dev(block + set_word[k] * 4);
     return reinterpret_cast<const VhSetDev*>(block + set_desc_word * 4);
   }
+  // a plan-only call (vh_query_select) whose filter can be read off a bit-sliced predicate projection: the program over its planes and where
+  // they lie (VhSelectSliced, vh_small_kernels.h; `set` is filled in once the plan block has its place). The projection is stamped and held.
+  bool sel_sliced = false;
+  VhBitsProg sel_prog{};
+  const char* sel_planes = nullptr; uint64_t sel_stride = 0, sel_pitch = 0;
   std::vector<int> filter_bitset_cols;         // bitset metrics the filter compares the cardinality of (VhPlanDev::fbs_offs order)
   bool device_rows = false;                    // emitted rows must (also) exist in device memory: they are exchanged or gathered next
   VhExec* exec = nullptr;                      // owned from launch to vh_result_free: stream, scratch (device-side state), staging (host view)

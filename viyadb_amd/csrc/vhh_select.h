@@ -3,6 +3,7 @@
 // ----------------------------------------------------------------- select (ordered row emission)
 struct vh_rows {
   vh_rows_info info{};
+  uint32_t flags = 0;           // which kernels answered, in vh_result_info.reserved's bits (vh_rows_flags)
   std::vector<int> elem;
   std::vector<size_t> off;
   char* d_out = nullptr;
@@ -15,6 +16,12 @@ extern "C" void vh_rows_free(vh_rows* r) { if (r) { VH_ENTER(); delete r; } }
 extern "C" int vh_rows_get_info(vh_rows* r, vh_rows_info* info) {
   if (!r || !info) return vh_fail(VH_E_INVALID, "null argument");
   *info = r->info;
+  return VH_OK;
+}
+
+extern "C" int vh_rows_flags(vh_rows* r, uint32_t* flags) {
+  if (!r || !flags) return vh_fail(VH_E_INVALID, "null argument");
+  *flags = r->flags;
   return VH_OK;
 }
 
@@ -35,6 +42,9 @@ struct VhSelectScan {
   char* S = nullptr;
   size_t o_win = 0, o_sel = 0, o_bs[VH_MAX_SELECT] = {};
   const uint32_t* d_counts = nullptr;
+  const unsigned long long* d_totals = nullptr;
+  bool sliced = false;                        // the filter is read off the bit-sliced predicate planes (QueryBuild::snapshot_segments decides): A, not P
+  VhSelectSliced A{};
   std::vector<unsigned long long> totals;     // passing rows per segment
   VhSelectDev D{};
 };
@@ -57,7 +67,9 @@ static int select_count_locked(vh_table* t, VhExec* x, const vh_select_plan* sp,
   if (int frc = derived_fence(t, st)) return frc;
   if (nseg == 0) return VH_OK;
 
-  const uint32_t cps = s->cps = (uint32_t)((t->padded_rows + VH_WAVE_STEP_ROWS - 1) / VH_WAVE_STEP_ROWS);
+  const bool sliced = s->sliced = pr->sel_sliced;
+  const uint32_t chunk_rows = sliced ? VH_SLICED_CHUNK_ROWS : VH_WAVE_STEP_ROWS;
+  const uint32_t cps = s->cps = (uint32_t)((t->padded_rows + chunk_rows - 1) / chunk_rows);
   const uint64_t nchunks = (uint64_t)nseg * cps;
   ScratchPlan spn;
   const size_t o_ctr = spn.take(256), o_segrows = spn.take(pr->plan_words * 4), o_counts = spn.take(nchunks * 4),
@@ -88,9 +100,17 @@ static int select_count_locked(vh_table* t, VhExec* x, const vh_select_plan* sp,
   uint32_t* d_counts = reinterpret_cast<uint32_t*>(S + o_counts);
   s->d_counts = d_counts;
   unsigned long long* d_totals = reinterpret_cast<unsigned long long*>(S + o_totals);
+  s->d_totals = d_totals;
   s->grid = (unsigned)std::min<uint64_t>((nchunks + 3) / 4, (uint64_t)g_ctx.num_cu * 8);
+  if (sliced) {
+    VhSelectSliced& A = s->A;
+    A.B = pr->sel_prog; A.B.set = P.set;
+    A.planes = pr->sel_planes; A.stride = pr->sel_stride; A.pitch = pr->sel_pitch;
+    A.seg_rows = P.seg_rows; A.counters = P.counters; A.nseg = nseg;
+  }
   HIP_TRY(hipEventRecord(x->ev[1], st));
-  hipLaunchKernelGGL(select_count_kernel, dim3(s->grid), dim3(256), 0, st, P, cps, d_counts);
+  if (sliced) hipLaunchKernelGGL(select_count_sliced_kernel, dim3(s->grid), dim3(256), 0, st, s->A, cps, d_counts);
+  else hipLaunchKernelGGL(select_count_kernel, dim3(s->grid), dim3(256), 0, st, P, cps, d_counts);
   hipLaunchKernelGGL(select_scan_kernel, dim3(nseg), dim3(256), 0, st, d_counts, cps, d_totals);
   HIP_TRY(hipGetLastError());
   s->totals.assign(nseg, 0);
@@ -130,7 +150,7 @@ static size_t select_layout(const std::vector<int>& elem, uint64_t nrows, std::v
   return bytes;
 }
 
-// Emission of the rows inside the windows `win` (one per segment of s) into out[c] + out_base: select_emit_kernel.
+// Emission of the rows inside the windows `win` (one per segment of s) into out[c] + out_base: select_emit_kernel, or its form over the planes.
 static int select_emit_locked(vh_table* t, VhExec* x, const vh_select_plan* sp, VhSelectScan* s, const VhSelectWindow* win,
                               const std::vector<int>& elem, char* const* out) {
   hipStream_t st = x->stream();
@@ -152,8 +172,12 @@ static int select_emit_locked(vh_table* t, VhExec* x, const vh_select_plan* sp, 
   }
   HIP_TRY(hipMemcpyAsync(S + s->o_sel, &D, sizeof(D), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(S + s->o_win, win, (size_t)nseg * sizeof(VhSelectWindow), hipMemcpyHostToDevice, st));
-  hipLaunchKernelGGL(select_emit_kernel, dim3(s->grid), dim3(256), 0, st, s->P, s->cps, s->d_counts,
-                     reinterpret_cast<const VhSelectWindow*>(S + s->o_win), reinterpret_cast<const VhSelectDev*>(S + s->o_sel));
+  if (s->sliced)
+    hipLaunchKernelGGL(select_emit_sliced_kernel, dim3(s->grid), dim3(256), 0, st, s->A, s->cps, s->d_counts, s->d_totals,
+                       reinterpret_cast<const VhSelectWindow*>(S + s->o_win), reinterpret_cast<const VhSelectDev*>(S + s->o_sel));
+  else
+    hipLaunchKernelGGL(select_emit_kernel, dim3(s->grid), dim3(256), 0, st, s->P, s->cps, s->d_counts,
+                       reinterpret_cast<const VhSelectWindow*>(S + s->o_win), reinterpret_cast<const VhSelectDev*>(S + s->o_sel));
   HIP_TRY(hipGetLastError());
   return VH_OK;
 }
@@ -174,6 +198,7 @@ extern "C" int vh_query_select(vh_table* t, const vh_select_plan* sp, vh_rows** 
   std::unique_ptr<vh_rows> rows(new vh_rows());
   rows->info.scanned_recs = s.pr->info.scanned_recs;
   rows->info.scanned_segments = s.pr->info.scanned_segments;
+  rows->flags = s.pr->info.reserved;
   for (int c = 0; c < sp->ncols; ++c) rows->elem.push_back(is_bitset_elem(t->cols[sp->cols[c]].elem) ? VH_U64 : t->cols[sp->cols[c]].elem);
   rows->off.assign(sp->ncols, 0);
   if (nseg == 0) { *out = rows.release(); return VH_OK; }
@@ -269,6 +294,7 @@ extern "C" int vh_query_select_sharded(vh_table* t, const vh_select_plan* sp, vh
   std::unique_ptr<vh_rows> rows(new vh_rows());
   rows->info.scanned_recs = scanned; rows->info.scanned_segments = scanned_segs; rows->info.passed_recs = passed;
   rows->info.nrows = R == root ? output_recs : 0;
+  rows->flags = s.pr ? s.pr->info.reserved : 0u;        // (this rank's: the ranks need not agree on the path)
   for (int c = 0; c < sp->ncols; ++c) rows->elem.push_back(is_bitset_elem(t->cols[sp->cols[c]].elem) ? VH_U64 : t->cols[sp->cols[c]].elem);
   rows->off.assign(sp->ncols, 0);
   if (output_recs == 0 || sp->ncols == 0) {                   // (the same on every rank: nothing to move)

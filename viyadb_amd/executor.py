@@ -440,6 +440,19 @@ class DeviceTable:
         capi.check(self.lib.vh_query_select(self.handle, C.byref(sp), C.byref(rows)))
         return self._collect_rows(rows, cols)
 
+    def query_select_ex(self, filter: Sequence, cols: Sequence[int], skip: int = 0, limit: int = 0,
+                        seg_rows: Optional[Sequence[int]] = None, flags: int = 0):
+        """-> ([one numpy array per selected column], RowsInfo, flags): query_select, and vh_rows_flags — which kernels answered, in
+        the bits of vh_result_info.reserved (bit 13: the filter was read off the bit-sliced predicate planes)."""
+        sp, keep = self._select_plan(filter, cols, skip, limit, seg_rows, flags)
+        rows = C.c_void_p()
+        capi.check(self.lib.vh_query_select(self.handle, C.byref(sp), C.byref(rows)))
+        path = C.c_uint32()
+        rc = self.lib.vh_rows_flags(rows, C.byref(path))
+        out, info = self._collect_rows(rows, cols)      # (frees the rows)
+        capi.check(rc)
+        return out, info, int(path.value)
+
     def _select_plan(self, filter, cols, skip, limit, seg_rows, flags):
         p, keep = self._build_plan(AggPlan(filter=filter, seg_rows=seg_rows, flags=flags))
         sp = capi.SelectPlan()

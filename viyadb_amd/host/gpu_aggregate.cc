@@ -484,6 +484,9 @@ void GpuSelect(SelectQuery& query, RowOutput& output, QueryStats& stats, std::ve
     stats.passed_recs = info.passed_recs;
     stats.scan_kernel_ms = info.kernel_ms;
     stats.device_total_ms = info.total_ms;
+    uint32_t path = 0;      // which kernels answered (bit 13: the filter was read off the bit-sliced predicate planes)
+    vh_check(vh_rows_flags(rows, &path));
+    stats.device_flags = path;
     nrows = info.nrows;
     std::vector<const void*> ptrs(cols.size() + 1, nullptr);
     vh_check(vh_rows_view(rows, ptrs.data()));
