@@ -2,7 +2,8 @@
 group is sunk) against the same plan with VH_TEST_DRAIN_DEPTH=0 (one drain after another), alternating, `rounds` times; per leg and
 round the median, min and max of the kernel time (scan + phase 2) of 20 queries. The legs must have run different code objects (the
 kernel's name carries the shape's hash, and the depth is part of the shape): anything else is an error.
-A second test knob can be swept the same way (the resident-block cap: `VH_TEST_BLOCKS_PER_CU 3,4,5`); "default" leaves the knob unset.
+A second test knob can be swept the same way (the resident-block cap: `VH_TEST_BLOCKS_PER_CU 3,4,5`; the wave scans as shuffles:
+`VH_JIT_FLAGS -DVH_WAVE_SCAN_SHFL=1,default`); "default" leaves the knob unset.
 usage: python tools/drain_ab.py [segments=1000] [rounds=3] [knob=VH_TEST_DRAIN_DEPTH] [values=0,default]"""
 import json, os, sys, time
 os.environ["VH_TEST_HOOKS"] = "1"            # the gate in front of the library's test hooks (viya_hip.hip test_env)
@@ -33,7 +34,7 @@ for rnd in range(rounds):
         kernels[v] = r.kernel
         med[v].append(ks[len(ks) // 2])
         print(json.dumps({"round": rnd, knob: v, "kernel_ms": round(ks[len(ks) // 2], 4), "kernel_ms_min": round(ks[0], 4), "kernel_ms_max": round(ks[-1], 4),
-                          "spread": round(ks[-1] - ks[0], 4), "wall_ms": round(ws[len(ws) // 2], 4), "passed": r.passed_recs, "ngroups": r.ngroups, "kernel": r.kernel}), flush=True)
+                          "spread": round(ks[-1] - ks[0], 4), "wall_ms": round(ws[len(ws) // 2], 4), "wall_ms_min": round(ws[0], 4), "wall_ms_max": round(ws[-1], 4), "passed": r.passed_recs, "ngroups": r.ngroups, "kernel": r.kernel}), flush=True)
 os.environ.pop(knob, None)
 print(json.dumps({"knob": knob, "kernels": kernels, "median_ms": {v: [round(x, 4) for x in med[v]] for v in values}}), flush=True)
 if knob == "VH_TEST_DRAIN_DEPTH" and len(set(kernels.values())) != len(values):

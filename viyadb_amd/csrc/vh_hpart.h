@@ -223,9 +223,7 @@ __global__ __launch_bounds__(HP_FAN) void hp_plan_kernel(const VhHpArgs* __restr
     }
   }
   const unsigned long long need = !c ? 0ull : vh_slice_extents(c, per, et, HA->slice_levels_cap);
-  unsigned long long incl = need;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { const unsigned long long o = __shfl_up(incl, off); if (lane >= off) incl += o; }
+  const unsigned long long incl = vh_wave_incl_add(need);
   if (lane == 63) wave_tot[wave] = incl;
   __syncthreads();
   unsigned long long before = 0;
@@ -665,9 +663,7 @@ __device__ __forceinline__ void hp_aggregate_body(const VhPlanDev& P, const VhHp
       // ---- this pass's groups: count, take places (off the result's row counter, or a piece of the block's chunk of the list), write
       uint32_t mine = 0;
       for (uint32_t g = tid; g <= GS; g += BLOCK) mine += gkeys[g] != VH_HASH_EMPTY;
-      uint32_t incl = mine;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off); if (lane >= off) incl += o; }
+      const uint32_t incl = vh_wave_incl_add(mine);
       if (lane == 63) S.wave_tot[wave] = incl;
       __syncthreads();
       uint32_t tot = 0, before = 0;

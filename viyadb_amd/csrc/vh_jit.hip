@@ -689,6 +689,12 @@ std::map<std::string, std::shared_ptr<Entry>> g_jit;
 }  // namespace
 
 static std::string kernel_name_of(const std::string& key) { return "viya_jit_scan_" + hash_hex(key).substr(0, 8); }
+// What a process keeps its kernels by: the shape, and whatever VH_JIT_FLAGS adds to the compiler's command line (experiments) — an A/B of
+// two flag sets inside ONE process compiles each shape once per set, and the kernels' names tell the legs apart.
+static std::string jit_key(const VhJitShape& s) {
+  const char* flags = getenv("VH_JIT_FLAGS");
+  return flags && *flags ? s.key() + "|" + flags : s.key();
+}
 
 int vh_jit_compile_only(const VhJitShape& s, std::vector<char>* code, std::string* log) {
   const std::string name = kernel_name_of(s.key());
@@ -696,7 +702,7 @@ int vh_jit_compile_only(const VhJitShape& s, std::vector<char>* code, std::strin
 }
 
 VhJitKernel* vh_jit_get(const VhJitShape& s, std::string* err) {
-  const std::string key = s.key();
+  const std::string key = jit_key(s);
   std::shared_ptr<Entry> e;
   {
     std::lock_guard<std::mutex> lk(g_jit_mu);
@@ -774,7 +780,7 @@ int vh_jit_peek(const VhJitShape& s, VhJitKernel** k, std::string* err) {
   std::shared_ptr<Entry> e;
   {
     std::lock_guard<std::mutex> lk(g_jit_mu);
-    auto it = g_jit.find(s.key());
+    auto it = g_jit.find(jit_key(s));
     if (it == g_jit.end()) return 0;
     e = it->second;
   }

@@ -526,16 +526,28 @@ __device__ __forceinline__ uint32_t vj_bits_rel(const uint32_t* x, uint64_t c, b
 // (vh_inset.h: vh_inset_bits) — a look-up table over the planes, whatever the list's length. NOT IN is its complement.
 template <int NB>
 __device__ __forceinline__ uint32_t vj_bits_inset(const uint32_t* x, const uint32_t* truth) { return vh_inset_bits<NB>(x, truth); }
-// The lane's passing rows (bits of `m`, row `base` + bit) appended to the wave's queue: ranks from a prefix sum of the lanes' counts, then
-// every lane writes its own rows — as many rounds as the busiest lane has survivors. At most 1 024 rows a call (the queue's room).
-__device__ __forceinline__ void vj_push_mask(uint32_t* q, uint32_t& cnt, uint32_t m, uint32_t base, int lane) {
+// A step's pass mask joins the queue in two pushes, lanes below 32 and lanes from 32 on (at most 1 024 rows each: the queue's room), with a
+// drain between them. Both pushes' ranks come from ONE scan of the lanes' counts: a lane holds at most 32 and a half at most 1 024, so the low
+// half's counts are summed in bits 0-15 and the high half's in bits 16-31 of the same word. excl: the lane's rank within its own half;
+// tot_lo, tot_hi: the halves' totals (wave-uniform).
+struct VjHalves { uint32_t excl, tot_lo, tot_hi; };
+__device__ __forceinline__ VjHalves vj_half_ranks(uint32_t m, int lane) {
   const uint32_t c = (uint32_t)__popc(m);
-  uint32_t incl = c;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off); if (lane >= off) incl += o; }
-  const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+#if VH_WAVE_SCAN_SHFL       // (a scan per half, as it was)
+  const uint32_t lo = vh_wave_incl_add(lane < 32 ? c : 0u), hi = vh_wave_incl_add(lane < 32 ? 0u : c);
+  return VjHalves{(lane < 32 ? lo : hi) - c, (uint32_t)__builtin_amdgcn_readlane((int)lo, 63), (uint32_t)__builtin_amdgcn_readlane((int)hi, 63)};
+#else
+  const uint32_t p = lane < 32 ? c : c << 16;
+  const uint32_t incl = vh_wave_incl_add(p);
+  const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+  return VjHalves{lane < 32 ? incl - p : (incl - p) >> 16, tot & 0xFFFFu, tot >> 16};      // (below lane 32 the high sum is still 0)
+#endif
+}
+// The lane's passing rows of one half (bits of `m`, row `base` + bit; 0 in the lanes of the other half) appended to the wave's queue at the
+// lane's rank `excl` among the half's `total` — every lane writes its own rows, as many rounds as the busiest lane has survivors.
+__device__ __forceinline__ void vj_push_mask(uint32_t* q, uint32_t& cnt, uint32_t m, uint32_t base, uint32_t excl, uint32_t total) {
   if (total == 0u) return;
-  uint32_t pos = cnt + incl - c;
+  uint32_t pos = cnt + excl;
   while (m) { q[pos++] = base + (uint32_t)__builtin_ctz(m); m &= m - 1u; }
   cnt += total;
 }
@@ -543,14 +555,10 @@ __device__ __forceinline__ void vj_push_mask(uint32_t* q, uint32_t& cnt, uint32_
 // The same for a plan that gathers from the GROUPED form of its record projection (J::GROUPED; vh_grouped.h): what a passing row leaves in
 // the queue is the PLACE of its record in the segment — the tile's first row + vh_grouped_pos() of the lane's mask `eq` of rows that hold the
 // grouping literal (m is a subset of it), the lanes' exclusive prefix `before` over those masks and the tile header's start[literal].
-__device__ __forceinline__ void vj_push_mask_grouped(uint32_t* q, uint32_t& cnt, uint32_t m, uint32_t eq, uint32_t before, uint32_t start, uint32_t tile_base, int lane) {
-  const uint32_t c = (uint32_t)__popc(m);
-  uint32_t incl = c;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off); if (lane >= off) incl += o; }
-  const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+__device__ __forceinline__ void vj_push_mask_grouped(uint32_t* q, uint32_t& cnt, uint32_t m, uint32_t eq, uint32_t before, uint32_t start, uint32_t tile_base,
+                                                     uint32_t excl, uint32_t total) {
   if (total == 0u) return;
-  uint32_t pos = cnt + incl - c;
+  uint32_t pos = cnt + excl;
   while (m) { q[pos++] = tile_base + vh_grouped_pos(eq, before, start, (uint32_t)__builtin_ctz(m)); m &= m - 1u; }
   cnt += total;
 }
@@ -685,7 +693,7 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
     // masks: a survivor's place IS its bit position. A run is about a quarter of a tile, so a lane-per-word step over ONE tile would leave
     // most lanes without loads; instead the wave takes up to 64 of its tiles at a time (lane t keeps tile t's first row and run), deals the
     // words of all their runs out to its lanes, 64 a batch — item k belongs to the tile whose inclusive prefix of word counts first exceeds k,
-    // found by a binary search over the lanes (six ds_bpermute) — and puts the next batch's loads in flight before it drains this batch's
+    // found through 64 slots of the wave's queue and a running maximum (fetch) — and puts the next batch's loads in flight before it drains this batch's
     // survivors. The next group's headers travel while this group's batches run. The same tiles in the same order as the row-order scan
     // (unit decomposition, counters, flush at a segment change, vj_drain): the host cannot tell the two apart.
     static_assert(J::GROUPED && J::SLICED && !J::LANES && J::QPAY == 0, "clustered planes belong to the grouped records");
@@ -736,9 +744,7 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
     collect(a_n, a_seg, a_base, a_start, a_end);
     while (a_n) {
       const uint32_t first = vh_gplanes_first_word(a_start), nw = vh_gplanes_last_word(a_start, a_end) - first;     // (lanes >= a_n: 0 words)
-      uint32_t incl = nw;
-#pragma unroll
-      for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off); if (lane >= off) incl += o; }
+      const uint32_t incl = vh_wave_incl_add(nw);
       const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
       uint32_t b_n, b_seg, b_base, b_start, b_end;
       collect(b_n, b_seg, b_base, b_start, b_end);
@@ -748,9 +754,24 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
       uint32_t i_place = 0, i_mask = 0;                  // the lane's item of the batch in flight: its word's first place in the segment, its in-run mask
       auto fetch = [&](uint32_t k0) {
         const uint32_t k = k0 + (uint32_t)lane;
+#if VH_WAVE_SCAN_SHFL       // (the binary search over the lanes, as it was)
         uint32_t t = 0;
 #pragma unroll
         for (uint32_t step = 32u; step; step >>= 1) { const uint32_t iv = (uint32_t)__shfl((int)incl, (int)(t + step - 1u)); if (iv <= k) t += step; }
+#else
+        // Item k -> tile by ONE LDS round trip: every tile that has an item in [k0, k0 + 64) leaves its number + 1 in the slot of its first item
+        // there (tiles with words have distinct first items), and a lane's tile is the last mark at or below its slot — a running maximum, the
+        // marks ascend with the slots. Slot 0 is always marked (k0 < total). The 64 slots are words 64..127 of the wave's own queue: cnt < 64
+        // here — both calls follow a drain, and what a drain keeps pending lies in registers — and the LDS operations of one wave execute in
+        // order, so every slot is read before the next push writes it.
+        uint32_t* const slot = q + 64;
+        slot[lane] = 0u;
+        if (nw && incl > k0 && incl - nw < k0 + 64u) slot[incl - nw > k0 ? incl - nw - k0 : 0u] = (uint32_t)lane + 1u;
+        __builtin_amdgcn_wave_barrier();
+        const uint32_t mark = slot[lane];
+        __builtin_amdgcn_wave_barrier();
+        uint32_t t = vh_wave_incl_max(mark) - 1u;
+#endif
         const bool act = k < total;
         t &= 63u;
         const uint32_t t_excl = (uint32_t)__shfl((int)(incl - nw), (int)t), t_first = (uint32_t)__shfl((int)first, (int)t);
@@ -768,14 +789,12 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
       for (uint32_t k0 = 0; k0 < total; k0 += 64u) {
         const uint32_t m = J::gp_mask(L, vg) & i_mask, place = i_place;
         if (k0 + 64u < total) fetch(k0 + 64u);           // the next batch travels while this one's survivors are drained
-        const uint32_t cnt0 = cnt;
-        vj_push_mask(q, cnt, lane < 32 ? m : 0u, place, lane);      // (two halves by lanes: at most 1 024 places join the queue between two drains)
-        npassed += cnt - cnt0;
+        const VjHalves h = vj_half_ranks(m, lane);
+        vj_push_mask(q, cnt, lane < 32 ? m : 0u, place, h.excl, h.tot_lo);      // (two halves by lanes: at most 1 024 places join the queue between two drains)
+        npassed += h.tot_lo + h.tot_hi;
         __builtin_amdgcn_wave_barrier();
         drain_gp(a_seg, false);
-        const uint32_t cnt1 = cnt;
-        vj_push_mask(q, cnt, lane < 32 ? 0u : m, place, lane);
-        npassed += cnt - cnt1;
+        vj_push_mask(q, cnt, lane < 32 ? 0u : m, place, h.excl, h.tot_hi);
         __builtin_amdgcn_wave_barrier();
         drain_gp(a_seg, flush && k0 + 64u >= total);
       }
@@ -837,10 +856,7 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
       }
       if constexpr (J::GROUPED) {
         const uint32_t gc = (uint32_t)__popc(geq);
-        uint32_t incl = gc;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off); if (lane >= off) incl += o; }
-        gbefore = incl - gc;
+        gbefore = vh_wave_incl_add(gc) - gc;
       }
     } else {
       if (wave_base + kWaveRows <= seg_rows) vj_slots<J, true>(L, v, row_l, seg_rows, q, cnt);
@@ -892,15 +908,14 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
       // 32 rows are one 128-byte line of a 4-byte column (a record array), and a line whose survivors are all queued together is gathered by
       // one or two consecutive drains. Split by rows (16 + 16) the two halves of every line were asked for a whole drain sequence apart — with
       // half the rows passing, C5's scan fetched every payload line twice (FETCH_SIZE 2.9 GB for 1.5 GB of columns; profiles/r05/NOTES.md)
-      if constexpr (J::GROUPED) vj_push_mask_grouped(q, cnt, lane < 32 ? smask : 0u, geq, gbefore, gstart_now, wave_base, lane);
-      else vj_push_mask(q, cnt, lane < 32 ? smask : 0u, row_l, lane);
-      npassed += cnt - cnt0;
+      const VjHalves h = vj_half_ranks(smask, lane);
+      if constexpr (J::GROUPED) vj_push_mask_grouped(q, cnt, lane < 32 ? smask : 0u, geq, gbefore, gstart_now, wave_base, h.excl, h.tot_lo);
+      else vj_push_mask(q, cnt, lane < 32 ? smask : 0u, row_l, h.excl, h.tot_lo);
+      npassed += h.tot_lo + h.tot_hi;
       __builtin_amdgcn_wave_barrier();
       drain_queue(false);
-      const uint32_t cnt1 = cnt;
-      if constexpr (J::GROUPED) vj_push_mask_grouped(q, cnt, lane < 32 ? 0u : smask, geq, gbefore, gstart_now, wave_base, lane);
-      else vj_push_mask(q, cnt, lane < 32 ? 0u : smask, row_l, lane);
-      npassed += cnt - cnt1;
+      if constexpr (J::GROUPED) vj_push_mask_grouped(q, cnt, lane < 32 ? 0u : smask, geq, gbefore, gstart_now, wave_base, h.excl, h.tot_hi);
+      else vj_push_mask(q, cnt, lane < 32 ? 0u : smask, row_l, h.excl, h.tot_hi);
       __builtin_amdgcn_wave_barrier();
     }
     drain_queue(flush);

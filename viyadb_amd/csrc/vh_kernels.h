@@ -18,6 +18,7 @@
 #include "vh_internal.h"
 #include "vh_time.h"
 #include "vh_grouped.h"
+#include "vh_wave_scan.h"
 #include <type_traits>
 
 #ifndef VH_ABLATE
@@ -1018,9 +1019,7 @@ __device__ __forceinline__ void vh_part_tile_write(const VhPlanDev& P, VhPartTil
   __builtin_amdgcn_wave_barrier();
   // lane p owns partition p: count, exclusive prefix (wave scan), cursor
   const uint32_t cnt = hist[lane];                       // lanes >= npart read 0
-  uint32_t incl = cnt;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off); if (lane >= off) incl += o; }
+  const uint32_t incl = vh_wave_incl_add(cnt);
   const uint32_t base = incl - cnt;
   __builtin_amdgcn_wave_barrier();
   hist[lane] = base;                                     // becomes the scatter cursor
@@ -1182,9 +1181,7 @@ __device__ __forceinline__ uint32_t vh_part_shares(uint32_t c, int npart, uint32
   const bool elig = c != 0 && share < cap;
   const uint64_t mask = __ballot(elig);
   if (elig && (uint32_t)__popcll(mask & ((1ull << lane) - 1ull)) < left) ++share;
-  uint32_t incl = share;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off); if (lane >= off) incl += o; }
+  const uint32_t incl = vh_wave_incl_add(share);
   *start = incl - share;
   return share;
 }

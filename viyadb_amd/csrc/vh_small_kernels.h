@@ -482,8 +482,7 @@ __global__ __launch_bounds__(256) void select_scan_kernel(uint32_t* counts, uint
   for (uint32_t t0 = 0; t0 < chunks_per_seg; t0 += 256) {
     const uint32_t i = t0 + threadIdx.x;
     const uint32_t v = i < chunks_per_seg ? c[i] : 0u;
-    uint32_t incl = v;
-    for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off); if (lane >= off) incl += o; }
+    const uint32_t incl = vh_wave_incl_add(v);
     if (lane == 63) wsum[wave] = incl;
     __syncthreads();
     uint32_t before = 0, tile = 0;
@@ -616,9 +615,7 @@ __global__ __launch_bounds__(256) void select_emit_sliced_kernel(const VhSelectS
     if (w.lo >= w.hi || ord >= w.hi || end <= w.lo) continue;      // no row of the window in this chunk
     uint32_t m = vh_select_sliced_mask(A, seg, base, seg_rows, lane);
     const uint32_t mine = (uint32_t)__popc(m);
-    uint32_t incl = mine;                           // passing rows in this lane and the lower ones
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off); if (lane >= off) incl += o; }
+    const uint32_t incl = vh_wave_incl_add(mine);   // passing rows in this lane and the lower ones
     uint64_t o = ord + incl - mine;                 // ordinal of this lane's first passing row
     if (o < w.hi && o + mine > w.lo) {              // (some row of this lane's is inside the window)
       const uint32_t row_l = (uint32_t)base + (uint32_t)lane * 32u;
@@ -1014,9 +1011,7 @@ __global__ __launch_bounds__(256) void group_bits_kernel(const VhGroupArgs A) {
   __syncthreads();
   for (uint32_t v = wave; v < nvals; v += 4u) {         // the lanes' exclusive prefix, per value (NL == 64: one wave, one value)
     const uint32_t c = (uint32_t)__popc(s_eq[v][lane]);
-    uint32_t incl = c;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const uint32_t o = __shfl_up(incl, off); if (lane >= off) incl += o; }
+    const uint32_t incl = vh_wave_incl_add(c);
     s_before[v][lane] = (uint16_t)(incl - c);
     if (lane == 63) s_total[v] = (uint16_t)incl;
   }
