@@ -228,6 +228,9 @@ enum vh_plan_flags {
   VH_PLAN_NO_GPLANES = 1u << 29,  /* ablation: a plan that gathers from the grouped records still reads the row-order bit planes, even where the
                                      planes clustered in the tiles' grouped order exist (an A/B inside one process) */
   VH_PLAN_SET_SEARCH = 1u << 30,  /* testing: every set of a VH_F_INSET leaf takes the sorted-array form, whatever its span */
+  VH_PLAN_SLICED_PREBUILT = 1u << 31, /* opt-in: an aggregate that no compiled kernel answers reads its filter off a bit-sliced predicate projection
+                                     through the pre-built scan_agg_sliced_kernel (the rule: "Pre-built scans on the bit-sliced planes" below;
+                                     VH_SLICED_PREBUILT=1 in the environment sets it for every aggregate of the process) */
   VH_PLAN_CARD32 = 1u << 22       /* the cardinality of a 32-bit-id bitset metric (count distinct) is delivered as a uint32 column instead of
                                      uint64 (it cannot exceed 2^32 - 1): vh_result_state_elem() tells what a state column holds */
 };
@@ -302,7 +305,9 @@ typedef struct vh_result_info {
                                         (bits 13 and 22 are set too; bit 23 still tells the form of the ordinary tables, which are uploaded all the same);
                                 bit 19: (VH_BUILD_BACKGROUND tables) a kernel compile or a layout build for this query's shape is queued or running:
                                         this query ran on what existed (the pre-built kernels, the arenas, layouts already there);
-                                bit 24: (tables with a layout budget) planning this query evicted at least one derived layout */
+                                bit 24: (tables with a layout budget) planning this query evicted at least one derived layout;
+                                bit 26: a PRE-BUILT scan read the filter off the bit-sliced predicate planes (VH_PLAN_SLICED_PREBUILT: bits 4, 11
+                                        and 13 are set too, bits 22 and 25 when the filter has VH_F_INSET leaves; bits 0, 1 and 5 are clear) */
   uint64_t returned_groups;  /* rows vh_result_copy delivers (= ngroups without HAVING) */
 } vh_result_info;
 
@@ -638,7 +643,18 @@ VH_API int vh_query_agg_sharded(vh_table* t, const vh_plan* plan, vh_comm* comm,
  * the program interpreted bit-serially on 32 rows per lane by pre-built kernels. Nothing is compiled, so VH_JIT, VH_PLAN_NO_JIT and
  * VH_JIT_MIN_ROWS do not bear on the choice. The select stamps the projection it reads like an aggregate does (vh_layout_info.uses) and
  * holds it against eviction while it runs; it never builds or queues a layout. The rows are the same either way; vh_rows_flags tells which
- * kernels ran. */
+ * kernels ran.
+ *
+ * Pre-built scans on the bit-sliced planes. An AGGREGATE takes the same planes through a pre-built kernel (scan_agg_sliced_kernel: the
+ * program interpreted bit-serially in front of the pre-built sinks) only when asked to — VH_PLAN_SLICED_PREBUILT on the plan, or
+ * VH_SLICED_PREBUILT=1 in the environment (read once per process) — and when all of this holds: no compiled kernel runs the query
+ * (VH_PLAN_NO_JIT, VH_JIT=off, fewer rows than VH_JIT_MIN_ROWS, a compile pending in background mode or failed, a shape the generator
+ * does not cover); the plan has a filter; the select's conditions above hold (one usable bit-sliced projection with every leaf's column, the
+ * inline budget, set leaves on fields of at most 10 bits, none of VH_PLAN_NO_SLICED / VH_PLAN_NO_PREDPACK / VH_PLAN_NO_NARROW); and the plan
+ * has not settled on a no-compaction (lanes) form, nor — for the partitioned dense organisation — on one-word tuples, which keep their
+ * kernels. The flag changes which kernel evaluates the predicate and nothing else: path, table organisation, tuple format
+ * and result are those of the same plan without it, so sharded ranks keep agreeing. The query stamps and holds the projection like the
+ * select; it builds and queues no layout. vh_result_info.reserved bit 26 tells. Without flag and variable nothing is different. */
 #define VH_COL_ROWID (-2)
 typedef struct vh_rows vh_rows;
 typedef struct vh_select_plan {

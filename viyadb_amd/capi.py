@@ -37,6 +37,7 @@ PLAN_NO_PREDPACK, PLAN_NO_QPAY, PLAN_FORCE_QPAY, PLAN_NO_SLICED = 1 << 24, 1 << 
 PLAN_NO_GROUPED = 1 << 28
 PLAN_NO_GPLANES = 1 << 29
 PLAN_SET_SEARCH = 1 << 30         # testing: every set of an F_INSET leaf takes the sorted-array form
+PLAN_SLICED_PREBUILT = 1 << 31    # opt-in: an aggregate no compiled kernel answers reads its filter off the bit-sliced planes (scan_agg_sliced_kernel)
 # paths
 PATH_SCALAR, PATH_DENSE_LDS, PATH_DENSE_GLOBAL, PATH_HASH, PATH_DENSE_PART = range(5)
 PATH_NAMES = ["scalar", "dense_lds", "dense_global", "hash", "dense_part"]
@@ -145,6 +146,7 @@ INFO_GROUPED_PLANES = 1 << 21     # vh_result_info.reserved bit 21
 INFO_INSET = 1 << 22              # vh_result_info.reserved bit 22: the filter's set leaves were evaluated by lookup
 INFO_INSET_SEARCH = 1 << 23       # ... bit 23: at least one of them by binary search in a sorted array
 INFO_INSET_SLICED = 1 << 25       # ... bit 25: all of them from truth tables on the bit-sliced predicate planes instead (no lookup per row)
+INFO_SLICED_PREBUILT = 1 << 26    # ... bit 26: a pre-built scan read the filter off the bit-sliced predicate planes (bits 4, 11 and 13 are set too)
 INFO_EVICTED = 1 << 24            # ... bit 24: planning this query evicted at least one derived layout (tables with a layout budget)
 
 

@@ -1,6 +1,6 @@
 // vh_bits_eval.h — a filter program evaluated BIT-SERIALLY on the bit-sliced predicate planes (VhPredPack::sliced), 32 rows per call.
 // Plain C++ for host and device, like vh_inset.h: the select kernels include it (vh_small_kernels.h: select_count_sliced_kernel,
-// select_emit_sliced_kernel), the planner fills its program (vhh_plan.h), and a host-compiled check holds it against a per-row evaluation
+// select_emit_sliced_kernel) and so does the pre-built aggregate scan (vh_scan_sliced.hip), the planner fills its program (vhh_plan.h), and a host-compiled check holds it against a per-row evaluation
 // of the same program (tests/bits_eval_host.cc).
 //
 // The per-query compiled scan reads the planes through code generated for the plan's shape (vh_jit_body.h: vj_bits_rel<NB, OP>,
@@ -41,7 +41,7 @@
 #ifndef VH_MAX_STACK
 #define VH_MAX_STACK 8           // operand stack of the program (= vh_internal.h)
 #endif
-#define VH_BITS_MAX_PROG 24      // = VH_INLINE_PROG, VH_INLINE_LITS (vh_internal.h; vh_small_kernels.h asserts both): the program travels in the
+#define VH_BITS_MAX_PROG 24      // = VH_INLINE_PROG, VH_INLINE_LITS (vh_internal.h; vh_sliced.h asserts both): the program travels in the
 #define VH_BITS_MAX_LITS 32      //   kernel arguments
 #define VH_BITS_MAX_FIELD 32     // planes of one field: a row word of the projection has 32 bits
 

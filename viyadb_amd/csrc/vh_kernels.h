@@ -784,18 +784,13 @@ struct VhScanCfg {
 // values of one survivor each and update the aggregate table. No block-wide barrier in
 // the loop: queues are per wave.
 __device__ __forceinline__ void vh_scan_block_end(const VhPlanDev& P, unsigned long long npassed, unsigned long long nfresh, unsigned long long npairs, uint32_t ext_end);     // (below, with the partition helpers)
-template <int MODE, int BLOCK, int SCOPE>
-__global__ __launch_bounds__(BLOCK) void scan_agg_kernel(const VhPlanDev P) {
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  typedef VhScanCfg<BLOCK> C;
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  // queues live behind the (optional) LDS aggregate table
-  uint32_t* q = reinterpret_cast<uint32_t*>(lds + ((MODE == VH_MODE_DENSE_LDS || MODE == VH_MODE_HASH) ? P.lds_bytes : 0)) +
-                wave * C::kQueueCap;
-  VhLdsHashWave H{0u, 0u, false, 0ull};
-  if (MODE == VH_MODE_HASH && P.lds_hash_slots) vh_lds_hash_init(P, lds, BLOCK);
 
+// The block's LDS table before and after the scan, for every compacting scan kernel (scan_agg_kernel, vh_scan_fast_body, scan_agg_sliced_kernel):
+// the hash organisation's front table emptied / merged into the HBM table, DENSE_LDS's table set to the identities / flushed with one global
+// update per (block, present group).
+template <int MODE, int BLOCK>
+__device__ __forceinline__ void vh_scan_table_init(const VhPlanDev& P, char* lds) {
+  if (MODE == VH_MODE_HASH && P.lds_hash_slots) vh_lds_hash_init(P, lds, BLOCK);
   if (MODE == VH_MODE_DENSE_LDS) {
     // identities: 0 for SUM/AVG/COUNT, type max for MIN, cpp_min_value for MAX
     // (src/codegen/db/store.cc:107-117)
@@ -813,6 +808,38 @@ __global__ __launch_bounds__(BLOCK) void scan_agg_kernel(const VhPlanDev P) {
     for (uint64_t g = threadIdx.x; g < P.G; g += BLOCK) reinterpret_cast<uint8_t*>(lds + P.lds_present_off)[g] = 0;
     __syncthreads();
   }
+}
+template <int MODE, int BLOCK, int SCOPE>
+__device__ __forceinline__ void vh_scan_table_flush(const VhPlanDev& P, char* lds) {
+  if (MODE == VH_MODE_HASH && P.lds_hash_slots) vh_lds_hash_flush(P, lds, BLOCK);
+  if (MODE == VH_MODE_DENSE_LDS) {
+    // flush this block's LDS table: one global update per (block, present group)
+    __syncthreads();
+    const uint64_t xo = P.nxcd > 1 ? (uint64_t)(vh_xcc_id() % P.nxcd) * P.xcd_stride : 0;
+    for (uint64_t g = threadIdx.x; g < P.G; g += BLOCK) {
+      if (!reinterpret_cast<uint8_t*>(lds + P.lds_present_off)[g]) continue;
+      P.present[xo + g] = 1;
+      for (int j = 0; j < P.nmetric; ++j) {
+        const VhMetricDev& m = P.m[j];
+        const uint64_t bits = vh_sop_bytes(m.sop()) == 4 ? reinterpret_cast<uint32_t*>(lds + m.lds_off)[g]
+                                                       : reinterpret_cast<uint64_t*>(lds + m.lds_off)[g];
+        vh_state_update<SCOPE>(m.state, xo + g, m.sop(), bits);
+      }
+    }
+  }
+}
+
+template <int MODE, int BLOCK, int SCOPE>
+__global__ __launch_bounds__(BLOCK) void scan_agg_kernel(const VhPlanDev P) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  typedef VhScanCfg<BLOCK> C;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  // queues live behind the (optional) LDS aggregate table
+  uint32_t* q = reinterpret_cast<uint32_t*>(lds + ((MODE == VH_MODE_DENSE_LDS || MODE == VH_MODE_HASH) ? P.lds_bytes : 0)) +
+                wave * C::kQueueCap;
+  VhLdsHashWave H{0u, 0u, false, 0ull};
+  vh_scan_table_init<MODE, BLOCK>(P, lds);
 
   const uint64_t xoff = (MODE == VH_MODE_DENSE_GLOBAL && P.nxcd > 1) ? (uint64_t)(vh_xcc_id() % P.nxcd) * P.xcd_stride : 0;
   const uint64_t lanemask_lt = (1ull << lane) - 1ull;
@@ -870,23 +897,7 @@ __global__ __launch_bounds__(BLOCK) void scan_agg_kernel(const VhPlanDev P) {
   if (MODE == VH_MODE_HASH) vh_hot_flush(P, H.hot);      // what the wave still keeps of its hot group
   for (int off = 32; off > 0; off >>= 1) { npassed += __shfl_down(npassed, off); H.npairs += __shfl_down(H.npairs, off); }
   vh_scan_block_end(P, npassed, nfresh, H.npairs, 0u);     // (one set of atomics per block; this kernel writes no tuples)
-  if (MODE == VH_MODE_HASH && P.lds_hash_slots) vh_lds_hash_flush(P, lds, BLOCK);
-
-  if (MODE == VH_MODE_DENSE_LDS) {
-    // flush this block's LDS table: one global update per (block, present group)
-    __syncthreads();
-    const uint64_t xo = P.nxcd > 1 ? (uint64_t)(vh_xcc_id() % P.nxcd) * P.xcd_stride : 0;
-    for (uint64_t g = threadIdx.x; g < P.G; g += BLOCK) {
-      if (!reinterpret_cast<uint8_t*>(lds + P.lds_present_off)[g]) continue;
-      P.present[xo + g] = 1;
-      for (int j = 0; j < P.nmetric; ++j) {
-        const VhMetricDev& m = P.m[j];
-        const uint64_t bits = vh_sop_bytes(m.sop()) == 4 ? reinterpret_cast<uint32_t*>(lds + m.lds_off)[g]
-                                                       : reinterpret_cast<uint64_t*>(lds + m.lds_off)[g];
-        vh_state_update<SCOPE>(m.state, xo + g, m.sop(), bits);
-      }
-    }
-  }
+  vh_scan_table_flush<MODE, BLOCK, SCOPE>(P, lds);
 }
 
 
@@ -1760,25 +1771,11 @@ __device__ __forceinline__ void vh_scan_fast_body(const VhPlanDev& P) {
   const int wave = threadIdx.x >> 6;
   uint32_t* q = reinterpret_cast<uint32_t*>(lds + ((MODE == VH_MODE_DENSE_LDS || MODE == VH_MODE_HASH) ? P.lds_bytes : 0)) + wave * C::kQueueCap;
   VhLdsHashWave H{0u, 0u, false, 0ull};
-  if (MODE == VH_MODE_HASH && P.lds_hash_slots) vh_lds_hash_init(P, lds, BLOCK);
   VhPartWave W;
   VhPartTile T;
   if (MODE == VH_MODE_DENSE_PART)
     vh_part_tile_init(P, lds, T, W);
-
-  if (MODE == VH_MODE_DENSE_LDS) {
-    for (int j = 0; j < P.nmetric; ++j) {
-      const VhMetricDev& m = P.m[j];
-      const uint64_t ident = m.ident;
-      if (vh_sop_bytes(m.sop()) == 4) {
-        for (uint64_t g = threadIdx.x; g < P.G; g += BLOCK) reinterpret_cast<uint32_t*>(lds + m.lds_off)[g] = (uint32_t)ident;
-      } else {
-        for (uint64_t g = threadIdx.x; g < P.G; g += BLOCK) reinterpret_cast<uint64_t*>(lds + m.lds_off)[g] = ident;
-      }
-    }
-    for (uint64_t g = threadIdx.x; g < P.G; g += BLOCK) reinterpret_cast<uint8_t*>(lds + P.lds_present_off)[g] = 0;
-    __syncthreads();
-  }
+  vh_scan_table_init<MODE, BLOCK>(P, lds);
 
   const uint64_t xoff = (MODE == VH_MODE_DENSE_GLOBAL && P.nxcd > 1) ? (uint64_t)(vh_xcc_id() % P.nxcd) * P.xcd_stride : 0;
   uint32_t npassed32 = 0;                    // per lane: a lane sees a 64th of this block's rows (< 2^32); one register less than a 64-bit count
@@ -1859,21 +1856,7 @@ __device__ __forceinline__ void vh_scan_fast_body(const VhPlanDev& P) {
   unsigned long long npassed = npassed32;
   for (int off = 32; off > 0; off >>= 1) npassed += __shfl_down(npassed, off);
   vh_scan_block_end(P, npassed, nfresh, 0ull, MODE == VH_MODE_DENSE_PART ? vh_part_wave_end(P, W) : 0u);
-  if (MODE == VH_MODE_HASH && P.lds_hash_slots) vh_lds_hash_flush(P, lds, BLOCK);
-  if (MODE == VH_MODE_DENSE_LDS) {
-    __syncthreads();
-    const uint64_t xo = P.nxcd > 1 ? (uint64_t)(vh_xcc_id() % P.nxcd) * P.xcd_stride : 0;
-    for (uint64_t g = threadIdx.x; g < P.G; g += BLOCK) {
-      if (!reinterpret_cast<uint8_t*>(lds + P.lds_present_off)[g]) continue;
-      P.present[xo + g] = 1;
-      for (int j = 0; j < P.nmetric; ++j) {
-        const VhMetricDev& m = P.m[j];
-        const uint64_t bits = vh_sop_bytes(m.sop()) == 4 ? reinterpret_cast<uint32_t*>(lds + m.lds_off)[g]
-                                                       : reinterpret_cast<uint64_t*>(lds + m.lds_off)[g];
-        vh_state_update<SCOPE>(m.state, xo + g, m.sop(), bits);
-      }
-    }
-  }
+  vh_scan_table_flush<MODE, BLOCK, SCOPE>(P, lds);
 }
 
 template <int MODE, int BLOCK, int SCOPE, int NP>

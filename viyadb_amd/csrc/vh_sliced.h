@@ -1,0 +1,42 @@
+// vh_sliced.h — what the PRE-BUILT readers of the bit-sliced predicate planes share on the device: the kernel arguments that name the planes
+// and carry the filter program (vh_bits_eval.h), and a lane's pass mask for its word of a chunk (vh_sliced_walk.h). Included by the select
+// kernels (vh_small_kernels.h) and by the aggregate scan over the planes (vh_scan_sliced.hip).
+#pragma once
+#include "vh_internal.h"
+#include "vh_bits_eval.h"
+#include "vh_sliced_walk.h"
+
+static_assert(VH_BITS_MAX_PROG == VH_INLINE_PROG && VH_BITS_MAX_LITS == VH_INLINE_LITS, "vh_bits_eval.h restates the inline program's budget");
+// Where a projection's planes lie. Kernel argument: 32- and 64-bit members only (VH_PACKED_FIELD, vh_internal.h).
+struct VhSlicedPlanes {
+  const char* planes;             // the projection's arena: segment 0, plane 0
+  uint64_t stride, pitch;         // bytes between segments / between planes
+};
+// The select kernels' argument: the program travels by value.
+struct VhSlicedArgs {
+  VhBitsProg B;
+  VhSlicedPlanes L;
+  const uint32_t* seg_rows;       // per segment: rows to scan (0 = skipped)
+  unsigned long long* counters;   // [0] passed rows
+  uint32_t nseg, pad;
+};
+// The aggregate scan's second argument, beside VhPlanDev (which names snapshot and counters): plan and program together would pass the 4 KB
+// of kernel arguments (VhPlanDev alone is 3.9 KB), so the program lies in the query's uploaded plan block, behind the sets, and is read
+// through this pointer. The launcher hands the kernel the pointer as a `__restrict__` parameter of its own and the planes by value: only
+// then does the compiler know the program for unclobbered and read it with scalar loads (inside a by-value struct it took vector loads, a
+// round trip per program word and chunk).
+struct VhSlicedRef {
+  const VhBitsProg* B;
+  VhSlicedPlanes L;
+};
+
+#if defined(__HIPCC__)
+// pass mask of the lane's word (rows base + 32 * lane ..) of a chunk that begins at row `base` < seg_rows
+__device__ __forceinline__ uint32_t vh_sliced_mask(const VhBitsProg& B, const VhSlicedPlanes& L, uint32_t seg, uint64_t base, uint32_t seg_rows, int lane) {
+  const uint64_t row_l = base + (uint64_t)lane * 32u;
+  const uint32_t keep = vh_sliced_tail_mask(row_l, seg_rows);
+  uint32_t m = 0u;
+  if (keep) m = vh_bits_eval(B, L.planes + (uint64_t)seg * L.stride, L.pitch, (uint32_t)(row_l >> 5) * 4u) & keep;
+  return m;
+}
+#endif

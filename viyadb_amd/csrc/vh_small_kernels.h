@@ -5,6 +5,7 @@
 #include "vh_topk_key.h"
 #include "vhh_layout_math.h"
 #include "vh_bits_eval.h"
+#include "vh_sliced.h"
 
 // ----------------------------------------------------------- table finalisation
 // Combine the per-XCD private copies of a dense table into copy 0 (they were only ever
@@ -544,52 +545,20 @@ __global__ __launch_bounds__(256) void select_emit_kernel(const VhPlanDev P, uin
 // rows — every lane of a wave owns one plane word — and select_scan_kernel runs between the two as it does for the arenas. The emission
 // evaluates the filter again: a mask buffer between the passes would be 1/8 byte per row of scratch per execution context.
 // Rows at or beyond the snapshot's seg_rows never pass: words that begin there are not read, the word that straddles it is masked.
-#define VH_SLICED_CHUNK_ROWS 2048u
-static_assert(VH_BITS_MAX_PROG == VH_INLINE_PROG && VH_BITS_MAX_LITS == VH_INLINE_LITS, "vh_bits_eval.h restates the inline program's budget");
-struct VhSelectSliced {           // kernel argument: 32- and 64-bit members only (VH_PACKED_FIELD, vh_internal.h)
-  VhBitsProg B;
-  const char* planes;             // the projection's arena: segment 0, plane 0
-  uint64_t stride, pitch;         // bytes between segments / between planes
-  const uint32_t* seg_rows;       // per segment: rows to scan (0 = skipped)
-  unsigned long long* counters;   // [0] passed rows
-  uint32_t nseg, pad;
-};
-
-// pass mask of the lane's word (rows base + 32 * lane ..) of a chunk that begins at row `base` < seg_rows
-__device__ __forceinline__ uint32_t vh_select_sliced_mask(const VhSelectSliced& A, uint32_t seg, uint64_t base, uint32_t seg_rows, int lane) {
-  const uint64_t row_l = base + (uint64_t)lane * 32u;
-  uint32_t m = 0u;
-  if (row_l < seg_rows) {
-    m = vh_bits_eval(A.B, A.planes + (uint64_t)seg * A.stride, A.pitch, (uint32_t)(row_l >> 5) * 4u);
-    const uint32_t left = seg_rows - (uint32_t)row_l;
-    if (left < 32u) m &= (1u << left) - 1u;
-  }
-  return m;
-}
-
-// A wave's walk over the chunks, as (segment, chunk of the segment): chunk 4 * block + wave first, then every (4 * blocks)-th. Stepped as the
-// pair: a 64-bit division per chunk would cost as much as the evaluation of a narrow field.
-struct VhChunkWalk {
-  uint32_t seg, k, step_seg, step_k, cps;
-  __device__ __forceinline__ VhChunkWalk(uint32_t wave, uint32_t chunks_per_seg) : cps(chunks_per_seg) {
-    const uint32_t c0 = blockIdx.x * 4u + wave, stride = gridDim.x * 4u;
-    seg = c0 / cps; k = c0 - seg * cps;
-    step_seg = stride / cps; step_k = stride - step_seg * cps;
-  }
-  __device__ __forceinline__ void next() { seg += step_seg; k += step_k; if (k >= cps) { k -= cps; ++seg; } }
-  __device__ __forceinline__ uint64_t chunk() const { return (uint64_t)seg * cps + k; }
-};
+// The argument (VhSlicedArgs), a lane's pass mask (vh_sliced_mask) and the waves' walk over the chunks (VhChunkWalk) are shared with the aggregate
+// scan over the planes: vh_sliced.h, vh_sliced_walk.h.
+typedef VhSlicedArgs VhSelectSliced;
 
 __global__ __launch_bounds__(256) void select_count_sliced_kernel(const VhSelectSliced A, uint32_t chunks_per_seg, uint32_t* counts) {
   const int lane = threadIdx.x & 63;
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (uniform, and known to be: chunk, segment and plane addresses are scalars)
   unsigned long long npassed = 0;
-  for (VhChunkWalk W(wave, chunks_per_seg); W.seg < A.nseg; W.next()) {
+  for (VhChunkWalk W(blockIdx.x, gridDim.x, 4u, wave, chunks_per_seg); W.seg < A.nseg; W.next()) {
     const uint64_t base = (uint64_t)W.k * VH_SLICED_CHUNK_ROWS;
     const uint32_t seg_rows = A.seg_rows[W.seg];
     uint32_t n = 0;
     if (base < seg_rows) {
-      n = __popc(vh_select_sliced_mask(A, W.seg, base, seg_rows, lane));
+      n = __popc(vh_sliced_mask(A.B, A.L, W.seg, base, seg_rows, lane));
       for (int off = 32; off > 0; off >>= 1) n += __shfl_xor(n, off);
     }
     if (lane == 0) { counts[W.chunk()] = n; npassed += n; }
@@ -603,7 +572,7 @@ __global__ __launch_bounds__(256) void select_emit_sliced_kernel(const VhSelectS
   const int lane = threadIdx.x & 63;
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int ncols = S->ncols;
-  for (VhChunkWalk W(wave, chunks_per_seg); W.seg < A.nseg; W.next()) {
+  for (VhChunkWalk W(blockIdx.x, gridDim.x, 4u, wave, chunks_per_seg); W.seg < A.nseg; W.next()) {
     const uint32_t seg = W.seg;
     const uint64_t base = (uint64_t)W.k * VH_SLICED_CHUNK_ROWS;
     const uint32_t seg_rows = A.seg_rows[seg];
@@ -613,7 +582,7 @@ __global__ __launch_bounds__(256) void select_emit_sliced_kernel(const VhSelectS
     const uint64_t ord = prefix[c];                 // ordinal (within the segment) of this chunk's first passing row ...
     const uint64_t end = W.k + 1 < chunks_per_seg ? (uint64_t)prefix[c + 1] : (uint64_t)seg_totals[seg];      // ... and of the next chunk's
     if (w.lo >= w.hi || ord >= w.hi || end <= w.lo) continue;      // no row of the window in this chunk
-    uint32_t m = vh_select_sliced_mask(A, seg, base, seg_rows, lane);
+    uint32_t m = vh_sliced_mask(A.B, A.L, seg, base, seg_rows, lane);
     const uint32_t mine = (uint32_t)__popc(m);
     const uint32_t incl = vh_wave_incl_add(mine);   // passing rows in this lane and the lower ones
     uint64_t o = ord + incl - mine;                 // ordinal of this lane's first passing row

@@ -361,7 +361,7 @@ static void replan_after(vh_table* t, vh_result* r, int retry, VhReplan* rp) {
     uint64_t next = (r->plan.hmask + 1) * 4;
     if (!rp->cap_override) {
       double sel = 1.0;
-      if (r->info.reserved & 1) { std::lock_guard<std::mutex> lk(t->mu); (void)estimate_selectivity(t, r->exec, r->plan, r->h_prog, r->h_lits, r->plan.nseg, &sel, nullptr, nullptr, !r->h_sets.empty(), &r->h_sets); }      // (set leaves: the interpreting kernel counts)
+      if (r->fast_scan) { std::lock_guard<std::mutex> lk(t->mu); (void)estimate_selectivity(t, r->exec, r->plan, r->h_prog, r->h_lits, r->plan.nseg, &sel, nullptr, nullptr, !r->h_sets.empty(), &r->h_sets); }      // (set leaves: the interpreting kernel counts)
       uint64_t survivors = (uint64_t)((double)r->info.scanned_recs * std::min(1.0, sel * 1.1)) + 1024;
       uint64_t sized = 1;
       while (sized < survivors * 2) sized <<= 1;

@@ -294,11 +294,29 @@ int QueryBuild::compile_kernel() {
   return VH_OK;
 }
 
+// The pre-built scan over the bit-sliced planes answers this aggregate (scan_agg_sliced_kernel; include/viya_hip.h states the rule): asked for
+// and found possible so far (planes_ready: a filter, every leaf a field of one usable bit-sliced projection, the inline budget, set leaves with
+// truth tables, none of the flags that keep a plan off the planes), no compiled kernel after all, and a plan whose sink the kernel carries —
+// not a no-compaction form, and of DENSE_PART what vh_launch_scan_fast_part would run: the compacting form with tuples of two words or more. (A plan
+// with a specialised drain, P.shape 1 / 2, goes through the generic one here: vh_consume_fast<.., 0> lays the same tuple out from m[j].tword /
+// tshift, and never looks at the second digit a one-column shape plan adds.)
+// It only changes which kernel evaluates the predicate. The projection is stamped and held like a compiled reader's; nothing is built or queued.
+void QueryBuild::choose_sliced_prebuilt() {
+  if (!planes_ready || jk || lanes || hpart || g_heavy.only || !sliced_use || sliced_use->applied_epoch != t->sync_epoch) return;
+  if (mode == VH_MODE_DENSE_PART && (!fast || P.gid_bits)) return;
+  sliced_prebuilt = true;
+  layout_use(t, sliced_use);
+}
+
 void QueryBuild::scan_dispatch(int grid_, int* occ) {
   const size_t qb = (size_t)(BLOCK / 64) * VhScanCfg<256>::kQueueCap * sizeof(uint32_t);
   const size_t lds_ = ((mode == VH_MODE_DENSE_LDS || mode == VH_MODE_HASH) ? lds_table : 0) + qb;
   hipStream_t s_ = x->stream();
-  if (jk) {
+  if (sliced_prebuilt) {
+    const uint32_t cps = (uint32_t)std::max<uint64_t>(1, (t->padded_rows + VH_SLICED_CHUNK_ROWS - 1) / VH_SLICED_CHUNK_ROWS);
+    vh_launch_scan_sliced(mode, P, planes_ref, cps, grid_, mode == VH_MODE_DENSE_PART ? qb : lds_, nxcd > 1, s_, occ);
+  }
+  else if (jk) {
     const size_t jl = ((mode == VH_MODE_DENSE_LDS || (mode == VH_MODE_HASH && !hpart)) ? lds_table : 0) + (size_t)(BLOCK / 64) * (VJ_QUEUE_CAP * sizeof(uint32_t)) +
                       (jshape.hp_fan ? VJ_FAN_LDS_BYTES(BLOCK) : 0) + (jshape.part_ring ? VH_RING_LDS_BYTES(jshape.part_ring, 2, BLOCK) : 0);
     if (occ) *occ = vh_jit_occupancy(jk, BLOCK, jl);
@@ -324,6 +342,7 @@ int QueryBuild::decompose_work() {
   // variant pays for more blocks with more table merges at the end (blocks x groups x metrics global atomics), so
   // it keeps one 1024-thread block per CU unless the scan dwarfs that.
   const int env_lanes_block = knobs().lanes_block, env_bpc = knobs().blocks_per_cu, env_unit = knobs().unit_rows;
+  choose_sliced_prebuilt();
   BLOCK = jk ? jit_block : mode == VH_MODE_DENSE_LDS ? 1024 : 256;
   if (mode == VH_MODE_DENSE_LDS && lanes) {
     if (env_lanes_block == 256 || env_lanes_block == 512 || env_lanes_block == 1024) BLOCK = env_lanes_block;
@@ -333,7 +352,8 @@ int QueryBuild::decompose_work() {
   {   // the kernel symbol(s) this query runs, as rocprofv3 prints them (vh_result_kernel: bench.py's roofline.kernel)
     const int np_ = std::max(1, (int)P.npred), scope = (mode == VH_MODE_DENSE_GLOBAL || mode == VH_MODE_DENSE_LDS) && nxcd > 1 ? (int)__HIP_MEMORY_SCOPE_WORKGROUP : (int)__HIP_MEMORY_SCOPE_AGENT;
     char nm[160];
-    if (!fast) snprintf(nm, sizeof(nm), "scan_agg_kernel<%d, %d, %d>", mode, BLOCK, scope);
+    if (sliced_prebuilt) snprintf(nm, sizeof(nm), "scan_agg_sliced_kernel<%d, %d, %d>", mode, BLOCK, (mode == VH_MODE_HASH || mode == VH_MODE_DENSE_PART) ? (int)__HIP_MEMORY_SCOPE_AGENT : scope);
+    else if (!fast) snprintf(nm, sizeof(nm), "scan_agg_kernel<%d, %d, %d>", mode, BLOCK, scope);
     else if (mode == VH_MODE_DENSE_PART && !lanes && P.shape) snprintf(nm, sizeof(nm), "scan_agg_shape_kernel<%d, %d, %d, %d, %d>", mode, BLOCK, (int)__HIP_MEMORY_SCOPE_AGENT, np_, P.shape);
     else snprintf(nm, sizeof(nm), "%s<%d, %d, %d, %d>", lanes ? "scan_agg_lanes_kernel" : "scan_agg_fast_kernel", mode, BLOCK,
                   (mode == VH_MODE_HASH || mode == VH_MODE_DENSE_PART) ? (int)__HIP_MEMORY_SCOPE_AGENT : scope, np_);
@@ -598,6 +618,14 @@ int QueryBuild::layout_scratch() {
   P.prog = reinterpret_cast<const VhProgOp*>(S + o_segrows + r->seg_words * 4);
   P.lits = reinterpret_cast<const uint64_t*>(S + o_segrows + r->seg_words * 4 + r->h_prog.size() * sizeof(VhProgOp));
   P.set = r->place_sets(x->h_segrows, S + o_segrows);
+  if (planes_ready) {      // the program over the planes, into the staging block behind the sets (BEFORE the upload reads it) ...
+    planes_prog.set = P.set;
+    memcpy(x->h_segrows + planes_word, &planes_prog, sizeof(VhBitsProg));
+  }
+  if (sliced_prebuilt) {   // ... and where the kernel finds it
+    planes_ref.B = reinterpret_cast<const VhBitsProg*>(S + o_segrows + planes_word * 4);
+    planes_ref.L.planes = sliced_use->plane[0].ptr; planes_ref.L.stride = sliced_use->plane[0].stride; planes_ref.L.pitch = sliced_use->pitch;
+  }
   if (mode == VH_MODE_HASH) {
     P.hkeys = reinterpret_cast<uint64_t*>(S + o_hkeys);
     P.htags = P.key_words > 1 ? reinterpret_cast<uint32_t*>(S + o_htags) : nullptr;
@@ -757,6 +785,10 @@ int QueryBuild::launch() {
   r->hpart = hpart;
   r->info.reserved = (hpart ? 64 : 0) | (fastj || jk ? 1 : 0) | (lanes ? 2 : 0) | (P.lds_hash_slots ? 4 : 0) | (packed ? 8 : 0) | (fastj && narrowed ? 16 : 0) | (jk ? 32 : 0) | (packed && packed_compressed ? 128 : 0) | (hpart && hp_pack ? 256 : 0) | (mode == VH_MODE_DENSE_PART && P.gid_bits ? 1024 : 0) | (jk && (jshape.pp_nplanes || jshape.pp_sliced) ? 2048 : 0) | (jk && jshape.qpay ? 4096 : 0) | (jk && jshape.pp_sliced ? 8192 : 0) | (mode == VH_MODE_DENSE_PART && P.gid_bits && P.tuple4 ? 16384 : 0)
                    | (has_set ? 1u << 22 : 0) | (has_set && set_search ? 1u << 23 : 0) | (jk && has_set && set_truth && jshape.pp_sliced ? 1u << 25 : 0) | (build_pending ? 1u << 19 : 0) | (jk && grouped ? 1u << 20 : 0) | (jk && grouped && gplanes ? 1u << 21 : 0) | (packed && packed_bits ? 32768 : 0) | (packed ? (uint32_t)(31 - __builtin_clz(std::max<uint32_t>(packed_rec, 2)) - 1) << 16 : 0);
+  r->fast_scan = (r->info.reserved & 1u) != 0;
+  // the pre-built scan over the bit-sliced planes: bit 26, with the bits of a predicate projection's bit-sliced form (and of the sets' truth tables);
+  // no register-resident kernel, no lanes form, no compiled kernel ran
+  if (sliced_prebuilt) r->info.reserved = (r->info.reserved & ~(1u | 2u | 32u)) | 1u << 26 | 1u << 4 | 1u << 11 | 1u << 13 | (has_set ? 1u << 22 | 1u << 25 : 0u);
   if (r->hp_chunks) memset(x->h_chunk, 0, VH_HP_CHUNKS * sizeof(unsigned long long));      // (what the context's previous query left there)
   // a second pass over heavy level-A partitions of a hashed partitioning: from the first pass's tuples when this plan's table can take them as
   // they are (one key word laid out as the first pass's, narrow ids) — else from the table's rows behind the bitmap, like any heavy range

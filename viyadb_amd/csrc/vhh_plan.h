@@ -281,6 +281,15 @@ struct QueryBuild {
   std::vector<int> pp_cols;                      // the filter's columns (ascending) when every leaf reads a fixed-width column: what a predicate projection must hold
   int pp_boff[VJ_MAX_PRED] = {}, pp_bbits[VJ_MAX_PRED] = {}, pp_soff[VJ_MAX_PRED] = {}, pp_sbits[VJ_MAX_PRED] = {};      // predicate column k's bit field in the byte-plane / bit-sliced projection noted in jshape
   void predpack_auto(bool want_sliced);          // counts this query towards an unasked predicate projection of the form it would have used
+  // The pre-built scan over the bit-sliced planes (scan_agg_sliced_kernel; opt-in: VH_PLAN_SLICED_PREBUILT, or VH_SLICED_PREBUILT=1 for the process).
+  bool planes_want = false;                      // shape_filter: the plan asks for it and has a filter — look for the projection even where no kernel is to be compiled
+  bool planes_ready = false;                     // snapshot_segments: the select's rule holds; the program over the planes' fields has its place in the plan block ...
+  size_t planes_word = 0;                        // ... at this u32 word
+  VhBitsProg planes_prog{};
+  bool sliced_prebuilt = false;                  // decompose_work: ... and no compiled kernel runs the query, which has not settled on a form that keeps its own kernels
+  VhSlicedRef planes_ref{};                      // layout_scratch: the kernel's view of program and planes
+  bool bits_prog_fill(VhBitsProg* B) const;      // the program of jshape over the fields of sliced_use (false: a leaf the planes cannot answer); the select shares it
+  void choose_sliced_prebuilt();
   VhJitKernel* jk = nullptr;
   bool build_pending = false;                    // background build mode: a job for this query's shape is queued or running (vh_result_info.reserved bit 19)
   int jit_block = 256;
@@ -525,18 +534,22 @@ int QueryBuild::shape_filter() {
   // A select (plan_only) compiles nothing: it takes this shape only to find the bit-sliced projection its pre-built kernels interpret the
   // program on (snapshot_segments), so neither the JIT policy nor the plan's JIT flags bear on it.
   const bool jit_allowed = vh_jit_policy() != VH_JIT_OFF && !(p->flags & (VH_PLAN_NO_JIT | VH_PLAN_NO_FAST));
-  jit_try = (jit_allowed || plan_only) && prog.size() <= VH_INLINE_PROG && r->h_lits.size() <= VH_INLINE_LITS;
-  if (jit_try) {
+  // An aggregate that asks for the pre-built scan over the planes (VH_PLAN_SLICED_PREBUILT) takes the shape for the same reason as the select, and
+  // attempts no compile for it either: planes_want opens the search below, jit_try stays what the JIT policy and the plan's flags make it.
+  planes_want = !plan_only && p->nfilter > 0 && ((p->flags & VH_PLAN_SLICED_PREBUILT) || knobs().sliced_prebuilt) &&
+                !(p->flags & (VH_PLAN_NO_SLICED | VH_PLAN_NO_PREDPACK | VH_PLAN_NO_NARROW));
+  bool shaped = (jit_allowed || plan_only || planes_want) && prog.size() <= VH_INLINE_PROG && r->h_lits.size() <= VH_INLINE_LITS;
+  if (shaped) {
     jshape.prog = prog;
     int nv = 0;
     for (VhProgOp& o : jshape.prog) {
       if (o.kind() != VH_F_REL && o.kind() != VH_F_IN && o.kind() != VH_F_INSET) continue;
       const int es = vh_elem_size((int)o.type());
-      if (!es) { jit_try = false; break; }                       // a bitset metric's cardinality: the generic kernel
+      if (!es) { shaped = false; break; }                        // a bitset metric's cardinality: the generic kernel
       int ps = -1;
       for (int k = 0; k < jshape.npred; ++k) if (jshape.pred[k].slot == (int)o.slot()) ps = k;
       if (ps < 0) {
-        if (jshape.npred >= VJ_MAX_PRED || nv + VH_SUBSTEPS * es > VJ_MAX_NV) { jit_try = false; break; }
+        if (jshape.npred >= VJ_MAX_PRED || nv + VH_SUBSTEPS * es > VJ_MAX_NV) { shaped = false; break; }
         ps = jshape.npred++;
         jshape.pred[ps] = VhJitPred{(int)o.slot(), (int)o.type(), es};
         jit_pred_col[ps] = slot_col[o.slot()];
@@ -546,6 +559,8 @@ int QueryBuild::shape_filter() {
     }
     jshape.nlits = (int)r->h_lits.size();
   }
+  jit_try = shaped && (jit_allowed || plan_only);
+  planes_want &= shaped;
 
   // Bit-packed predicate projections (vh_table_predpack) of the filter's columns: the byte-plane form serves every compiled kernel form,
   // the bit-sliced one the compacting kernels. Both are noted here when they exist; compile_kernel picks (the no-compaction form and the
@@ -553,13 +568,13 @@ int QueryBuild::shape_filter() {
   // for the queries to come (predpack_auto).
   bool jit_predpack = false;
   pp_cols.clear();
-  if (jit_try && jshape.npred > 0 && !(p->flags & (VH_PLAN_NO_NARROW | VH_PLAN_NO_PREDPACK))) {
+  if ((jit_try || planes_want) && jshape.npred > 0 && !(p->flags & (VH_PLAN_NO_NARROW | VH_PLAN_NO_PREDPACK))) {
     bool all_cols = true;
     for (int k = 0; k < jshape.npred; ++k) { all_cols &= jit_pred_col[k] >= 0; pp_cols.push_back(jit_pred_col[k]); }
     std::sort(pp_cols.begin(), pp_cols.end());
     pp_cols.erase(std::unique(pp_cols.begin(), pp_cols.end()), pp_cols.end());
     if (!all_cols) pp_cols.clear();
-    VhPredPack* pb = all_cols ? predpack_usable(t, pp_cols, 0) : nullptr;
+    VhPredPack* pb = all_cols && jit_try ? predpack_usable(t, pp_cols, 0) : nullptr;      // (byte planes: the compiled kernels' alone)
     VhPredPack* ps = all_cols ? predpack_usable(t, pp_cols, 1) : nullptr;
     // (bit-serial comparisons cannot look a member up: a set leaf on bit planes is a truth table over its field, 2^bits bits of it — narrow fields
     // only; a plan with a set leaf on a wider one wants the row's value: byte planes, narrow copies, arenas)
@@ -645,6 +660,25 @@ int QueryBuild::shape_filter() {
   return VH_OK;
 }
 
+// The filter program as the pre-built readers of the bit-sliced planes interpret it (vh_bits_eval.h): jshape's program with every leaf's field
+// of the projection shape_filter found (pp_soff / pp_sbits). The select and the aggregate scan over the planes share it; `set` is filled
+// in once the plan block has its place. false: a leaf of a type or on a field the planes cannot answer.
+bool QueryBuild::bits_prog_fill(VhBitsProg* Bp) const {
+  VhBitsProg& B = *Bp;
+  B = VhBitsProg{};
+  B.nprog = (int32_t)jshape.prog.size(); B.flat = P.prog_flat;
+  bool ok = true;
+  for (size_t k = 0; k < jshape.prog.size(); ++k) {
+    const VhProgOp& o = jshape.prog[k];
+    const bool leaf = o.kind() == VH_F_REL || o.kind() == VH_F_IN || o.kind() == VH_F_INSET;
+    const int ps = leaf ? (int)o.pslot() : 0;
+    if (leaf) ok &= o.type() <= VH_I64 && pp_sbits[ps] >= 1 && pp_sbits[ps] <= VH_BITS_MAX_FIELD;
+    B.op[k] = vh_bits_op(o.kind(), o.type(), o.op(), o.count(), o.lit(), leaf ? (uint32_t)pp_soff[ps] : 0u, leaf ? (uint32_t)pp_sbits[ps] : 0u);
+  }
+  std::copy(r->h_lits.begin(), r->h_lits.end(), B.lits);
+  return ok;
+}
+
 int QueryBuild::snapshot_segments() {
   int rc = VH_OK;
   // ---------------- segments: snapshot + skip
@@ -654,6 +688,11 @@ int QueryBuild::snapshot_segments() {
   r->set_desc_word = plan_words;
   plan_words += r->h_sets.size() * (sizeof(VhSetDev) / sizeof(uint32_t));                                                  // the descriptors (vh_result::place_sets fills them in), then the tables
   for (size_t k = 0; k < r->h_sets.size(); ++k) { r->set_word[k] = plan_words; plan_words += r->h_sets[k].words.size(); }      // (every table an even number of words: 8-byte aligned)
+  // An aggregate that may read its filter off the bit-sliced planes through the pre-built scan (planes_want: shape_filter) keeps the program over the
+  // planes' fields behind the sets: beside VhPlanDev it would not fit the kernel arguments (vh_sliced.h). The select's rule, all but the last
+  // word, which waits for the organisation and the compile (choose_sliced_prebuilt).
+  static_assert(sizeof(VhBitsProg) % 8 == 0, "the plan block's parts are 8-byte aligned");
+  if (planes_want && sliced_use && bits_prog_fill(&planes_prog)) { planes_ready = true; planes_word = plan_words; plan_words += sizeof(VhBitsProg) / sizeof(uint32_t); }
   rc = ensure_segrows(x, plan_words);
   if (rc) { return rc; }
   memcpy(x->h_segrows + seg_words, prog.data(), prog.size() * sizeof(VhProgOp));
@@ -679,19 +718,7 @@ int QueryBuild::snapshot_segments() {
     // set leaf's field has a truth table), a filter to evaluate, none of the flags that keep a plan off the planes: the select reads the planes
     // (select_count_sliced_kernel / select_emit_sliced_kernel). It stamps the projection like an aggregate that settled on it; it builds nothing.
     if (sliced_use && p->nfilter > 0 && !(p->flags & (VH_PLAN_NO_SLICED | VH_PLAN_NO_PREDPACK | VH_PLAN_NO_NARROW))) {
-      VhBitsProg& B = r->sel_prog;
-      B = VhBitsProg{};
-      B.nprog = (int32_t)jshape.prog.size(); B.flat = P.prog_flat;
-      bool ok = true;
-      for (size_t k = 0; k < jshape.prog.size(); ++k) {
-        const VhProgOp& o = jshape.prog[k];
-        const bool leaf = o.kind() == VH_F_REL || o.kind() == VH_F_IN || o.kind() == VH_F_INSET;
-        const int ps = leaf ? (int)o.pslot() : 0;
-        if (leaf) ok &= o.type() <= VH_I64 && pp_sbits[ps] >= 1 && pp_sbits[ps] <= VH_BITS_MAX_FIELD;
-        B.op[k] = vh_bits_op(o.kind(), o.type(), o.op(), o.count(), o.lit(), leaf ? (uint32_t)pp_soff[ps] : 0u, leaf ? (uint32_t)pp_sbits[ps] : 0u);
-      }
-      std::copy(r->h_lits.begin(), r->h_lits.end(), B.lits);
-      if (ok) {
+      if (bits_prog_fill(&r->sel_prog)) {
         r->sel_sliced = true;
         r->sel_planes = sliced_use->plane[0].ptr; r->sel_stride = sliced_use->plane[0].stride; r->sel_pitch = sliced_use->pitch;
         layout_use(t, sliced_use);

@@ -66,6 +66,7 @@ extern "C" int vh_segment_stats(vh_table* t, uint32_t seg, int32_t col, vh_anynu
 
 // ------------------------------------------------------------------ results
 struct vh_result {
+  bool fast_scan = false;           // a register-resident scan was planned (vh_result_info.reserved bit 0, before a pre-built scan over the bit-sliced planes cleared it): replan_after probes the selectivity
   bool hpart = false;               // hashed partitioning ran: the table is a compact list of group records ...
   uint32_t part_blocks = 0;         // DENSE_PART: blocks of the phase-2 launch (what vh_part_shares shares out)
   bool hp_direct = false;           // ... or its aggregation kernel already wrote the output columns (no emission kernel to run)

@@ -105,7 +105,7 @@ static int select_count_locked(vh_table* t, VhExec* x, const vh_select_plan* sp,
   if (sliced) {
     VhSelectSliced& A = s->A;
     A.B = pr->sel_prog; A.B.set = P.set;
-    A.planes = pr->sel_planes; A.stride = pr->sel_stride; A.pitch = pr->sel_pitch;
+    A.L.planes = pr->sel_planes; A.L.stride = pr->sel_stride; A.L.pitch = pr->sel_pitch;
     A.seg_rows = P.seg_rows; A.counters = P.counters; A.nseg = nseg;
   }
   HIP_TRY(hipEventRecord(x->ev[1], st));

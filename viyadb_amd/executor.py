@@ -98,6 +98,7 @@ class AggResult:
     inset: bool = False            # the filter's "inset" leaves were evaluated by set lookup
     inset_search: bool = False     # ... at least one of them by binary search in a sorted array (the others: one bit of a bitmap)
     inset_sliced: bool = False     # ... or, instead, all of them from truth tables on the bit-sliced predicate planes (no lookup per row)
+    sliced_prebuilt: bool = False  # a pre-built scan read the filter off the bit-sliced predicate planes (PLAN_SLICED_PREBUILT / VH_SLICED_PREBUILT=1)
 
 
 
@@ -420,7 +421,7 @@ class DeviceTable:
                          (2 << ((info.reserved >> 16) & 7)) if info.reserved & 8 else 0,
                          bool(info.reserved & capi.INFO_GROUPED_PAYLOAD), bool(info.reserved & capi.INFO_GROUPED_PLANES),
                          bool(info.reserved & capi.INFO_INSET), bool(info.reserved & capi.INFO_INSET_SEARCH),
-                         bool(info.reserved & capi.INFO_INSET_SLICED))
+                         bool(info.reserved & capi.INFO_INSET_SLICED), bool(info.reserved & capi.INFO_SLICED_PREBUILT))
 
     def query_agg(self, plan: AggPlan, copy: bool = True) -> AggResult:
         p, keep = self._build_plan(plan)
