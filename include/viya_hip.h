@@ -234,6 +234,13 @@ enum vh_plan_flags {
   VH_PLAN_CARD32 = 1u << 22       /* the cardinality of a 32-bit-id bitset metric (count distinct) is delivered as a uint32 column instead of
                                      uint64 (it cannot exceed 2^32 - 1): vh_result_state_elem() tells what a state column holds */
 };
+/* vh_plan.flags2: all 32 bits of `flags` are taken. */
+enum vh_plan_flags2 {
+  VH_PLAN2_PLANE_AGG = 1u << 0    /* opt-in: an aggregate of few groups that no compiled kernel answers is computed ON the bit-sliced planes —
+                                     sums and min / max by popcount, no row materialised (scan_agg_planes_kernel; the rule: "Aggregates on
+                                     the bit-sliced planes" below; VH_PLANE_AGG=1 in the environment sets it for every aggregate of the
+                                     process that is not a vh_query_agg_sharded call) */
+};
 typedef struct vh_plan {
   const vh_filter_node* filter; int32_t nfilter;   /* postfix program        */
   const vh_anynum* lits;        int32_t nlits;
@@ -250,7 +257,7 @@ typedef struct vh_plan {
    * `lits`, but `col` is a RESULT column: i < ngroups = group column i, else metric (col - ngroups) of this
    * plan. Semantics of post_agg.cc:77-83: AVG compares its raw sum, a bitset its cardinality. Only groups that
    * pass are returned; vh_result_info.ngroups still counts every group (agg_map.size()). */
-  const vh_filter_node* having; int32_t nhaving; int32_t reserved2;
+  const vh_filter_node* having; int32_t nhaving; uint32_t flags2;   /* enum vh_plan_flags2 (was reserved: 0) */
   /* Optional device-side top-N, for `sort` + `limit` whose FIRST sort column is numeric (the
    * reference's INTEGER / FLOAT sort types, src/db/column.h:198-200,270-272; not string, time, boolean or AVG
    * columns, whose order is an order of formatted strings): top_k = skip + limit (0 = off), top_col = RESULT
@@ -307,7 +314,10 @@ typedef struct vh_result_info {
                                         this query ran on what existed (the pre-built kernels, the arenas, layouts already there);
                                 bit 24: (tables with a layout budget) planning this query evicted at least one derived layout;
                                 bit 26: a PRE-BUILT scan read the filter off the bit-sliced predicate planes (VH_PLAN_SLICED_PREBUILT: bits 4, 11
-                                        and 13 are set too, bits 22 and 25 when the filter has VH_F_INSET leaves; bits 0, 1 and 5 are clear) */
+                                        and 13 are set too, bits 22 and 25 when the filter has VH_F_INSET leaves; bits 0, 1 and 5 are clear);
+                                bit 27: the aggregate was computed ON the bit-sliced planes, sums and min / max by popcount (VH_PLAN2_PLANE_AGG:
+                                        bits 4, 11 and 13 are set too, bits 22 and 25 when the filter has VH_F_INSET leaves; bits 0, 1, 5 and 26
+                                        are clear, and so are the projection's bits 3, 7 and 15-18: no payload is gathered) */
   uint64_t returned_groups;  /* rows vh_result_copy delivers (= ngroups without HAVING) */
 } vh_result_info;
 
@@ -654,7 +664,29 @@ VH_API int vh_query_agg_sharded(vh_table* t, const vh_plan* plan, vh_comm* comm,
  * has not settled on a no-compaction (lanes) form, nor — for the partitioned dense organisation — on one-word tuples, which keep their
  * kernels. The flag changes which kernel evaluates the predicate and nothing else: path, table organisation, tuple format
  * and result are those of the same plan without it, so sharded ranks keep agreeing. The query stamps and holds the projection like the
- * select; it builds and queues no layout. vh_result_info.reserved bit 26 tells. Without flag and variable nothing is different. */
+ * select; it builds and queues no layout. vh_result_info.reserved bit 26 tells. Without flag and variable nothing is different.
+ *
+ * Aggregates on the bit-sliced planes. The readers above take only the PREDICATE from the planes and turn every survivor back into a row.
+ * scan_agg_planes_kernel computes the aggregate itself there: with the pass mask m of 32 rows and a metric's field in planes x[0 .. nb), a
+ * SUM is the sum over b of popcount(m & x[b]) << b, MIN and MAX a narrowing of m from the top plane down, and the rows of a group are those
+ * whose group columns' fields equal its values. No row is materialised; the bytes read are the bits of the fields involved, whatever
+ * passes. A query takes this path when all of this holds:
+ *  - it was asked for — VH_PLAN2_PLANE_AGG in vh_plan.flags2, or VH_PLANE_AGG=1 in the environment (read once per process) — and is not a
+ *    vh_query_agg_sharded call (sharded queries ignore the switch);
+ *  - no compiled kernel runs the query (the cases listed for VH_PLAN_SLICED_PREBUILT above);
+ *  - the organisation is the dense LDS table (VH_PATH_DENSE_LDS, VH_PATH_SCALAR) with at most 64 group ids: the loop over the ids is paid
+ *    per plane word, so this bounds the design, it is not a tuned figure;
+ *  - the filter is empty, or satisfies the select's conditions above on ONE usable bit-sliced projection F (every leaf's column a field, the
+ *    inline budget, set leaves on fields of at most 10 bits); none of VH_PLAN_NO_SLICED / VH_PLAN_NO_PREDPACK / VH_PLAN_NO_NARROW is set;
+ *  - ONE usable, current bit-sliced projection V holds every group column and every metric's source column, the hidden count included
+ *    when the plan carries one (V may be F);
+ *  - no group column has a granularity or rollup rules;
+ *  - every metric is an integer SUM, COUNT, AVG, MIN or MAX: no float or double metric, no bitset metric, no VH_COL_ROWID (a column with
+ *    negative values has no field, so it is in no projection).
+ * Whether the plan had settled on the no-compaction (lanes) form plays no part. When both this and VH_PLAN_SLICED_PREBUILT apply, this wins.
+ * It changes which kernel fills the same LDS table and nothing else: organisation, states (a u32 sum wraps as before), HAVING, top-N and
+ * delivery are those of the same plan without the switch. The query stamps F and V (vh_layout_info.uses) and holds them against eviction
+ * while it runs; it builds and queues no layout. vh_result_info.reserved bit 27 tells. */
 #define VH_COL_ROWID (-2)
 typedef struct vh_rows vh_rows;
 typedef struct vh_select_plan {

@@ -38,6 +38,7 @@ PLAN_NO_GROUPED = 1 << 28
 PLAN_NO_GPLANES = 1 << 29
 PLAN_SET_SEARCH = 1 << 30         # testing: every set of an F_INSET leaf takes the sorted-array form
 PLAN_SLICED_PREBUILT = 1 << 31    # opt-in: an aggregate no compiled kernel answers reads its filter off the bit-sliced planes (scan_agg_sliced_kernel)
+PLAN2_PLANE_AGG = 1 << 0          # vh_plan.flags2 (enum vh_plan_flags2). Opt-in: an aggregate of few groups is computed on the bit-sliced planes (scan_agg_planes_kernel)
 # paths
 PATH_SCALAR, PATH_DENSE_LDS, PATH_DENSE_GLOBAL, PATH_HASH, PATH_DENSE_PART = range(5)
 PATH_NAMES = ["scalar", "dense_lds", "dense_global", "hash", "dense_part"]
@@ -73,7 +74,7 @@ class Plan(C.Structure):
                 ("metrics", C.POINTER(C.c_int32)), ("nmetrics", C.c_int32),
                 ("seg_rows", C.POINTER(C.c_uint64)), ("nseg", C.c_uint32),
                 ("flags", C.c_uint32), ("groups_hint", C.c_uint64),
-                ("having", C.POINTER(FilterNode)), ("nhaving", C.c_int32), ("reserved2", C.c_int32),
+                ("having", C.POINTER(FilterNode)), ("nhaving", C.c_int32), ("flags2", C.c_uint32),
                 ("top_col", C.c_int32), ("top_desc", C.c_int32), ("top_k", C.c_uint64)]
 
 
@@ -147,6 +148,7 @@ INFO_INSET = 1 << 22              # vh_result_info.reserved bit 22: the filter's
 INFO_INSET_SEARCH = 1 << 23       # ... bit 23: at least one of them by binary search in a sorted array
 INFO_INSET_SLICED = 1 << 25       # ... bit 25: all of them from truth tables on the bit-sliced predicate planes instead (no lookup per row)
 INFO_SLICED_PREBUILT = 1 << 26    # ... bit 26: a pre-built scan read the filter off the bit-sliced predicate planes (bits 4, 11 and 13 are set too)
+INFO_PLANE_AGG = 1 << 27          # ... bit 27: the aggregate was computed on the bit-sliced planes (bits 4, 11 and 13 are set too; bits 0, 1, 5 and 26 are clear)
 INFO_EVICTED = 1 << 24            # ... bit 24: planning this query evicted at least one derived layout (tables with a layout budget)
 
 

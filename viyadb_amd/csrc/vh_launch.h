@@ -15,6 +15,9 @@ void vh_launch_scan_fast_part(const VhPlanDev& P, int grid, size_t lds, hipStrea
 struct VhSlicedRef;
 // the pre-built scan over the bit-sliced predicate planes (vh_sliced.h), whatever the organisation: `mode` picks the sink
 void vh_launch_scan_sliced(int mode, const VhPlanDev& P, const VhSlicedRef& A, uint32_t chunks_per_seg, int grid, size_t lds, bool xcd_private, hipStream_t s, int* occ = nullptr);
+struct VhPlaneAggRef;
+// the aggregate scan ON the bit-sliced planes (vh_sliced.h): DENSE_LDS plans of at most VH_PLANE_AGG_MAX_GROUPS ids, sums and min / max by popcount
+void vh_launch_scan_planes(const VhPlanDev& P, const VhPlaneAggRef& A, uint32_t chunks_per_seg, int grid, size_t lds, bool xcd_private, hipStream_t s, int* occ = nullptr);
 void vh_launch_part_agg(const VhPlanDev& P, int blocks_per_part, size_t lds, hipStream_t s);
 void vh_launch_part_split(const VhPlanDev& P, int blocks_per_part, bool ring, hipStream_t s);
 struct VhHpArgs;

@@ -1,0 +1,105 @@
+// The aggregate scan ON the bit-sliced predicate planes: the fourth reader of the planes, and the first that turns no survivor back into a
+// row. The filter program gives the pass mask of a lane's 32 rows (vh_bits_eval.h, over projection F); the group columns' fields give the rows
+// of every group id; a SUM is Σ_b popcount(rows & plane b) << b over the metric's field, MIN / MAX a narrowing of the rows from the top
+// plane down (vh_bits_agg.h, over projection V). No queue, no gather, no state update per row: the bytes read are the bits of the fields
+// involved, whatever passes. Serves the DENSE_LDS organisation (scalar aggregates included) with at most VH_PLANE_AGG_MAX_GROUPS group ids,
+// integer SUM / COUNT / AVG / MIN / MAX states; QueryBuild::choose_plane_agg (vhh_launch.h) holds the rule.
+#include "vh_kernels.h"
+#include "vh_launch.h"
+#include "vh_sliced.h"
+#include "vh_bits_agg.h"
+#include "vh_wave_scan.h"
+
+// VhPlanDev by value as for every scan kernel, the two projections' places by value behind it; program and descriptor lie in the plan block
+// and are read through restrict pointers of their own (vh_sliced.h).
+static_assert(sizeof(VhPlanDev) + 2 * sizeof(void*) + 2 * sizeof(VhSlicedPlanes) + 8 <= 4096, "scan_agg_planes_kernel: plan and planes together exceed the 4 KB of kernel arguments");
+static_assert(VH_PLANE_AGG_MAX_GROUPS <= 64, "VhPlaneAggDesc::valid has a bit per group id");
+
+// scan_agg_sliced_kernel's walk: a wave takes 2048-row chunks (VhChunkWalk), lane l owns plane word l of the chunk. A skipped segment, a chunk
+// at or beyond the snapshot and a word at or beyond it are never read (vh_sliced_mask / vh_sliced_tail_mask); a lane none of whose rows pass
+// reads none of V either. Per word the lane loads every plane of V that a field of the plan covers ONCE, into an array that is indexed by
+// constants only (V has at most 32 planes: vh_bits_agg.h on the `_at` form). Then, per group id g — a loop whose every branch is on the plan,
+// so all 64 lanes are active in it, which the wave combination needs —: the lane's rows of g, nothing more to do when no lane has any, and
+// per metric the lane's partial result, combined across the wave (the DPP scans of vh_wave_scan.h) and added to
+// the block's LDS table by ONE lane: one LDS update per (chunk, group, metric) in place of one per row and metric.
+// A passing row that belongs to no id (a value outside the planned range, synced in since) raises VH_ERR_RANGE as vh_consume does: the
+// host plans again.
+template <int BLOCK, int SCOPE>
+__global__ __launch_bounds__(BLOCK) void scan_agg_planes_kernel(const VhPlanDev P, const VhBitsProg* __restrict__ B, const VhPlaneAggDesc* __restrict__ D,
+                                                                const VhSlicedPlanes F, const VhSlicedPlanes V, uint32_t chunks_per_seg) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  const int lane = threadIdx.x & 63;
+  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  vh_scan_table_init<VH_MODE_DENSE_LDS, BLOCK>(P, lds);
+
+  const uint32_t need = D->need, care = D->care, has_filter = D->has_filter;
+  const uint64_t valid = D->valid;
+  const uint32_t G = (uint32_t)P.G;                    // <= VH_PLANE_AGG_MAX_GROUPS
+  uint32_t npassed32 = 0;                              // per lane: 32 rows of every chunk this wave takes
+  bool range_err = false;
+
+  for (VhChunkWalk K(blockIdx.x, gridDim.x, (uint32_t)(BLOCK / 64), wave, chunks_per_seg); K.seg < P.nseg; K.next()) {
+    const uint32_t seg = K.seg;
+    const uint64_t base = K.base();
+    const uint32_t seg_rows = P.seg_rows[seg];
+    if (base >= seg_rows) continue;
+    const uint64_t row_l = base + (uint64_t)lane * 32u;
+    const uint32_t mask = has_filter ? vh_sliced_mask(*B, F, seg, base, seg_rows, lane) : vh_sliced_tail_mask(row_l, seg_rows);
+    npassed32 += __popc(mask);
+    if (__ballot(mask != 0u) == 0ull) continue;
+
+    uint32_t v[VH_BITS_MAX_FIELD];
+#pragma unroll
+    for (int p = 0; p < VH_BITS_MAX_FIELD; ++p) v[p] = 0u;
+    if (mask) {      // (mask != 0: the word begins below the snapshot)
+      const char* planes = V.planes + (uint64_t)seg * V.stride;      // (uniform: a plane's address is a scalar, the lane adds its word's 32-bit offset)
+      const uint32_t woff = (uint32_t)(row_l >> 5) * 4u;
+#pragma unroll
+      for (int p = 0; p < VH_BITS_MAX_FIELD; ++p)
+        if ((need >> p) & 1u) v[p] = VH_BITS_LOAD(planes + (uint64_t)p * V.pitch + woff);
+    }
+
+    uint32_t seen = 0u;
+#pragma unroll 1
+    for (uint32_t g = 0; g < G; ++g) {
+      if (__ballot((mask & ~seen) != 0u) == 0ull) break;      // every passing row of the wave's chunk has found its group
+      const uint32_t mg = ((valid >> g) & 1ull) ? (mask & vh_bits_match(v, care, D->pat[g])) : 0u;
+      seen |= mg;
+      if (__ballot(mg != 0u) == 0ull) continue;
+      const bool in = mg != 0u;
+#pragma unroll 1
+      for (int j = 0; j < P.nmetric; ++j) {
+        const VhMetricDev& m = P.m[j];
+        const int sop = (int)m.sop();
+        const uint32_t off = D->moff[j], nb = D->mbits[j];
+        // the lanes' partial results combined by DPP scans (vh_wave_scan.h; all lanes are active here): lane 63 ends up with the wave's. A
+        // field's value is an unsigned number of at most 32 bits, so MAX takes 0 from a lane without a row of g and MIN is the complement
+        // of the MAX of the complements.
+        uint64_t total;
+        bool empty;
+        if (sop == SOP_ADD32 || sop == SOP_ADD64) total = vh_wave_incl_add((unsigned long long)vh_bits_sum_at(v, off, nb, mg));
+        else if (sop == SOP_MIN_I32 || sop == SOP_MIN_U32 || sop == SOP_MIN_I64 || sop == SOP_MIN_U64) total = (uint32_t)~vh_wave_incl_max(in ? ~vh_bits_min_at(v, off, nb, mg, &empty) : 0u);
+        else total = vh_wave_incl_max(in ? vh_bits_max_at(v, off, nb, mg, &empty) : 0u);
+        if (lane == 63) vh_state_update<__HIP_MEMORY_SCOPE_WORKGROUP>(lds + m.lds_off, g, sop, total);
+      }
+      if (lane == 63) reinterpret_cast<uint8_t*>(lds + P.lds_present_off)[g] = 1;
+    }
+    range_err |= (mask & ~seen) != 0u;
+  }
+
+  if (__ballot(range_err) != 0ull && lane == 0) atomicOr(P.counters + 2, VH_ERR_RANGE);
+  unsigned long long npassed = npassed32;
+  for (int off = 32; off > 0; off >>= 1) npassed += __shfl_down(npassed, off);
+  vh_scan_block_end(P, npassed, 0ull, 0ull, 0u);
+  vh_scan_table_flush<VH_MODE_DENSE_LDS, BLOCK, SCOPE>(P, lds);
+}
+
+void vh_launch_scan_planes(const VhPlanDev& P, const VhPlaneAggRef& A, uint32_t chunks_per_seg, int grid, size_t lds, bool xcd_private, hipStream_t s, int* occ) {
+  constexpr int BLOCK = 256;       // (at 1024 threads a lane may hold 128 registers, a few fewer than the filter interpreter and the 32 plane words take: QueryBuild::decompose_work)
+  auto go = [&](auto k) {
+    if (occ) { if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, k, BLOCK, lds) != hipSuccess) *occ = 0; }
+    else hipLaunchKernelGGL(k, dim3(grid), dim3(BLOCK), lds, s, P, A.B, A.D, A.F, A.V, chunks_per_seg);
+  };
+  if (xcd_private) go(scan_agg_planes_kernel<BLOCK, __HIP_MEMORY_SCOPE_WORKGROUP>);
+  else go(scan_agg_planes_kernel<BLOCK, __HIP_MEMORY_SCOPE_AGENT>);
+}

@@ -1,6 +1,7 @@
 // vh_sliced.h — what the PRE-BUILT readers of the bit-sliced predicate planes share on the device: the kernel arguments that name the planes
 // and carry the filter program (vh_bits_eval.h), and a lane's pass mask for its word of a chunk (vh_sliced_walk.h). Included by the select
-// kernels (vh_small_kernels.h) and by the aggregate scan over the planes (vh_scan_sliced.hip).
+// kernels (vh_small_kernels.h), by the aggregate scan over the planes (vh_scan_sliced.hip) and by the one that also aggregates on them
+// (vh_scan_planes.hip).
 #pragma once
 #include "vh_internal.h"
 #include "vh_bits_eval.h"
@@ -28,6 +29,25 @@ struct VhSlicedArgs {
 struct VhSlicedRef {
   const VhBitsProg* B;
   VhSlicedPlanes L;
+};
+// The aggregate scan ON the planes (vh_scan_planes.hip: scan_agg_planes_kernel) reads two projections: F, whose fields the filter program
+// compares, and V, which holds every group column and every metric's source column (V may be F). Where their fields lie in V is this
+// descriptor's; it follows the program in the plan block and is passed as a restrict pointer of its own, for the reason given above.
+#define VH_PLANE_AGG_MAX_GROUPS 64      // group ids of a plan that takes the path: the loop over ids is paid per plane word
+struct VhPlaneAggDesc {
+  uint32_t has_filter;            // 0: no program, every row of the snapshot passes
+  uint32_t need;                  // bit p: plane p of V belongs to a group column's or a metric's field (the others are not read)
+  uint32_t care;                  // bit p: ... to a group column's
+  uint32_t pad;
+  uint64_t valid;                 // bit g: every group column's value of id g lies within its field (else no row can belong to g)
+  uint32_t pat[VH_PLANE_AGG_MAX_GROUPS];      // id g: the group columns' values (VhGroupDev::lo + digit) at their fields' places (vh_bits_match)
+  uint32_t goff[VH_MAX_GROUP], gbits[VH_MAX_GROUP];       // group column i: first plane and planes of its field in V (what pat and care were made of)
+  uint32_t moff[VH_MAX_METRIC], mbits[VH_MAX_METRIC];     // metric j (VhPlanDev::m[j], the hidden count included): ... of its source column's field
+};
+struct VhPlaneAggRef {
+  const VhBitsProg* B;            // nullptr: no filter
+  const VhPlaneAggDesc* D;
+  VhSlicedPlanes F, V;
 };
 
 #if defined(__HIPCC__)

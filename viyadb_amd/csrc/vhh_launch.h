@@ -302,17 +302,79 @@ int QueryBuild::compile_kernel() {
 // tshift, and never looks at the second digit a one-column shape plan adds.)
 // It only changes which kernel evaluates the predicate. The projection is stamped and held like a compiled reader's; nothing is built or queued.
 void QueryBuild::choose_sliced_prebuilt() {
-  if (!planes_ready || jk || lanes || hpart || g_heavy.only || !sliced_use || sliced_use->applied_epoch != t->sync_epoch) return;
+  if (!sliced_asked || plane_agg || !planes_ready || jk || lanes || hpart || g_heavy.only || !sliced_use || sliced_use->applied_epoch != t->sync_epoch) return;
   if (mode == VH_MODE_DENSE_PART && (!fast || P.gid_bits)) return;
   sliced_prebuilt = true;
   layout_use(t, sliced_use);
+}
+
+// The aggregate is computed ON the bit-sliced planes (scan_agg_planes_kernel; include/viya_hip.h states the rule, "Aggregates on the bit-sliced
+// planes"): asked for and not a sharded query (pagg_want), no compiled kernel after all, the dense LDS table with at most VH_PLANE_AGG_MAX_GROUPS
+// ids, no filter or the select's rule on one current projection F (planes_ready), plain group columns, integer SUM / COUNT / AVG / MIN / MAX states
+// only, and ONE usable, current bit-sliced projection V with every group column and every metric's source column, the hidden count included
+// (F itself when it has them). Whether the plan settled on the lanes form plays no part. It only changes which kernel fills the block's LDS
+// table. F and V are stamped and held; nothing is built or queued.
+void QueryBuild::choose_plane_agg() {
+  if (!pagg_want || jk || mode != VH_MODE_DENSE_LDS || P.G > VH_PLANE_AGG_MAX_GROUPS || P.nbitset) return;
+  VhPredPack* f = nullptr;
+  if (pagg_filter) {
+    if (!planes_ready || !sliced_use || sliced_use->applied_epoch != t->sync_epoch) return;
+    f = sliced_use;
+  }
+  std::vector<int> cols;
+  for (int i = 0; i < P.ngroup; ++i) {
+    if (P.g[i].gran() != VH_T_NONE || P.g[i].nroll()) return;
+    cols.push_back(p->groups[i].col);
+  }
+  for (int j = 0; j < P.nmetric; ++j) {
+    const int sop = (int)P.m[j].sop();
+    const bool integer = sop == SOP_ADD32 || sop == SOP_ADD64 || (sop >= SOP_MIN_I32 && sop <= SOP_MAX_U64);
+    if (!integer || P.m[j].slot() == VH_SLOT_ROWID || metric_col[j] < 0) return;
+    cols.push_back(metric_col[j]);
+  }
+  std::sort(cols.begin(), cols.end());
+  cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
+  if (cols.empty()) return;
+  VhPredPack* v = f && std::includes(f->cols.begin(), f->cols.end(), cols.begin(), cols.end()) ? f : predpack_usable(t, cols, 1);
+  if (!v || !v->sliced || v->bits > VH_BITS_MAX_FIELD || v->applied_epoch != t->sync_epoch) return;
+
+  VhPlaneAggDesc& D = pagg_desc;
+  D = VhPlaneAggDesc{};
+  D.has_filter = pagg_filter ? 1u : 0u;
+  auto field = [&](int col, uint32_t* off, uint32_t* bits) {
+    const size_t at = (size_t)(std::find(v->cols.begin(), v->cols.end(), col) - v->cols.begin());
+    *off = v->bitoff[at]; *bits = v->bitw[at];
+    return (*bits >= 32u ? ~0u : (1u << *bits) - 1u) << *off;
+  };
+  for (int i = 0; i < P.ngroup; ++i) D.care |= field(p->groups[i].col, &D.goff[i], &D.gbits[i]);
+  D.need = D.care;
+  for (int j = 0; j < P.nmetric; ++j) D.need |= field(metric_col[j], &D.moff[j], &D.mbits[j]);
+  for (uint64_t g = 0; g < P.G; ++g) {      // id g's digits -> the values its rows hold, at their fields' places
+    uint32_t pat = 0;
+    bool fits = true;
+    for (int i = 0; i < P.ngroup; ++i) {
+      const uint64_t value = P.g[i].lo + (g / P.g[i].stride) % P.g[i].extent;
+      if (value >> D.gbits[i]) fits = false;      // beyond the field: no row holds it
+      else pat |= (uint32_t)value << D.goff[i];
+    }
+    D.pat[g] = pat;
+    if (fits) D.valid |= 1ull << g;
+  }
+  plane_agg = true;
+  pagg_v = v;
+  if (f) layout_use(t, f);
+  layout_use(t, v);
 }
 
 void QueryBuild::scan_dispatch(int grid_, int* occ) {
   const size_t qb = (size_t)(BLOCK / 64) * VhScanCfg<256>::kQueueCap * sizeof(uint32_t);
   const size_t lds_ = ((mode == VH_MODE_DENSE_LDS || mode == VH_MODE_HASH) ? lds_table : 0) + qb;
   hipStream_t s_ = x->stream();
-  if (sliced_prebuilt) {
+  if (plane_agg) {      // (no queue: the block's LDS table alone)
+    const uint32_t cps = (uint32_t)std::max<uint64_t>(1, (t->padded_rows + VH_SLICED_CHUNK_ROWS - 1) / VH_SLICED_CHUNK_ROWS);
+    vh_launch_scan_planes(P, pagg_ref, cps, grid_, lds_table, nxcd > 1, s_, occ);
+  }
+  else if (sliced_prebuilt) {
     const uint32_t cps = (uint32_t)std::max<uint64_t>(1, (t->padded_rows + VH_SLICED_CHUNK_ROWS - 1) / VH_SLICED_CHUNK_ROWS);
     vh_launch_scan_sliced(mode, P, planes_ref, cps, grid_, mode == VH_MODE_DENSE_PART ? qb : lds_, nxcd > 1, s_, occ);
   }
@@ -342,9 +404,10 @@ int QueryBuild::decompose_work() {
   // variant pays for more blocks with more table merges at the end (blocks x groups x metrics global atomics), so
   // it keeps one 1024-thread block per CU unless the scan dwarfs that.
   const int env_lanes_block = knobs().lanes_block, env_bpc = knobs().blocks_per_cu, env_unit = knobs().unit_rows;
+  choose_plane_agg();           // (first: when both apply, the aggregate on the planes wins)
   choose_sliced_prebuilt();
-  BLOCK = jk ? jit_block : mode == VH_MODE_DENSE_LDS ? 1024 : 256;
-  if (mode == VH_MODE_DENSE_LDS && lanes) {
+  BLOCK = jk ? jit_block : mode == VH_MODE_DENSE_LDS && !plane_agg ? 1024 : 256;      // (the aggregate on the planes: 151 registers a lane, three 256-thread blocks per CU; its table has at most 64 groups to flush)
+  if (mode == VH_MODE_DENSE_LDS && lanes && !plane_agg) {
     if (env_lanes_block == 256 || env_lanes_block == 512 || env_lanes_block == 1024) BLOCK = env_lanes_block;
     else if ((uint64_t)g_ctx.num_cu * 5 * G * std::max(1, P.nmetric) <= rows_to_scan / 32) BLOCK = 256;
   }
@@ -352,7 +415,8 @@ int QueryBuild::decompose_work() {
   {   // the kernel symbol(s) this query runs, as rocprofv3 prints them (vh_result_kernel: bench.py's roofline.kernel)
     const int np_ = std::max(1, (int)P.npred), scope = (mode == VH_MODE_DENSE_GLOBAL || mode == VH_MODE_DENSE_LDS) && nxcd > 1 ? (int)__HIP_MEMORY_SCOPE_WORKGROUP : (int)__HIP_MEMORY_SCOPE_AGENT;
     char nm[160];
-    if (sliced_prebuilt) snprintf(nm, sizeof(nm), "scan_agg_sliced_kernel<%d, %d, %d>", mode, BLOCK, (mode == VH_MODE_HASH || mode == VH_MODE_DENSE_PART) ? (int)__HIP_MEMORY_SCOPE_AGENT : scope);
+    if (plane_agg) snprintf(nm, sizeof(nm), "scan_agg_planes_kernel<%d, %d>", BLOCK, scope);
+    else if (sliced_prebuilt) snprintf(nm, sizeof(nm), "scan_agg_sliced_kernel<%d, %d, %d>", mode, BLOCK, (mode == VH_MODE_HASH || mode == VH_MODE_DENSE_PART) ? (int)__HIP_MEMORY_SCOPE_AGENT : scope);
     else if (!fast) snprintf(nm, sizeof(nm), "scan_agg_kernel<%d, %d, %d>", mode, BLOCK, scope);
     else if (mode == VH_MODE_DENSE_PART && !lanes && P.shape) snprintf(nm, sizeof(nm), "scan_agg_shape_kernel<%d, %d, %d, %d, %d>", mode, BLOCK, (int)__HIP_MEMORY_SCOPE_AGENT, np_, P.shape);
     else snprintf(nm, sizeof(nm), "%s<%d, %d, %d, %d>", lanes ? "scan_agg_lanes_kernel" : "scan_agg_fast_kernel", mode, BLOCK,
@@ -626,6 +690,16 @@ int QueryBuild::layout_scratch() {
     planes_ref.B = reinterpret_cast<const VhBitsProg*>(S + o_segrows + planes_word * 4);
     planes_ref.L.planes = sliced_use->plane[0].ptr; planes_ref.L.stride = sliced_use->plane[0].stride; planes_ref.L.pitch = sliced_use->pitch;
   }
+  if (pagg_want) {         // the descriptor of the aggregate on the planes (zeros when the rule did not hold after all), and the kernel's view
+    memcpy(x->h_segrows + pagg_word, &pagg_desc, sizeof(VhPlaneAggDesc));
+    if (plane_agg) {
+      const VhPredPack* f = pagg_filter ? sliced_use : pagg_v;
+      pagg_ref.B = pagg_filter ? reinterpret_cast<const VhBitsProg*>(S + o_segrows + planes_word * 4) : nullptr;
+      pagg_ref.D = reinterpret_cast<const VhPlaneAggDesc*>(S + o_segrows + pagg_word * 4);
+      pagg_ref.F.planes = f->plane[0].ptr; pagg_ref.F.stride = f->plane[0].stride; pagg_ref.F.pitch = f->pitch;
+      pagg_ref.V.planes = pagg_v->plane[0].ptr; pagg_ref.V.stride = pagg_v->plane[0].stride; pagg_ref.V.pitch = pagg_v->pitch;
+    }
+  }
   if (mode == VH_MODE_HASH) {
     P.hkeys = reinterpret_cast<uint64_t*>(S + o_hkeys);
     P.htags = P.key_words > 1 ? reinterpret_cast<uint32_t*>(S + o_htags) : nullptr;
@@ -789,6 +863,9 @@ int QueryBuild::launch() {
   // the pre-built scan over the bit-sliced planes: bit 26, with the bits of a predicate projection's bit-sliced form (and of the sets' truth tables);
   // no register-resident kernel, no lanes form, no compiled kernel ran
   if (sliced_prebuilt) r->info.reserved = (r->info.reserved & ~(1u | 2u | 32u)) | 1u << 26 | 1u << 4 | 1u << 11 | 1u << 13 | (has_set ? 1u << 22 | 1u << 25 : 0u);
+  // the aggregate computed on the planes: bit 27 with the same company, and without bit 26; it gathers no payload, so the projection's bits
+  // (3, 7, 15-18) are clear whatever choose_projection had found
+  if (plane_agg) r->info.reserved = (r->info.reserved & ~(1u | 2u | 32u | 1u << 26 | 8u | 128u | 32768u | 7u << 16)) | 1u << 27 | 1u << 4 | 1u << 11 | 1u << 13 | (has_set ? 1u << 22 | 1u << 25 : 0u);
   if (r->hp_chunks) memset(x->h_chunk, 0, VH_HP_CHUNKS * sizeof(unsigned long long));      // (what the context's previous query left there)
   // a second pass over heavy level-A partitions of a hashed partitioning: from the first pass's tuples when this plan's table can take them as
   // they are (one key word laid out as the first pass's, narrow ids) — else from the table's rows behind the bitmap, like any heavy range

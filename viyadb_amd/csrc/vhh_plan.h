@@ -290,6 +290,17 @@ struct QueryBuild {
   VhSlicedRef planes_ref{};                      // layout_scratch: the kernel's view of program and planes
   bool bits_prog_fill(VhBitsProg* B) const;      // the program of jshape over the fields of sliced_use (false: a leaf the planes cannot answer); the select shares it
   void choose_sliced_prebuilt();
+  bool sliced_asked = false;                     // shape_filter: VH_PLAN_SLICED_PREBUILT / VH_SLICED_PREBUILT=1 (planes_want may be the aggregate on the planes' alone)
+  // The aggregate ON the bit-sliced planes (scan_agg_planes_kernel; opt-in: VH_PLAN2_PLANE_AGG, or VH_PLANE_AGG=1 for the process). Its filter is the
+  // program above (planes_prog over sliced_use = F), or none.
+  bool pagg_want = false;                        // shape_filter: asked for, not a sharded query, none of the flags that keep a plan off the planes
+  bool pagg_filter = false;                      // ... and the filter has a leaf (nodes that are always true alone: no program, as with no filter)
+  size_t pagg_word = 0;                          // snapshot_segments: the descriptor's u32 word in the plan block (behind the program)
+  VhPredPack* pagg_v = nullptr;                  // decompose_work: the projection that holds group and metric columns (V) ...
+  bool plane_agg = false;                        // ... and the rule holds: the kernel runs
+  VhPlaneAggDesc pagg_desc{};
+  VhPlaneAggRef pagg_ref{};                      // layout_scratch: the kernel's view of program, descriptor and the two projections
+  void choose_plane_agg();
   VhJitKernel* jk = nullptr;
   bool build_pending = false;                    // background build mode: a job for this query's shape is queued or running (vh_result_info.reserved bit 19)
   int jit_block = 256;
@@ -536,8 +547,13 @@ int QueryBuild::shape_filter() {
   const bool jit_allowed = vh_jit_policy() != VH_JIT_OFF && !(p->flags & (VH_PLAN_NO_JIT | VH_PLAN_NO_FAST));
   // An aggregate that asks for the pre-built scan over the planes (VH_PLAN_SLICED_PREBUILT) takes the shape for the same reason as the select, and
   // attempts no compile for it either: planes_want opens the search below, jit_try stays what the JIT policy and the plan's flags make it.
-  planes_want = !plan_only && p->nfilter > 0 && ((p->flags & VH_PLAN_SLICED_PREBUILT) || knobs().sliced_prebuilt) &&
-                !(p->flags & (VH_PLAN_NO_SLICED | VH_PLAN_NO_PREDPACK | VH_PLAN_NO_NARROW));
+  const bool planes_allowed = !plan_only && !(p->flags & (VH_PLAN_NO_SLICED | VH_PLAN_NO_PREDPACK | VH_PLAN_NO_NARROW));
+  sliced_asked = planes_allowed && p->nfilter > 0 && ((p->flags & VH_PLAN_SLICED_PREBUILT) || knobs().sliced_prebuilt);
+  // ... and so does one that asks to be computed on the planes (VH_PLAN2_PLANE_AGG), unless it has no filter: then it needs no program.
+  // Sharded queries (an agreed plan, a summary call, rows kept on the device for the exchange) ignore that switch.
+  pagg_want = planes_allowed && ((p->flags2 & VH_PLAN2_PLANE_AGG) || knobs().plane_agg) && !ag && !summary_out && !device_rows;
+  for (const VhProgOp& o : prog) pagg_filter |= o.kind() == VH_F_REL || o.kind() == VH_F_IN || o.kind() == VH_F_INSET;
+  planes_want = sliced_asked || (pagg_want && pagg_filter);
   bool shaped = (jit_allowed || plan_only || planes_want) && prog.size() <= VH_INLINE_PROG && r->h_lits.size() <= VH_INLINE_LITS;
   if (shaped) {
     jshape.prog = prog;
@@ -693,6 +709,11 @@ int QueryBuild::snapshot_segments() {
   // word, which waits for the organisation and the compile (choose_sliced_prebuilt).
   static_assert(sizeof(VhBitsProg) % 8 == 0, "the plan block's parts are 8-byte aligned");
   if (planes_want && sliced_use && bits_prog_fill(&planes_prog)) { planes_ready = true; planes_word = plan_words; plan_words += sizeof(VhBitsProg) / sizeof(uint32_t); }
+  // ... and one that may be computed on the planes keeps the descriptor of its fields behind that (filled in by choose_plane_agg, once the
+  // organisation, the metrics and the compile are known)
+  static_assert(sizeof(VhPlaneAggDesc) % 8 == 0, "the plan block's parts are 8-byte aligned");
+  if (pagg_want && (!pagg_filter || planes_ready)) { plan_words = (plan_words + 1) / 2 * 2; pagg_word = plan_words; plan_words += sizeof(VhPlaneAggDesc) / sizeof(uint32_t); }
+  else pagg_want = false;
   rc = ensure_segrows(x, plan_words);
   if (rc) { return rc; }
   memcpy(x->h_segrows + seg_words, prog.data(), prog.size() * sizeof(VhProgOp));

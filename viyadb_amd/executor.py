@@ -60,6 +60,7 @@ class AggPlan:
     groups_hint: int = 0
     having: Sequence = ()          # same node tuples; `col` = result column (group i, or len(groups) + metric j)
     top: Optional[tuple] = None    # (result column, descending, k): device top-N superset (see include/viya_hip.h)
+    flags2: int = 0                # vh_plan.flags2 (capi.PLAN2_*)
 
 
 @dataclass
@@ -100,6 +101,10 @@ class AggResult:
     inset_sliced: bool = False     # ... or, instead, all of them from truth tables on the bit-sliced predicate planes (no lookup per row)
     sliced_prebuilt: bool = False  # a pre-built scan read the filter off the bit-sliced predicate planes (PLAN_SLICED_PREBUILT / VH_SLICED_PREBUILT=1)
 
+    @property
+    def plane_agg(self) -> bool:
+        """The aggregate was computed on the bit-sliced planes (PLAN2_PLANE_AGG / VH_PLANE_AGG=1): derived from `flags`, no field of its own."""
+        return bool(self.flags & capi.INFO_PLANE_AGG)
 
 
 class DeviceTable:
@@ -372,6 +377,7 @@ class DeviceTable:
             p.seg_rows = sa
             p.nseg = len(plan.seg_rows)
         p.flags = int(plan.flags)
+        p.flags2 = int(plan.flags2)
         p.groups_hint = int(plan.groups_hint)
         if hnodes:
             ha = (capi.FilterNode * len(hnodes))(*hnodes)
