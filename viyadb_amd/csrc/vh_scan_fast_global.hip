@@ -2,17 +2,10 @@
 #include "vh_kernels.h"
 #include "vh_launch.h"
 
-template <int SCOPE>
-static void launch_np(const VhPlanDev& P, int grid, size_t lds, hipStream_t s, int* occ) {
-  switch (P.npred) {
-    case 0: case 1: VH_LAUNCH_OR_OCC((scan_agg_fast_kernel<VH_MODE_DENSE_GLOBAL, 256, SCOPE, 1>), 256, grid, lds, s, P, occ); break;
-    case 2: VH_LAUNCH_OR_OCC((scan_agg_fast_kernel<VH_MODE_DENSE_GLOBAL, 256, SCOPE, 2>), 256, grid, lds, s, P, occ); break;
-    case 3: VH_LAUNCH_OR_OCC((scan_agg_fast_kernel<VH_MODE_DENSE_GLOBAL, 256, SCOPE, 3>), 256, grid, lds, s, P, occ); break;
-    default: VH_LAUNCH_OR_OCC((scan_agg_fast_kernel<VH_MODE_DENSE_GLOBAL, 256, SCOPE, 4>), 256, grid, lds, s, P, occ); break;
-  }
-}
-
-void vh_launch_scan_fast_global(const VhPlanDev& P, int grid, size_t lds, bool xcd_private, hipStream_t s, int* occ) {
-  if (xcd_private) launch_np<__HIP_MEMORY_SCOPE_WORKGROUP>(P, grid, lds, s, occ);
-  else launch_np<__HIP_MEMORY_SCOPE_AGENT>(P, grid, lds, s, occ);
+void vh_launch_scan_fast_global(const VhPlanDev& P, const VhScanLaunch& L, bool xcd_private) {
+  vh_with_scope(xcd_private, [&](auto scope) { vh_with_np(P.npred, [&](auto np) {
+    constexpr int SCOPE = decltype(scope)::value, NP = decltype(np)::value;
+    L.named("scan_agg_fast_kernel<%d, %d, %d, %d>", VH_MODE_DENSE_GLOBAL, 256, SCOPE, NP);
+    vh_launch_or_ask(L, scan_agg_fast_kernel<VH_MODE_DENSE_GLOBAL, 256, SCOPE, NP>, 256, true, P);
+  }); });
 }

@@ -2,17 +2,10 @@
 #include "vh_kernels.h"
 #include "vh_launch.h"
 
-template <int SCOPE>
-static void launch_np(const VhPlanDev& P, int grid, size_t lds, hipStream_t s) {
-  switch (P.npred) {
-    case 0: case 1: hipLaunchKernelGGL((scan_agg_fast_kernel<VH_MODE_DENSE_LDS, 1024, SCOPE, 1>), dim3(grid), dim3(1024), lds, s, P); break;
-    case 2: hipLaunchKernelGGL((scan_agg_fast_kernel<VH_MODE_DENSE_LDS, 1024, SCOPE, 2>), dim3(grid), dim3(1024), lds, s, P); break;
-    case 3: hipLaunchKernelGGL((scan_agg_fast_kernel<VH_MODE_DENSE_LDS, 1024, SCOPE, 3>), dim3(grid), dim3(1024), lds, s, P); break;
-    default: hipLaunchKernelGGL((scan_agg_fast_kernel<VH_MODE_DENSE_LDS, 1024, SCOPE, 4>), dim3(grid), dim3(1024), lds, s, P); break;
-  }
-}
-
-void vh_launch_scan_fast_lds(const VhPlanDev& P, int grid, size_t lds, bool xcd_private, hipStream_t s) {
-  if (xcd_private) launch_np<__HIP_MEMORY_SCOPE_WORKGROUP>(P, grid, lds, s);
-  else launch_np<__HIP_MEMORY_SCOPE_AGENT>(P, grid, lds, s);
+void vh_launch_scan_fast_lds(const VhPlanDev& P, const VhScanLaunch& L, bool xcd_private) {
+  vh_with_scope(xcd_private, [&](auto scope) { vh_with_np(P.npred, [&](auto np) {
+    constexpr int SCOPE = decltype(scope)::value, NP = decltype(np)::value;
+    L.named("scan_agg_fast_kernel<%d, %d, %d, %d>", VH_MODE_DENSE_LDS, 1024, SCOPE, NP);
+    vh_launch_or_ask(L, scan_agg_fast_kernel<VH_MODE_DENSE_LDS, 1024, SCOPE, NP>, 1024, false, P);      // (one block per CU: the occupancy is not asked)
+  }); });
 }

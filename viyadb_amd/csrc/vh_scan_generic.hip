@@ -3,15 +3,16 @@
 #include "vh_launch.h"
 
 template <int MODE, int BLOCK>
-static void launch(const VhPlanDev& P, int grid, size_t lds, bool xcd_private, hipStream_t s) {
-  if (xcd_private)
-    hipLaunchKernelGGL((scan_agg_kernel<MODE, BLOCK, __HIP_MEMORY_SCOPE_WORKGROUP>), dim3(grid), dim3(BLOCK), lds, s, P);
-  else
-    hipLaunchKernelGGL((scan_agg_kernel<MODE, BLOCK, __HIP_MEMORY_SCOPE_AGENT>), dim3(grid), dim3(BLOCK), lds, s, P);
+static void launch(const VhPlanDev& P, const VhScanLaunch& L, bool xcd_private) {
+  vh_with_scope(xcd_private, [&](auto scope) {
+    constexpr int SCOPE = decltype(scope)::value;
+    L.named("scan_agg_kernel<%d, %d, %d>", MODE, BLOCK, SCOPE);
+    vh_launch_or_ask(L, scan_agg_kernel<MODE, BLOCK, SCOPE>, BLOCK, false, P);      // (the occupancy is not asked: the host's default of blocks per CU)
+  });
 }
 
-void vh_launch_scan_generic(int mode, const VhPlanDev& P, int grid, size_t lds, bool xcd_private, hipStream_t s) {
-  if (mode == VH_MODE_DENSE_LDS) launch<VH_MODE_DENSE_LDS, 1024>(P, grid, lds, xcd_private, s);
-  else if (mode == VH_MODE_DENSE_GLOBAL) launch<VH_MODE_DENSE_GLOBAL, 256>(P, grid, lds, xcd_private, s);
-  else launch<VH_MODE_HASH, 256>(P, grid, lds, false, s);
+void vh_launch_scan_generic(int mode, const VhPlanDev& P, const VhScanLaunch& L, bool xcd_private) {
+  if (mode == VH_MODE_DENSE_LDS) launch<VH_MODE_DENSE_LDS, 1024>(P, L, xcd_private);
+  else if (mode == VH_MODE_DENSE_GLOBAL) launch<VH_MODE_DENSE_GLOBAL, 256>(P, L, xcd_private);
+  else launch<VH_MODE_HASH, 256>(P, L, false);
 }

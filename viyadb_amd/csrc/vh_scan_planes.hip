@@ -94,12 +94,11 @@ __global__ __launch_bounds__(BLOCK) void scan_agg_planes_kernel(const VhPlanDev 
   vh_scan_table_flush<VH_MODE_DENSE_LDS, BLOCK, SCOPE>(P, lds);
 }
 
-void vh_launch_scan_planes(const VhPlanDev& P, const VhPlaneAggRef& A, uint32_t chunks_per_seg, int grid, size_t lds, bool xcd_private, hipStream_t s, int* occ) {
+void vh_launch_scan_planes(const VhPlanDev& P, const VhPlaneAggRef& A, uint32_t chunks_per_seg, const VhScanLaunch& L, bool xcd_private) {
   constexpr int BLOCK = 256;       // (at 1024 threads a lane may hold 128 registers, a few fewer than the filter interpreter and the 32 plane words take: QueryBuild::decompose_work)
-  auto go = [&](auto k) {
-    if (occ) { if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, k, BLOCK, lds) != hipSuccess) *occ = 0; }
-    else hipLaunchKernelGGL(k, dim3(grid), dim3(BLOCK), lds, s, P, A.B, A.D, A.F, A.V, chunks_per_seg);
-  };
-  if (xcd_private) go(scan_agg_planes_kernel<BLOCK, __HIP_MEMORY_SCOPE_WORKGROUP>);
-  else go(scan_agg_planes_kernel<BLOCK, __HIP_MEMORY_SCOPE_AGENT>);
+  vh_with_scope(xcd_private, [&](auto scope) {
+    constexpr int SCOPE = decltype(scope)::value;
+    L.named("scan_agg_planes_kernel<%d, %d>", BLOCK, SCOPE);
+    vh_launch_or_ask(L, scan_agg_planes_kernel<BLOCK, SCOPE>, BLOCK, true, P, A.B, A.D, A.F, A.V, chunks_per_seg);
+  });
 }

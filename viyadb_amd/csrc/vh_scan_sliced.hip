@@ -83,18 +83,17 @@ __global__ __launch_bounds__(BLOCK) void scan_agg_sliced_kernel(const VhPlanDev 
 }
 
 template <int MODE, int BLOCK>
-static void launch(const VhPlanDev& P, const VhSlicedRef& A, uint32_t cps, int grid, size_t lds, bool xcd_private, hipStream_t s, int* occ) {
-  auto go = [&](auto k) {
-    if (occ) { if (hipOccupancyMaxActiveBlocksPerMultiprocessor(occ, k, BLOCK, lds) != hipSuccess) *occ = 0; }
-    else hipLaunchKernelGGL(k, dim3(grid), dim3(BLOCK), lds, s, P, A.B, A.L, cps);
-  };
-  if (xcd_private) go(scan_agg_sliced_kernel<MODE, BLOCK, __HIP_MEMORY_SCOPE_WORKGROUP>);
-  else go(scan_agg_sliced_kernel<MODE, BLOCK, __HIP_MEMORY_SCOPE_AGENT>);
+static void launch(const VhPlanDev& P, const VhSlicedRef& A, uint32_t cps, const VhScanLaunch& L, bool xcd_private) {
+  vh_with_scope(xcd_private, [&](auto scope) {
+    constexpr int SCOPE = decltype(scope)::value;
+    L.named("scan_agg_sliced_kernel<%d, %d, %d>", MODE, BLOCK, SCOPE);
+    vh_launch_or_ask(L, scan_agg_sliced_kernel<MODE, BLOCK, SCOPE>, BLOCK, true, P, A.B, A.L, cps);
+  });
 }
 
-void vh_launch_scan_sliced(int mode, const VhPlanDev& P, const VhSlicedRef& A, uint32_t chunks_per_seg, int grid, size_t lds, bool xcd_private, hipStream_t s, int* occ) {
-  if (mode == VH_MODE_DENSE_LDS) launch<VH_MODE_DENSE_LDS, 1024>(P, A, chunks_per_seg, grid, lds, xcd_private, s, occ);
-  else if (mode == VH_MODE_DENSE_GLOBAL) launch<VH_MODE_DENSE_GLOBAL, 256>(P, A, chunks_per_seg, grid, lds, xcd_private, s, occ);
-  else if (mode == VH_MODE_DENSE_PART) launch<VH_MODE_DENSE_PART, 256>(P, A, chunks_per_seg, grid, lds, false, s, occ);
-  else launch<VH_MODE_HASH, 256>(P, A, chunks_per_seg, grid, lds, false, s, occ);
+void vh_launch_scan_sliced(int mode, const VhPlanDev& P, const VhSlicedRef& A, uint32_t chunks_per_seg, const VhScanLaunch& L, bool xcd_private) {
+  if (mode == VH_MODE_DENSE_LDS) launch<VH_MODE_DENSE_LDS, 1024>(P, A, chunks_per_seg, L, xcd_private);
+  else if (mode == VH_MODE_DENSE_GLOBAL) launch<VH_MODE_DENSE_GLOBAL, 256>(P, A, chunks_per_seg, L, xcd_private);
+  else if (mode == VH_MODE_DENSE_PART) launch<VH_MODE_DENSE_PART, 256>(P, A, chunks_per_seg, L, false);      // (tuples and the hash table have no private copies)
+  else launch<VH_MODE_HASH, 256>(P, A, chunks_per_seg, L, false);
 }

@@ -354,7 +354,9 @@ static int query_agg_device_rows(vh_table* t, const vh_plan* plan, vh_result** o
   int rc = VH_OK;
   for (uint32_t attempt = 0; attempt < 12; ++attempt) {
     vh_result* r = nullptr;
-    { std::lock_guard<std::mutex> lk(t->mu); rc = query_launch_locked(t, x, plan, &r, rp.cap_override, rp.force_hash, rp.part_override, rp.no_part, false, nullptr, nullptr, true, rp.hp_passes, rp.no_hpart); }
+    VhLaunchOpts o;
+    o.rp = rp; o.device_rows = true;
+    { std::lock_guard<std::mutex> lk(t->mu); rc = query_launch_locked(t, x, plan, &r, o); }
     if (rc) break;
     r->exec = x;
     int retry = 0;
@@ -731,7 +733,9 @@ extern "C" int vh_query_agg_sharded(vh_table* t, const vh_plan* plan, vh_comm* c
     }
     if (!cached) {
       VhSummary mine{};
-      { std::lock_guard<std::mutex> lk(t->mu); vh_result* none = nullptr; lrc = query_launch_locked(t, x, plan, &none, 0, false, 0, false, false, &mine); }
+      VhLaunchOpts so;
+      so.summary_out = &mine;
+      { std::lock_guard<std::mutex> lk(t->mu); vh_result* none = nullptr; lrc = query_launch_locked(t, x, plan, &none, so); }
       if (lrc && !local_err[0]) snprintf(local_err, sizeof(local_err), "%s", g_err);
       mine.cap_override = rp.cap_override; mine.part_override = rp.part_override;
       mine.force_hash = rp.force_hash; mine.no_part = rp.no_part; mine.fatal = lrc ? 1 : 0;
@@ -751,7 +755,9 @@ extern "C" int vh_query_agg_sharded(vh_table* t, const vh_plan* plan, vh_comm* c
 
     // ---- 2. scan this rank's shard with the agreed plan
     vh_result* r = nullptr;
-    { std::lock_guard<std::mutex> lk(t->mu); lrc = query_launch_locked(t, x, plan, &r, rp.cap_override, rp.force_hash, rp.part_override, rp.no_part, false, nullptr, &ag, true, rp.hp_passes, rp.no_hpart); }
+    VhLaunchOpts o;
+    o.rp = rp; o.ag = &ag; o.device_rows = true;
+    { std::lock_guard<std::mutex> lk(t->mu); lrc = query_launch_locked(t, x, plan, &r, o); }
     if (lrc && cached && changed) { lrc = VH_OK; r = nullptr; }          // a stale agreement may not even plan: not an error, everyone re-agrees below
     if (lrc && !local_err[0]) snprintf(local_err, sizeof(local_err), "%s", g_err);
     std::unique_ptr<vh_result> holder(r);

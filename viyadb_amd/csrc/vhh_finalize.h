@@ -25,7 +25,9 @@ static int heavy_pass_enqueue(vh_result* r, VhHeavyRun& H) {
   std::lock_guard<std::mutex> lk(t->mu);
   g_heavy.only = r->plan.heavy_mark; g_heavy.ids_bound = H.ids_bound; g_heavy.allow_mark = false;
   g_heavy.tuples_of = H.from_tuples ? r : nullptr; g_heavy.epoch = r->launch_epoch;
-  const int rc = query_launch_locked(t, H.x2, &H.p2, &H.r2, H.cap, true, 0, false, false, nullptr, nullptr, false, 0, true);
+  VhLaunchOpts o;
+  o.rp.cap_override = H.cap; o.rp.force_hash = true; o.rp.no_hpart = true;
+  const int rc = query_launch_locked(t, H.x2, &H.p2, &H.r2, o);
   g_heavy = VhHeavyCtx{};
   if (g_plan_carry) { r->info.reserved |= 1u << 24; g_plan_carry = false; }      // (what the pass evicted is the query's to report)
   if (rc) H.r2 = nullptr; else H.r2->exec = H.x2;
@@ -334,7 +336,7 @@ extern "C" int vh_query_launch(vh_table* t, const vh_plan* plan, vh_result** out
   if (int rc = exec_acquire(t, &x)) return rc;
   vh_result* r = nullptr;
   int rc;
-  { std::lock_guard<std::mutex> lk(t->mu); rc = query_launch_locked(t, x, plan, &r, 0, false); }
+  { std::lock_guard<std::mutex> lk(t->mu); rc = query_launch_locked(t, x, plan, &r); }
   if (rc) { (void)hipStreamSynchronize(x->stream()); exec_release(t, x); return rc; }
   r->exec = x;
   *out = r;
@@ -352,8 +354,7 @@ extern "C" int vh_result_finalize(vh_result* r) {
   return VH_OK;
 }
 
-// One attempt's verdict -> the overrides of the next one. Shared by vh_query_agg and the sharded form.
-struct VhReplan { uint64_t cap_override = 0, part_override = 0; bool force_hash = false, no_part = false; uint32_t hp_passes = 0; bool no_hpart = false; };
+// One attempt's verdict -> the overrides of the next one (VhReplan, vhh_plan.h). Shared by vh_query_agg and the sharded form.
 static void replan_after(vh_table* t, vh_result* r, int retry, VhReplan* rp) {
   if (retry == 1) {
     // table too small. The number of groups is bounded by the number of surviving rows: estimate those
@@ -494,7 +495,9 @@ extern "C" int vh_query_agg(vh_table* t, const vh_plan* plan, vh_result** out) {
     {
       std::lock_guard<std::mutex> lk(t->mu);
       g_heavy.allow_mark = true;        // (this caller can run the second pass over heavy ranges: it holds the plan when the verdict is in)
-      rc = query_launch_locked(t, x, plan, &r, rp.cap_override, rp.force_hash, rp.part_override, rp.no_part, false, nullptr, nullptr, false, rp.hp_passes, rp.no_hpart);
+      VhLaunchOpts o;
+      o.rp = rp;
+      rc = query_launch_locked(t, x, plan, &r, o);
       g_heavy = VhHeavyCtx{};
     }
     if (rc) break;

@@ -143,6 +143,19 @@ int vh_jit_drain_depth(const VhJitShape& s) {
   return depth;
 }
 
+// No compiled kernel for this plan (yet): hand the query to a second plan for the pre-built kernels, with the options of this one. keep_part:
+// an organisation chosen as DENSE_PART stays DENSE_PART; no_hashed_part: the hashed partitioning, which only a compiled scan feeds, is off.
+int QueryBuild::plan_again(bool keep_part, bool no_hashed_part) {
+  vh_plan p2 = *p;
+  p2.flags |= VH_PLAN_NO_JIT;
+  if (keep_part && mode == VH_MODE_DENSE_PART) p2.flags |= VH_PLAN_FORCE_PART;
+  VhLaunchOpts o2 = o;
+  o2.rp.no_hpart |= no_hashed_part;
+  holder.reset();
+  done = true;
+  return query_launch_locked(t, x, &p2, out, o2);
+}
+
 int QueryBuild::compile_kernel() {
   // ---------------- the scan kernel compiled for this plan shape (vh_jit.hip), when there is to be one
   // the no-compaction kernels are pre-built, except DENSE_LDS's over plain 4- / 8-byte arena columns (C2's shape), which has a compiled form
@@ -246,13 +259,8 @@ int QueryBuild::compile_kernel() {
         if (!known) ++t->inline_builds;
       }
       if (pending) {
-        vh_plan p2 = *p;
-        p2.flags |= VH_PLAN_NO_JIT;
-        if (mode == VH_MODE_DENSE_PART) p2.flags |= VH_PLAN_FORCE_PART;
-        holder.reset();
-        done = true;
         ++g_build_quiet;        // (the second plan counts towards no automatic layout: this query has been counted)
-        const int prc = query_launch_locked(t, x, &p2, out, hash_capacity_override, force_hash, part_tuples_override, no_part, plan_only, summary_out, ag, device_rows, hp_passes_override, no_hpart);
+        const int prc = plan_again(true, false);
         --g_build_quiet;
         if (!prc && out && *out) (*out)->info.reserved |= 1u << 19;
         return prc;
@@ -267,14 +275,9 @@ int QueryBuild::compile_kernel() {
                                                      "vh_result_info.reserved bit 5 tells per query (VH_JIT_VERBOSE=1 for every occurrence)\n", jerr.substr(0, 200).c_str()); });
         }
         if ((p->flags & VH_PLAN_FORCE_JIT) || vh_jit_policy() == VH_JIT_FORCE) return vh_fail(VH_E_UNSUPPORTED, "per-query kernel requested (VH_PLAN_FORCE_JIT / VH_JIT=force) but unavailable: %s", jerr.c_str());
-        vh_plan p2 = *p;
-        p2.flags |= VH_PLAN_NO_JIT;
         // (the organisation must not depend on whether THIS rank could compile: partitioning chosen because a compiled scan makes tuples
         // cheap stays chosen — the pre-built kernels run it too — so that sharded ranks keep identically laid out partial tables)
-        if (mode == VH_MODE_DENSE_PART) p2.flags |= VH_PLAN_FORCE_PART;
-        holder.reset();
-        done = true;
-        return query_launch_locked(t, x, &p2, out, hash_capacity_override, force_hash, part_tuples_override, no_part, plan_only, summary_out, ag, device_rows, hp_passes_override, no_hpart);
+        return plan_again(true, false);
       }
     }
   }
@@ -285,11 +288,7 @@ int QueryBuild::compile_kernel() {
     for (int j = 0; j < P.nmetric; ++j) lanes_narrow |= vh_elem_size(P.m[j].type()) < 4;
   }
   if (!jk && (packed_compressed || (mode == VH_MODE_DENSE_PART && P.gid_bits) || lanes_narrow || hpart)) {      // compressed records / one-word tuples / narrow lanes columns / the hashed partitioning (its scan writes level A itself) and no compiled kernel to handle them after all: plan again for the pre-built ones
-    vh_plan p2 = *p;
-    p2.flags |= VH_PLAN_NO_JIT;
-    holder.reset();
-    done = true;
-    return query_launch_locked(t, x, &p2, out, hash_capacity_override, force_hash, part_tuples_override, no_part, plan_only, summary_out, ag, device_rows, hp_passes_override, no_hpart || hpart);
+    return plan_again(false, hpart);
   }
   return VH_OK;
 }
@@ -366,34 +365,39 @@ void QueryBuild::choose_plane_agg() {
   layout_use(t, v);
 }
 
-void QueryBuild::scan_dispatch(int grid_, int* occ) {
+// The one place that decides which scan kernel runs. L brings the grid to launch — or, with L.occ / L.name set, what the chosen launcher is to
+// answer instead of launching (VhScanLaunch) —; LDS bytes and stream are filled in here. A compiled kernel carries its own name (jk->name).
+void QueryBuild::scan_dispatch(VhScanLaunch L) {
   const size_t qb = (size_t)(BLOCK / 64) * VhScanCfg<256>::kQueueCap * sizeof(uint32_t);
-  const size_t lds_ = ((mode == VH_MODE_DENSE_LDS || mode == VH_MODE_HASH) ? lds_table : 0) + qb;
-  hipStream_t s_ = x->stream();
+  const bool xcd_private = nxcd > 1;
+  const uint32_t chunks_per_seg = (uint32_t)std::max<uint64_t>(1, (t->padded_rows + VH_SLICED_CHUNK_ROWS - 1) / VH_SLICED_CHUNK_ROWS);      // the readers of the planes walk 2048-row chunks
+  L.lds = ((mode == VH_MODE_DENSE_LDS || mode == VH_MODE_HASH) ? lds_table : 0) + qb;
+  L.stream = x->stream();
   if (plane_agg) {      // (no queue: the block's LDS table alone)
-    const uint32_t cps = (uint32_t)std::max<uint64_t>(1, (t->padded_rows + VH_SLICED_CHUNK_ROWS - 1) / VH_SLICED_CHUNK_ROWS);
-    vh_launch_scan_planes(P, pagg_ref, cps, grid_, lds_table, nxcd > 1, s_, occ);
+    L.lds = lds_table;
+    vh_launch_scan_planes(P, pagg_ref, chunks_per_seg, L, xcd_private);
   }
   else if (sliced_prebuilt) {
-    const uint32_t cps = (uint32_t)std::max<uint64_t>(1, (t->padded_rows + VH_SLICED_CHUNK_ROWS - 1) / VH_SLICED_CHUNK_ROWS);
-    vh_launch_scan_sliced(mode, P, planes_ref, cps, grid_, mode == VH_MODE_DENSE_PART ? qb : lds_, nxcd > 1, s_, occ);
+    if (mode == VH_MODE_DENSE_PART) L.lds = qb;
+    vh_launch_scan_sliced(mode, P, planes_ref, chunks_per_seg, L, xcd_private);
   }
   else if (jk) {
     const size_t jl = ((mode == VH_MODE_DENSE_LDS || (mode == VH_MODE_HASH && !hpart)) ? lds_table : 0) + (size_t)(BLOCK / 64) * (VJ_QUEUE_CAP * sizeof(uint32_t)) +
                       (jshape.hp_fan ? VJ_FAN_LDS_BYTES(BLOCK) : 0) + (jshape.part_ring ? VH_RING_LDS_BYTES(jshape.part_ring, 2, BLOCK) : 0);
-    if (occ) *occ = vh_jit_occupancy(jk, BLOCK, jl);
-    else (void)vh_jit_launch(jk, P, grid_, BLOCK, jl, s_);
+    if (L.occ) *L.occ = vh_jit_occupancy(jk, BLOCK, jl);
+    else if (!L.name) (void)vh_jit_launch(jk, P, L.grid, BLOCK, jl, L.stream);
   }
   else if (mode == VH_MODE_DENSE_PART) {
-    if (lanes) vh_launch_scan_lanes_part(P, grid_, 4 * vh_part_tile_bytes(P), s_, occ);
-    else vh_launch_scan_fast_part(P, grid_, qb, s_, occ);   // the compacting form appends straight to the extents: no tile in LDS
+    L.lds = lanes ? 4 * vh_part_tile_bytes(P) : qb;      // (the compacting form appends straight to the extents: no tile in LDS)
+    if (lanes) vh_launch_scan_lanes_part(P, L);
+    else vh_launch_scan_fast_part(P, L);
   }
-  else if (!fast) { if (!occ) vh_launch_scan_generic(mode, P, grid_, lds_, nxcd > 1, s_); }
-  else if (lanes && mode == VH_MODE_HASH) vh_launch_scan_lanes_hash(P, grid_, lds_, s_, occ);
-  else if (lanes) vh_launch_scan_lanes_lds(P, BLOCK, grid_, lds_, nxcd > 1, s_, occ);
-  else if (mode == VH_MODE_DENSE_LDS) { if (!occ) vh_launch_scan_fast_lds(P, grid_, lds_, nxcd > 1, s_); }   // 1024-thread blocks: one per CU
-  else if (mode == VH_MODE_DENSE_GLOBAL) vh_launch_scan_fast_global(P, grid_, lds_, nxcd > 1, s_, occ);
-  else vh_launch_scan_fast_hash(P, grid_, lds_, s_, occ);
+  else if (!fast) vh_launch_scan_generic(mode, P, L, xcd_private);
+  else if (lanes && mode == VH_MODE_HASH) vh_launch_scan_lanes_hash(P, L);
+  else if (lanes) vh_launch_scan_lanes_lds(P, BLOCK, L, xcd_private);
+  else if (mode == VH_MODE_DENSE_LDS) vh_launch_scan_fast_lds(P, L, xcd_private);   // 1024-thread blocks: one per CU
+  else if (mode == VH_MODE_DENSE_GLOBAL) vh_launch_scan_fast_global(P, L, xcd_private);
+  else vh_launch_scan_fast_hash(P, L);
 }
 
 int QueryBuild::decompose_work() {
@@ -411,16 +415,13 @@ int QueryBuild::decompose_work() {
     if (env_lanes_block == 256 || env_lanes_block == 512 || env_lanes_block == 1024) BLOCK = env_lanes_block;
     else if ((uint64_t)g_ctx.num_cu * 5 * G * std::max(1, P.nmetric) <= rows_to_scan / 32) BLOCK = 256;
   }
-  // One place decides which scan kernel runs; with `occ` it only asks how many of its blocks fit a CU.
+  // The scan launcher answers, without launching: how many of its kernel's blocks fit a CU, and — a pre-built kernel — what it is called.
+  int occupancy = 0;
   {   // the kernel symbol(s) this query runs, as rocprofv3 prints them (vh_result_kernel: bench.py's roofline.kernel)
-    const int np_ = std::max(1, (int)P.npred), scope = (mode == VH_MODE_DENSE_GLOBAL || mode == VH_MODE_DENSE_LDS) && nxcd > 1 ? (int)__HIP_MEMORY_SCOPE_WORKGROUP : (int)__HIP_MEMORY_SCOPE_AGENT;
-    char nm[160];
-    if (plane_agg) snprintf(nm, sizeof(nm), "scan_agg_planes_kernel<%d, %d>", BLOCK, scope);
-    else if (sliced_prebuilt) snprintf(nm, sizeof(nm), "scan_agg_sliced_kernel<%d, %d, %d>", mode, BLOCK, (mode == VH_MODE_HASH || mode == VH_MODE_DENSE_PART) ? (int)__HIP_MEMORY_SCOPE_AGENT : scope);
-    else if (!fast) snprintf(nm, sizeof(nm), "scan_agg_kernel<%d, %d, %d>", mode, BLOCK, scope);
-    else if (mode == VH_MODE_DENSE_PART && !lanes && P.shape) snprintf(nm, sizeof(nm), "scan_agg_shape_kernel<%d, %d, %d, %d, %d>", mode, BLOCK, (int)__HIP_MEMORY_SCOPE_AGENT, np_, P.shape);
-    else snprintf(nm, sizeof(nm), "%s<%d, %d, %d, %d>", lanes ? "scan_agg_lanes_kernel" : "scan_agg_fast_kernel", mode, BLOCK,
-                  (mode == VH_MODE_HASH || mode == VH_MODE_DENSE_PART) ? (int)__HIP_MEMORY_SCOPE_AGENT : scope, np_);
+    char nm[160] = "";
+    VhScanLaunch ask;
+    ask.occ = env_bpc <= 0 ? &occupancy : nullptr; ask.name = jk ? nullptr : nm; ask.name_cap = sizeof(nm);
+    if (ask.occ || ask.name) scan_dispatch(ask);
     r->kernel = jk ? jk->name : std::string(nm);
     if (hpart) {      // (the scatter kernel runs twice per query, level A and level B: named twice, so that per-query sums over the names count it twice)
       char hn[160];
@@ -428,11 +429,11 @@ int QueryBuild::decompose_work() {
       else snprintf(hn, sizeof(hn), " + hp_scatter_kernel<1024, %d> + hp_scatter_kernel<1024, %d> + ", hp_units, hp_units);
       r->kernel += hn + jk->name + "_hpagg";
     }
-    const std::string pagg = jit_pagg() ? " + " + jk->name + "_pagg" : std::string(" + part_agg_kernel<1024>");
-    if (mode == VH_MODE_DENSE_PART) r->kernel += P.nlevel != 2 ? pagg : (P.tw == 2 || P.gid_bits) ? (std::string(" + part_split_ring_kernel<256, ") + (P.tuple4 ? "4>" : P.gid_bits ? "8>" : "16>") + pagg) : " + part_split_kernel<256>" + pagg;
+    if (mode == VH_MODE_DENSE_PART) {
+      if (P.nlevel == 2) r->kernel += " + " + vh_part_split_name(P);
+      r->kernel += " + " + (jit_pagg() ? jk->name + "_pagg" : std::string(vh_part_agg_name()));
+    }
   }
-  int occupancy = 0;
-  if (env_bpc <= 0) scan_dispatch(0, &occupancy);
   const uint32_t step = BLOCK * (jk && jshape.pp_sliced ? 32u : (uint32_t)VH_LANE_ROWS);      // (bit-sliced predicates: a lane owns 32 consecutive rows per step)
   const uint64_t padded = (t->segment_rows + step - 1) / step * step;
   // all blocks co-resident (the compacting kernels need ~100-130 VGPRs: 4 waves/SIMD), units small enough
@@ -493,7 +494,7 @@ int QueryBuild::layout_scratch() {
   // eight words buys nothing (profiles/r05/NOTES.md)
   const bool hp_streamed = knobs().hp_stream > 0 ? capacity >= (1ull << 22) : test_env("VH_TEST_HP_STREAM") != nullptr;
   const bool hp_regions = !hp_streamed && knobs().hp_regions > 1 && capacity >= (1ull << 22);
-  if (r->hp_direct && !device_rows && (hp_streamed || hp_regions)) {
+  if (r->hp_direct && !o.device_rows && (hp_streamed || hp_regions)) {
     int nch = std::min(hp_regions ? knobs().hp_regions : knobs().hp_stream > 0 ? knobs().hp_stream : 4, VH_HP_CHUNKS);
     while (HP_FAN % nch) --nch;
     r->hp_chunks = nch;
@@ -569,7 +570,7 @@ int QueryBuild::layout_scratch() {
   if (part_balanced) o_pcount = sp.take(VH_MAX_PART * VH_PART_COUNT_WAYS * sizeof(uint32_t));
   // hashed partitioning whose groups leave straight into the output columns, planned by a caller that can run a second pass (vh_query_agg): ranges
   // that are too heavy for a block's LDS tables are marked in a bitmap of the 65 536 ranges instead of voiding the attempt
-  heavy_marks = hpart && r->hp_direct && !r->hp_chunks && !device_rows && g_heavy.allow_mark && !g_heavy.only && P.hp_passes == 1 && !test_env("VH_NO_HEAVY_PASS");
+  heavy_marks = hpart && r->hp_direct && !r->hp_chunks && !o.device_rows && g_heavy.allow_mark && !g_heavy.only && P.hp_passes == 1 && !test_env("VH_NO_HEAVY_PASS");
   if (heavy_marks) o_heavy = sp.take(65536 / 8);
   if (hpart) part_tuple_cap = hp_tuple_cap;
   if (mode == VH_MODE_DENSE_PART || hpart) {
@@ -600,7 +601,7 @@ int QueryBuild::layout_scratch() {
     // included); only more survivors than estimated void the attempt, and the re-run is sized for the survivors it counted
     uint64_t pos1 = 0;
     if (ring1) { pos1 = part_tuple_cap / per1 / ext_tuples + 1; max_ext = std::min<uint64_t>(pos1 * per1 + part_tuple_cap / ext_tuples + per1 + 64, 0xFFFFFFF0ull); }      // (+ per1: every stream's last, part-filled overflow extent)
-    if (!part_tuples_override && test_env("VH_TEST_PART_EXTENTS")) max_ext = std::max(1, atoi(test_env("VH_TEST_PART_EXTENTS")));   // tests: make the first attempt run out of extents
+    if (!o.rp.part_override && test_env("VH_TEST_PART_EXTENTS")) max_ext = std::max(1, atoi(test_env("VH_TEST_PART_EXTENTS")));   // tests: make the first attempt run out of extents
     const uint32_t test_levels = test_env("VH_TEST_POS_LEVELS") ? (uint32_t)std::max(0, atoi(test_env("VH_TEST_POS_LEVELS"))) : ~0u;      // tests: few (or no) positional levels — the tuples go through the overflow regions
     P.slice_levels_cap = test_levels;
     if (ring1) P.pos_levels = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(pos1, max_ext / per1), test_levels);
@@ -608,15 +609,15 @@ int QueryBuild::layout_scratch() {
     // the scan's waves take their extent chunks by position (no shared cursor, no returning atomics: VhPlanDev::ext_waves). The pool above
     // holds that whenever the waves' tuple counts agree within the 25 % the estimate leaves; a re-run after VH_ERR_PART_FULL goes back to
     // the cursor, which packs the chunks whatever the imbalance
-    P.ext_waves = ring1 || part_tuples_override || test_env("VH_TEST_EXT_CURSOR") || t->part_clustered.count(r->group_sig) ? 0u : (uint32_t)grid * (uint32_t)(BLOCK / 64);
+    P.ext_waves = ring1 || o.rp.part_override || test_env("VH_TEST_EXT_CURSOR") || t->part_clustered.count(r->group_sig) ? 0u : (uint32_t)grid * (uint32_t)(BLOCK / 64);
     o_tuples = sp.take(max_ext * ext_stride * (P.tuple4 ? 4 : P.tw * 8));
     o_emiss = sp.take(max_ext * sizeof(uint16_t));
     o_epart = sp.take(max_ext);
     if (P.nlevel == 2) {
       // pool 2: small extents (4096 ranges x every splitting wave keep one open), sized like pool 1 plus what stays open
       split_bpp = std::max(1, 2 * g_ctx.num_cu / std::max(1, P.npart));     // 256-thread blocks, ~2 per CU whatever the partition count: more waves keep more extents open (4 per CU measured slower)
-      // one- and two-word tuples are split through the ring writer (part_split_ring_kernel): a block is one writer, more of them cost less
-      const bool tiled = P.tw == 2 || P.gid_bits;
+      // one- and two-word tuples are split through the ring writer (vh_part_split_rings): a block is one writer, more of them cost less
+      const bool tiled = vh_part_split_rings(P);
       if (tiled) split_bpp = std::max(1, 4 * g_ctx.num_cu / std::max(1, P.npart));
       const uint64_t et2 = tiled ? VH_SPLIT_TILE_TUPLES : 256;
       P.ext_tuples2 = (int32_t)et2;
@@ -625,7 +626,7 @@ int QueryBuild::layout_scratch() {
       // (slices laid out on the device from the partitions' counted tuples — vh_slice_extents: positional extents + an overflow region as big as the count)
       if (split_ring) max2 = 2 * (part_tuple_cap / et2) + (uint64_t)P.npart * (2 * 64 * split_bpp + 2) + 64;
       if (max2 > 0xFFFFFFF0ull) max2 = 0xFFFFFFF0ull;
-      if (!part_tuples_override && test_env("VH_TEST_PART_EXTENTS2")) max2 = std::max(1, atoi(test_env("VH_TEST_PART_EXTENTS2")));   // tests: the second pool runs out first
+      if (!o.rp.part_override && test_env("VH_TEST_PART_EXTENTS2")) max2 = std::max(1, atoi(test_env("VH_TEST_PART_EXTENTS2")));   // tests: the second pool runs out first
       P.max_extents2 = (uint32_t)max2;
       o_tuples2 = sp.take(max2 * et2 * (P.tuple4 ? 4 : P.tw * 8));
       o_emiss2 = sp.take(max2 * sizeof(uint16_t));
@@ -642,13 +643,13 @@ int QueryBuild::layout_scratch() {
       // then the shared overflow region: all the tuples once more (any skew between the digits fits)
       const uint64_t per = (uint64_t)grid * HP_FAN, posa = cap / per / hp_et + 1;
       uint64_t ma = posa * per + cap / hp_et + per + 64;
-      if (!part_tuples_override && test_env("VH_TEST_PART_EXTENTS")) ma = std::max(1, atoi(test_env("VH_TEST_PART_EXTENTS")));      // tests: the first attempt's pool is too small
+      if (!o.rp.part_override && test_env("VH_TEST_PART_EXTENTS")) ma = std::max(1, atoi(test_env("VH_TEST_PART_EXTENTS")));      // tests: the first attempt's pool is too small
       P.pos_levels2 = (uint32_t)std::min<uint64_t>(std::min<uint64_t>(posa, ma / per), test_env("VH_TEST_POS_LEVELS") ? (uint64_t)std::max(0, atoi(test_env("VH_TEST_POS_LEVELS"))) : ~0ull);
       // level B: hp_plan_kernel's slices — positional extents + an overflow region as big as the partition's count (vh_slice_extents).
       hp_ring_nb = 1;      // (level-B blocks per partition. Measured, C5: two or four of them write level B no faster — 0.425 / 0.421 / 0.397 ms — and leave the
                            //  aggregation two or four extents per range to walk: 1.08 / 1.24 / 1.69 ms)
       uint64_t mb = 2 * (cap / hp_et) + (uint64_t)HP_FAN * (2 * HP_FAN * hp_ring_nb + 2) + 64;
-      if (!part_tuples_override && test_env("VH_TEST_PART_EXTENTS2")) mb = std::max(1, atoi(test_env("VH_TEST_PART_EXTENTS2")));   // tests: the last pool runs out
+      if (!o.rp.part_override && test_env("VH_TEST_PART_EXTENTS2")) mb = std::max(1, atoi(test_env("VH_TEST_PART_EXTENTS2")));   // tests: the last pool runs out
       hpo[k].maxa = ma; hpo[k].maxb = mb;
       hpo[k].ta = sp.take(ma * hp_es * 16 * hp_units); hpo[k].fa = sp.take(ma * 2); hpo[k].ga = sp.take(ma);
       hpo[k].tb = sp.take(mb * hp_es * 16 * hp_units); hpo[k].fb = sp.take(mb * 2); hpo[k].gb = sp.take(mb);
@@ -892,7 +893,7 @@ int QueryBuild::launch() {
     return vh_fail(VH_E_RANGE, "second pass over heavy ranges: the table changed since the first pass");      // (heavy_pass_finish gives up; the caller re-plans the whole query)
   if (from_tuples) {
   } else if (P.total_units) {
-    scan_dispatch(grid, nullptr);
+    scan_dispatch(VhScanLaunch{grid});
     if (hpart) {
       vh_launch_hpart(P, d_hpargs, hp_units, g_ctx.num_cu, grid, hp_ring_nb, st);
       if (!r->hp_chunks) HIP_TRY(vh_jit_launch_hpagg(jk, P, d_hpargs, hp_bpp, 0, HP_FAN * hp_bpp, lds_table, st));
@@ -931,7 +932,7 @@ int QueryBuild::launch() {
   // the three parallel launches it replaces are the faster tail
   r->small_tail = mode != VH_MODE_HASH && r->out_cap <= VH_SMALL_TAIL_MAX && r->out_region_bytes <= (8u << 20) && !r->topk_active && !r->hp_chunks &&
                   (uint64_t)r->out_cap * (uint64_t)std::max(1, nxcd) * (uint64_t)std::max(1, (int)P.nmetric) <= VH_SMALL_TAIL_STATES &&
-                  !device_rows && !knobs().no_direct_emit && !test_env("VH_TEST_NO_SMALL_TAIL");
+                  !o.device_rows && !knobs().no_direct_emit && !test_env("VH_TEST_NO_SMALL_TAIL");
   if (mode != VH_MODE_HASH && nxcd > 1) {
     r->unmerged = true;
     if (!r->small_tail) { if (int mrc = merge_copies_now(r, st)) return mrc; }
@@ -941,10 +942,7 @@ int QueryBuild::launch() {
   return VH_OK;
 }
 
-static int query_launch_locked(vh_table* t, VhExec* x, const vh_plan* p, vh_result** out, uint64_t hash_capacity_override,
-                               bool force_hash, uint64_t part_tuples_override = 0, bool no_part = false,
-                               bool plan_only = false, VhSummary* summary_out = nullptr, const VhAgreed* ag = nullptr,
-                               bool device_rows = false, uint32_t hp_passes_override = 0, bool no_hpart = false) {
+static int query_launch_locked(vh_table* t, VhExec* x, const vh_plan* p, vh_result** out, const VhLaunchOpts& o) {
   if (int src = sync_resolve(t)) return src;      // a batched sync may still be on its way: its rows and its share of the stats, before anything is planned
   // One tick per query (a plan that starts over keeps it): what the layouts this plan reads are stamped with (layout_use). When the outermost
   // call returns, a budget that a refresh pushed past — the table grew, a projection was rebuilt wider — is restored at the cost of layouts
@@ -969,9 +967,8 @@ static int query_launch_locked(vh_table* t, VhExec* x, const vh_plan* p, vh_resu
       if (further) g_plan_carry = g_plan_evicted;
       else if (g_plan_evicted && out && *out) (*out)->info.reserved |= 1u << 24;
     }
-  } tick(t, out, summary_out != nullptr || g_heavy.only != nullptr);
-  QueryBuild b(t, x, p, out, hash_capacity_override, force_hash, part_tuples_override, no_part, plan_only, summary_out, ag, device_rows,
-               hp_passes_override, no_hpart);
+  } tick(t, out, o.summary_out != nullptr || g_heavy.only != nullptr);
+  QueryBuild b(t, x, p, out, o);
   int (QueryBuild::* const steps[])() = {&QueryBuild::shape_filter, &QueryBuild::snapshot_segments, &QueryBuild::shape_groups, &QueryBuild::shape_metrics,
                                          &QueryBuild::choose_organisation, &QueryBuild::plan_hashed_partitioning, &QueryBuild::choose_projection,
                                          &QueryBuild::compile_kernel, &QueryBuild::decompose_work, &QueryBuild::layout_scratch, &QueryBuild::launch};

@@ -155,8 +155,9 @@ static int estimate_selectivity(vh_table* t, VhExec* x, const VhPlanDev& P, cons
   }
   const size_t qbytes = (size_t)16 * VhScanCfg<1024>::kQueueCap * sizeof(uint32_t);
   // (generic: predicate columns of other widths than 4 bytes — plans only the per-query compiled kernels run register-resident)
-  if (generic) vh_launch_scan_generic(VH_MODE_DENSE_LDS, S, (int)std::min<uint32_t>(nseg, (uint32_t)g_ctx.num_cu), 16 + qbytes, false, st);
-  else vh_launch_scan_fast_lds(S, (int)std::min<uint32_t>(nseg, (uint32_t)g_ctx.num_cu), 16 + qbytes, false, st);
+  const VhScanLaunch L{(int)std::min<uint32_t>(nseg, (uint32_t)g_ctx.num_cu), 16 + qbytes, st};      // grid, LDS bytes, stream
+  if (generic) vh_launch_scan_generic(VH_MODE_DENSE_LDS, S, L, false);
+  else vh_launch_scan_fast_lds(S, L, false);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(x->h_counters + 8, S.counters, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -193,6 +194,16 @@ struct VhAgreed {
   uint64_t rows_max;          // the largest shard: what one rank's kernels will see
   double sel;
 };
+// What a failed attempt asks of the next one (replan_after in vhh_finalize.h, merge_summaries in vh_sharded.h) ...
+struct VhReplan { uint64_t cap_override = 0, part_override = 0; bool force_hash = false, no_part = false; uint32_t hp_passes = 0; bool no_hpart = false; };
+// ... and how query_launch_locked is asked for a plan, beyond table, context and the plan itself: every caller names the members it sets.
+struct VhLaunchOpts {
+  VhReplan rp;
+  bool plan_only = false;               // vh_query_select: filter program, column slots and the segment snapshot, nothing launched
+  VhSummary* summary_out = nullptr;     // a sharded query's first half: report what this rank's planner looks at and stop
+  const VhAgreed* ag = nullptr;         // ... and its second: plan with the figures all ranks agreed on
+  bool device_rows = false;             // emitted rows must (also) exist in device memory: they are exchanged or gathered next
+};
 
 // Heavy ranges of the hashed partitioning (VhPlanDev::heavy_mark / heavy_only), per calling thread: vh_query_agg lets its plans mark heavy ranges
 // (it can run the second pass: it holds the caller's plan when the verdict is in); the second pass itself plans with `only` = the first pass's bitmap
@@ -207,8 +218,7 @@ static thread_local VhHeavyCtx g_heavy;
 struct QueryBuild {
   // ---- the call
   vh_table* t; VhExec* x; const vh_plan* p; vh_result** out;
-  uint64_t hash_capacity_override; bool force_hash; uint64_t part_tuples_override; bool no_part, plan_only;
-  VhSummary* summary_out; const VhAgreed* ag; bool device_rows; uint32_t hp_passes_override; bool no_hpart;
+  const VhLaunchOpts o;
   std::unique_ptr<vh_result> holder;      // every early return drops it
   vh_result* r;
   VhPlanDev& P;
@@ -314,18 +324,13 @@ struct QueryBuild {
   size_t o_hpargs = 0, hp_meta_bytes = 0;
   char* S = nullptr;
 
-  QueryBuild(vh_table* t_, VhExec* x_, const vh_plan* p_, vh_result** out_, uint64_t hash_capacity_override_, bool force_hash_,
-             uint64_t part_tuples_override_, bool no_part_, bool plan_only_, VhSummary* summary_out_, const VhAgreed* ag_,
-             bool device_rows_, uint32_t hp_passes_override_, bool no_hpart_)
-      : t(t_), x(x_), p(p_), out(out_), hash_capacity_override(hash_capacity_override_), force_hash(force_hash_),
-        part_tuples_override(part_tuples_override_), no_part(no_part_), plan_only(plan_only_), summary_out(summary_out_), ag(ag_),
-        device_rows(device_rows_), hp_passes_override(hp_passes_override_), no_hpart(no_hpart_),
-        holder(new vh_result()), r(holder.get()), P(r->plan), prog(r->h_prog) {}
+  QueryBuild(vh_table* t_, VhExec* x_, const vh_plan* p_, vh_result** out_, const VhLaunchOpts& o_)
+      : t(t_), x(x_), p(p_), out(out_), o(o_), holder(new vh_result()), r(holder.get()), P(r->plan), prog(r->h_prog) {}
 
   int slot(int col);                              // the plan's slot of a table column (-1: none left / bad column, -2: a bitset metric)
   int probed_selectivity(double* sel);
   bool jit_pagg() const { return jk && jk->fn_pagg && mode == VH_MODE_DENSE_PART && !knobs().no_jit_pagg; }      // phase 2 of DENSE_PART runs as the plan's compiled `_pagg` kernel
-  void scan_dispatch(int grid_, int* occ);        // one place decides which scan kernel runs; with `occ` it only asks how many of its blocks fit a CU
+  void scan_dispatch(VhScanLaunch L);             // the one place that decides which scan kernel runs, or — L.occ / L.name — has its launcher answer instead
   // the steps, in order
   int shape_filter();
   int snapshot_segments();
@@ -335,14 +340,13 @@ struct QueryBuild {
   int plan_hashed_partitioning();
   int choose_projection();
   int compile_kernel();
+  int plan_again(bool keep_part, bool no_hashed_part);      // compile_kernel's way out: the same query, planned for the pre-built kernels
   int decompose_work();
   int layout_scratch();
   int launch();
 };
 
-static int query_launch_locked(vh_table* t, VhExec* x, const vh_plan* p, vh_result** out, uint64_t hash_capacity_override,
-                               bool force_hash, uint64_t part_tuples_override, bool no_part, bool plan_only, VhSummary* summary_out,
-                               const VhAgreed* ag, bool device_rows, uint32_t hp_passes_override, bool no_hpart);
+static int query_launch_locked(vh_table* t, VhExec* x, const vh_plan* p, vh_result** out, const VhLaunchOpts& o = {});
 
 void QueryBuild::hold_payload() {
   if (!t->layout_budget) return;
@@ -547,14 +551,14 @@ int QueryBuild::shape_filter() {
   const bool jit_allowed = vh_jit_policy() != VH_JIT_OFF && !(p->flags & (VH_PLAN_NO_JIT | VH_PLAN_NO_FAST));
   // An aggregate that asks for the pre-built scan over the planes (VH_PLAN_SLICED_PREBUILT) takes the shape for the same reason as the select, and
   // attempts no compile for it either: planes_want opens the search below, jit_try stays what the JIT policy and the plan's flags make it.
-  const bool planes_allowed = !plan_only && !(p->flags & (VH_PLAN_NO_SLICED | VH_PLAN_NO_PREDPACK | VH_PLAN_NO_NARROW));
+  const bool planes_allowed = !o.plan_only && !(p->flags & (VH_PLAN_NO_SLICED | VH_PLAN_NO_PREDPACK | VH_PLAN_NO_NARROW));
   sliced_asked = planes_allowed && p->nfilter > 0 && ((p->flags & VH_PLAN_SLICED_PREBUILT) || knobs().sliced_prebuilt);
   // ... and so does one that asks to be computed on the planes (VH_PLAN2_PLANE_AGG), unless it has no filter: then it needs no program.
   // Sharded queries (an agreed plan, a summary call, rows kept on the device for the exchange) ignore that switch.
-  pagg_want = planes_allowed && ((p->flags2 & VH_PLAN2_PLANE_AGG) || knobs().plane_agg) && !ag && !summary_out && !device_rows;
+  pagg_want = planes_allowed && ((p->flags2 & VH_PLAN2_PLANE_AGG) || knobs().plane_agg) && !o.ag && !o.summary_out && !o.device_rows;
   for (const VhProgOp& o : prog) pagg_filter |= o.kind() == VH_F_REL || o.kind() == VH_F_IN || o.kind() == VH_F_INSET;
   planes_want = sliced_asked || (pagg_want && pagg_filter);
-  bool shaped = (jit_allowed || plan_only || planes_want) && prog.size() <= VH_INLINE_PROG && r->h_lits.size() <= VH_INLINE_LITS;
+  bool shaped = (jit_allowed || o.plan_only || planes_want) && prog.size() <= VH_INLINE_PROG && r->h_lits.size() <= VH_INLINE_LITS;
   if (shaped) {
     jshape.prog = prog;
     int nv = 0;
@@ -575,7 +579,7 @@ int QueryBuild::shape_filter() {
     }
     jshape.nlits = (int)r->h_lits.size();
   }
-  jit_try = shaped && (jit_allowed || plan_only);
+  jit_try = shaped && (jit_allowed || o.plan_only);
   planes_want &= shaped;
 
   // Bit-packed predicate projections (vh_table_predpack) of the filter's columns: the byte-plane form serves every compiled kernel form,
@@ -643,7 +647,7 @@ int QueryBuild::shape_filter() {
       // (every query that filters on the column reads it in full, whatever passes: the copy pays from the first query that uses it on)
       if (!have && auto_after > 0 && nwidth && !g_build_quiet && ++t->pred_seen[col] >= (uint32_t)auto_after) {
         const size_t need = (size_t)t->cap_seg * ((t->segment_rows + 255) / 256 * 256) * (size_t)nwidth;
-        if (build_background(t)) build_pending |= build_request_layout(t, VB_NARROW, std::vector<int>{col}, false, true, std::string(), plan_only ? nullptr : p);      // (the worker builds it; the guard is its to evaluate)
+        if (build_background(t)) build_pending |= build_request_layout(t, VB_NARROW, std::vector<int>{col}, false, true, std::string(), o.plan_only ? nullptr : p);      // (the worker builds it; the guard is its to evaluate)
         else if (budget_room(VhBuf::bytes(t->cap_seg, t->padded_rows * (uint64_t)nwidth)) && device_room(need)) { const size_t had = t->narrows.size(); (void)table_narrow_locked(t, col, true); t->inline_builds += t->narrows.size() > had; }
         else t->pred_seen[col] = 0;
       }
@@ -732,8 +736,8 @@ int QueryBuild::snapshot_segments() {
   r->info.scanned_recs = scanned_recs;
   r->info.scanned_segments = scanned_segments;
   // a compile pays off for scans of some size (or when asked for): small tables keep the interpreting kernels
-  if (jit_try && !(p->flags & VH_PLAN_FORCE_JIT) && vh_jit_policy() != VH_JIT_FORCE && (ag ? ag->rows_max : rows_to_scan) < vh_jit_min_rows()) jit_try = false;
-  if (plan_only) {   // vh_query_select: filter program, column slots and the segment snapshot are all it shares
+  if (jit_try && !(p->flags & VH_PLAN_FORCE_JIT) && vh_jit_policy() != VH_JIT_FORCE && (o.ag ? o.ag->rows_max : rows_to_scan) < vh_jit_min_rows()) jit_try = false;
+  if (o.plan_only) {   // vh_query_select: filter program, column slots and the segment snapshot are all it shares
     P.nseg = nseg;
     // Every leaf a field of one usable bit-sliced projection (shape_filter found it: the program and its literals fit the kernel arguments, every
     // set leaf's field has a truth table), a filter to evaluate, none of the flags that keep a plan off the planes: the select reads the planes
@@ -759,7 +763,7 @@ int QueryBuild::snapshot_segments() {
 // selectivity of the filter, from a one-launch probe; it only depends on the filter and the rows, so it is cached
 // until the table changes. Sharded queries plan with the estimate all ranks agreed on.
 int QueryBuild::probed_selectivity(double* sel) {
-  if (ag) { *sel = ag->sel; return VH_OK; }
+  if (o.ag) { *sel = o.ag->sel; return VH_OK; }
   if (p->nfilter == 0) { *sel = 1.0; probe_passed = probe_sampled = rows_to_scan; return VH_OK; }   // no filter: every row passes
   std::string key((const char*)prog.data(), sizeof(VhProgOp) * prog.size());
   key.append((const char*)r->h_lits.data(), sizeof(uint64_t) * r->h_lits.size());
@@ -781,9 +785,9 @@ int QueryBuild::shape_groups() {
   int rc = VH_OK;
   // ---------------- group columns
   P.ngroup = p->ngroups;
-  if (summary_out) for (int i = 0; i < VH_MAX_GROUP; ++i) { summary_out->klo[i] = ~0ull; summary_out->khi[i] = 0; }
-  r->device_rows = device_rows;
-  dense_ok = !force_hash && !(p->flags & VH_PLAN_FORCE_HASH);
+  if (o.summary_out) for (int i = 0; i < VH_MAX_GROUP; ++i) { o.summary_out->klo[i] = ~0ull; o.summary_out->khi[i] = 0; }
+  r->device_rows = o.device_rows;
+  dense_ok = !o.rp.force_hash && !(p->flags & VH_PLAN_FORCE_HASH);
   int key_bits_total = 0;
   for (int i = 0; i < p->ngroups; ++i) {
     const vh_group_col& gc = p->groups[i];
@@ -817,8 +821,8 @@ int QueryBuild::shape_groups() {
     } else {
       uint64_t klo = ~0ull, khi = 0;
       for (uint32_t sgi : live) { klo = std::min(klo, t->stats[gc.col][sgi].lo); khi = std::max(khi, t->stats[gc.col][sgi].hi); }
-      if (summary_out) { summary_out->klo[i] = klo; summary_out->khi[i] = khi; }
-      if (ag) { klo = ag->klo[i]; khi = ag->khi[i]; }      // the range over ALL ranks' segments: identically indexed tables everywhere
+      if (o.summary_out) { o.summary_out->klo[i] = klo; o.summary_out->khi[i] = khi; }
+      if (o.ag) { klo = o.ag->klo[i]; khi = o.ag->khi[i]; }      // the range over ALL ranks' segments: identically indexed tables everywhere
       if (klo > khi) { lo = 0; extent = 1; }
       else {
         lo = bits_of_order_key(c.elem, klo);
@@ -833,15 +837,15 @@ int QueryBuild::shape_groups() {
       else G *= extent;
     }
   }
-  if (summary_out) {       // sharded queries, first half: report and stop
-    summary_out->rows_to_scan = rows_to_scan;
+  if (o.summary_out) {       // sharded queries, first half: report and stop
+    o.summary_out->rows_to_scan = rows_to_scan;
     double sel = 0;
     if (fast_ok || jit_try || p->nfilter == 0) { rc = probed_selectivity(&sel); if (rc) return rc; }
-    summary_out->probe_passed = probe_passed; summary_out->probe_sampled = probe_sampled;
+    o.summary_out->probe_passed = probe_passed; o.summary_out->probe_sampled = probe_sampled;
     done = true;
     return VH_OK;
   }
-  const uint64_t plan_rows = ag ? ag->rows_to_scan : rows_to_scan;
+  const uint64_t plan_rows = o.ag ? o.ag->rows_to_scan : rows_to_scan;
   const uint64_t dense_limit = std::max<uint64_t>(4096, std::min<uint64_t>(1ull << 24, plan_rows * 4));
   if (G > dense_limit) dense_ok = false;
   if (dense_ok) {
@@ -1042,7 +1046,7 @@ int QueryBuild::choose_organisation() {
   // Global atomics are written through to the fabric one by one; when the group-id space is too big
   // for one LDS table but splits into <= VH_MAX_PART LDS-sized ranges, radix-partition the survivors
   // and aggregate each range in LDS instead (DENSE_PART).
-  if (mode == VH_MODE_DENSE_GLOBAL && fastj && !no_part && !(p->flags & (VH_PLAN_NO_PART | VH_PLAN_FORCE_GLOBAL)) && P.nmetric >= 1 && P.nmetric <= VH_FAST_COLS) {
+  if (mode == VH_MODE_DENSE_GLOBAL && fastj && !o.rp.no_part && !(p->flags & (VH_PLAN_NO_PART | VH_PLAN_FORCE_GLOBAL)) && P.nmetric >= 1 && P.nmetric <= VH_FAST_COLS) {
     int shift = 0;
     const size_t part_table_bytes = test_env("VH_PART_TABLE_KB") ? (size_t)atoi(test_env("VH_PART_TABLE_KB")) * 1024 : 128 * 1024;      // (tests shrink it between two queries to force many ranges)   // one 1024-thread block per CU in phase 2 (160 KB LDS)
     // The presence byte rides in a 32-bit SUM state when there is one (SOP_ADD32P: a 64-bit word whose upper half counts rows): two LDS
@@ -1058,11 +1062,11 @@ int QueryBuild::choose_organisation() {
     const bool two_level = np > VH_MAX_PART;
     bool want_part = np <= (uint64_t)VH_MAX_PART * 64 && G <= 0xFFFFFFFFull && !(two_level && (p->flags & VH_PLAN_NO_PART2));
     double sel = 0;
-    if (want_part && !part_tuples_override) {       // (a forced plan still sizes its tuple buffer from the estimate)
+    if (want_part && !o.rp.part_override) {       // (a forced plan still sizes its tuple buffer from the estimate)
       rc = probed_selectivity(&sel);
       if (rc) { return rc; }
     }
-    if (want_part && !(p->flags & VH_PLAN_FORCE_PART) && !part_tuples_override) {
+    if (want_part && !(p->flags & VH_PLAN_FORCE_PART) && !o.rp.part_override) {
       bool covered = false;
       if (!(p->flags & VH_PLAN_NO_PACK)) {
         for (auto& pk : t->packs) {
@@ -1086,7 +1090,7 @@ int QueryBuild::choose_organisation() {
       // ... and the second phase has a price that does not depend on the rows (every block clears and merges a 120 KB LDS
       // table: ~0.25 ms for 13 partitions), while what partitioning saves grows with the survivors: ~50 ms per 1 G rows and
       // point of selectivity beyond the crossover. A 125 M-row shard of C3 (8 GPUs) stays on direct atomics, 1 G rows do not.
-      const double shard_rows = (double)(ag ? ag->rows_max : rows_to_scan);
+      const double shard_rows = (double)(o.ag ? o.ag->rows_max : rows_to_scan);
       if (want_part && shard_rows * (sel - (covered ? 0.03 : 0.045)) < (two_level ? 1e7 : 3.5e6)) want_part = false;      // (C3 shards: 125 M rows 0.733 ms direct vs 0.74-0.78 partitioned, 250 M rows 1.30 vs 1.18)
       // Round 3: with the scan compiled for the plan and two-word tuples leaving as whole lines (then the per-wave writer, now the block's ring writer) a tuple costs ~10 ps
       // against ~86 ps for its two direct atomics, and phase 2's fixed cost is ~0.1 ms: an eighth of C3 (125 M rows, 6.2 M survivors) runs
@@ -1202,7 +1206,7 @@ int QueryBuild::choose_organisation() {
       P.lds_present_off = (uint32_t)off; if (part_carrier < 0) off += gpp;
       lds_table = (off + 15) / 16 * 16;
       P.lds_bytes = (uint32_t)lds_table;
-      part_tuple_cap = part_tuples_override ? part_tuples_override
+      part_tuple_cap = o.rp.part_override ? o.rp.part_override
                      : std::max<uint64_t>((uint64_t)((double)rows_to_scan * std::max(sel, 0.02) * 1.25), 1ull << 16);
       part_tuple_cap = std::min<uint64_t>(part_tuple_cap, rows_to_scan + 1);
     }
@@ -1243,10 +1247,10 @@ int QueryBuild::choose_organisation() {
     // sizing: explicit override (regrow) > caller's hint > what the same group columns produced last time > 1 M
     const auto seen = t->groups_seen.find(sig);
     const uint64_t hint = p->groups_hint ? p->groups_hint : (seen != t->groups_seen.end() ? seen->second + seen->second / 4 : 0);
-    uint64_t want = hash_capacity_override ? hash_capacity_override
+    uint64_t want = o.rp.cap_override ? o.rp.cap_override
                   : std::max<uint64_t>(hint ? hint * 2 : (1ull << 20), 1ull << 12);
     const uint64_t cap_rows = std::max<uint64_t>(rows_to_scan * 2, 1ull << 12);
-    if (!hash_capacity_override) want = std::min(want, cap_rows);
+    if (!o.rp.cap_override) want = std::min(want, cap_rows);
     capacity = 1; while (capacity < want) capacity <<= 1;
     P.hmask = capacity - 1;
     P.max_probe = (uint32_t)std::min<uint64_t>(capacity - 1, 2048);
@@ -1306,7 +1310,7 @@ int QueryBuild::plan_hashed_partitioning() {
   // (Sharded queries take it too: what ranks exchange — finalised groups and, for a bitset metric, (group, id) pairs by owner — does not
   // depend on how a rank aggregated its shard, so the choice need not even agree between ranks; with an agreement it is made from the
   // agreed figures all the same.)
-  if (mode == VH_MODE_HASH && jit_try && (!lanes || (p->flags & VH_PLAN_FORCE_HPART)) && !no_hpart && !(p->flags & VH_PLAN_NO_HPART) && !(t->hpart_hopeless.count(r->group_sig) && !(p->flags & VH_PLAN_FORCE_HPART)) && P.key_words == 1 && P.nmetric >= 1 && rows_to_scan) {
+  if (mode == VH_MODE_HASH && jit_try && (!lanes || (p->flags & VH_PLAN_FORCE_HPART)) && !o.rp.no_hpart && !(p->flags & VH_PLAN_NO_HPART) && !(t->hpart_hopeless.count(r->group_sig) && !(p->flags & VH_PLAN_FORCE_HPART)) && P.key_words == 1 && P.nmetric >= 1 && rows_to_scan) {
     int bits = 0, nb = 0;
     bool ok = true;
     for (int j = 0; j < P.nmetric; ++j) {
@@ -1321,18 +1325,18 @@ int QueryBuild::plan_hashed_partitioning() {
       const double survivors = (double)rows_to_scan * sel;
       const auto seen = t->groups_seen.find(r->group_sig);
       const uint64_t known = p->groups_hint ? p->groups_hint : (seen != t->groups_seen.end() ? seen->second : 0);
-      const double survivors_dec = ag ? (double)ag->rows_max * sel : survivors;      // (what the decision looks at: the largest shard's)
+      const double survivors_dec = o.ag ? (double)o.ag->rows_max * sel : survivors;      // (what the decision looks at: the largest shard's)
       // worth it when the groups are many (the LDS front table then only wastes probes) and the tuples pay for three more launches:
       // C5 (count-distinct) 15.9 ms through the plain table against 5.6 ms, C5t (groups + COUNT alone) 4.0 against 2.8 ms
       // (profiles/r03/NOTES.md; the first version of the tuple path lost that one, 5-6 ms)
       hpart = (p->flags & VH_PLAN_FORCE_HPART) || (survivors_dec >= 8e6 && known >= 2000000);
       if (hpart) {
-        hp_tuple_cap = part_tuples_override ? part_tuples_override : std::max<uint64_t>((uint64_t)(survivors * 1.25) + 1024, 1ull << 16);
+        hp_tuple_cap = o.rp.part_override ? o.rp.part_override : std::max<uint64_t>((uint64_t)(survivors * 1.25) + 1024, 1ull << 16);
         hp_tuple_cap = std::min<uint64_t>(hp_tuple_cap, rows_to_scan + 1);
         if (nb) {    // the tuples carry the row's ids, two at a time: a row of k ids writes max(1, ceil(k / 2)) tuples — at most rows + (ids + rows) / 2 of them
           const uint64_t worst = (bitset_ids[0] + std::min<uint64_t>(hp_tuple_cap, rows_to_scan)) / 2 + 1;
           const uint64_t by_ids = std::min<uint64_t>(worst, (uint64_t)(((double)bitset_ids[0] * std::max(sel, 0.02) * 1.25 + (double)hp_tuple_cap) / 2) + (1ull << 16));
-          hp_tuple_cap = part_tuples_override ? hp_tuple_cap + worst : std::max(hp_tuple_cap, by_ids) + (1ull << 16);
+          hp_tuple_cap = o.rp.part_override ? hp_tuple_cap + worst : std::max(hp_tuple_cap, by_ids) + (1ull << 16);
           hp_units = 2;
           // Packed tuples: 16 bytes instead of 32 when the payload values and two ids fit ONE word next to their count. The bits come from
           // what the mirror knows about the scanned segments: min / max of the metric columns (refresh_stats), the largest id (bs_maxid).
@@ -1389,15 +1393,15 @@ int QueryBuild::plan_hashed_partitioning() {
         for (int j = 0; j < P.nmetric; ++j) slot_bytes += P.m[j].sop() == SOP_BITSET ? 4 : vh_sop_bytes(P.m[j].sop());      // (a cardinality, in LDS: 32 bits)
         auto table_bytes = [&](uint32_t g, uint32_t q) { return (size_t)(g + 1) * slot_bytes + (size_t)q * 8; };
         const size_t budget = 136 * 1024;                       // of the 160 KB a block may own (lists, counters and alignment take the rest)
-        uint32_t passes = hp_passes_override ? hp_passes_override : 1, gs = 256, ss = nb ? 1024 : 0;
-        if (const char* env_passes = test_env("VH_TEST_HPART_PASSES")) if (!hp_passes_override) passes = (uint32_t)std::max(1, atoi(env_passes));
+        uint32_t passes = o.rp.hp_passes ? o.rp.hp_passes : 1, gs = 256, ss = nb ? 1024 : 0;
+        if (const char* env_passes = test_env("VH_TEST_HPART_PASSES")) if (!o.rp.hp_passes) passes = (uint32_t)std::max(1, atoi(env_passes));
         for (;;) {       // tables for one pass's share of a range at <= 70 % load; what the LDS cannot hold takes more passes
           const double load_g = knobs().hp_load_g, load_s = knobs().hp_load_s;
-          const bool need_g = hp_passes_override ? true : groups_est / passes > load_g * gs, need_s = nb && (hp_passes_override ? true : ids_est / passes > load_s * ss);
+          const bool need_g = o.rp.hp_passes ? true : groups_est / passes > load_g * gs, need_s = nb && (o.rp.hp_passes ? true : ids_est / passes > load_s * ss);
           if (need_g && table_bytes(gs * 2, ss) <= budget && (!need_s || gs * 4 <= ss * 2 || table_bytes(gs, ss * 2) > budget)) { gs *= 2; continue; }
           if (need_s && table_bytes(gs, ss * 2) <= budget) { ss *= 2; continue; }
           if (need_g && table_bytes(gs * 2, ss) <= budget) { gs *= 2; continue; }
-          if (hp_passes_override || (!need_g && !need_s) || passes >= 64) break;      // (a re-plan takes the biggest tables that fit, whatever the estimate said)
+          if (o.rp.hp_passes || (!need_g && !need_s) || passes >= 64) break;      // (a re-plan takes the biggest tables that fit, whatever the estimate said)
           passes *= 2;
         }
         P.hp_passes = (int32_t)passes; P.hp_gslots = (int32_t)gs; P.hp_sslots = (int32_t)ss;

@@ -57,7 +57,9 @@ static int select_count_locked(vh_table* t, VhExec* x, const vh_select_plan* sp,
   p.filter = sp->filter; p.nfilter = sp->nfilter; p.lits = sp->lits; p.nlits = sp->nlits;
   p.seg_rows = sp->seg_rows; p.nseg = sp->nseg; p.flags = sp->flags;
   vh_result* pr = nullptr;
-  int rc = query_launch_locked(t, x, &p, &pr, 0, false, 0, false, true);
+  VhLaunchOpts o;
+  o.plan_only = true;
+  int rc = query_launch_locked(t, x, &p, &pr, o);
   if (rc) return rc;
   s->pr.reset(pr);
   VhPlanDev& P = s->P;
