@@ -317,7 +317,10 @@ typedef struct vh_result_info {
                                         and 13 are set too, bits 22 and 25 when the filter has VH_F_INSET leaves; bits 0, 1 and 5 are clear);
                                 bit 27: the aggregate was computed ON the bit-sliced planes, sums and min / max by popcount (VH_PLAN2_PLANE_AGG:
                                         bits 4, 11 and 13 are set too, bits 22 and 25 when the filter has VH_F_INSET leaves; bits 0, 1, 5 and 26
-                                        are clear, and so are the projection's bits 3, 7 and 15-18: no payload is gathered) */
+                                        are clear, and so are the projection's bits 3, 7 and 15-18: no payload is gathered);
+                                bit 28: the grouped form is SUB-SORTED by the column of a range leaf (tiles ordered by grouping value, then that
+                                        column's field, then row) and the scan TRIMMED every run to the words that can pass the leaf, found
+                                        through 64 boundary keys per tile (bits 20 and 21 are set too) */
   uint64_t returned_groups;  /* rows vh_result_copy delivers (= ngroups without HAVING) */
 } vh_result_info;
 

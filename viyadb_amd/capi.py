@@ -149,6 +149,7 @@ INFO_INSET_SEARCH = 1 << 23       # ... bit 23: at least one of them by binary s
 INFO_INSET_SLICED = 1 << 25       # ... bit 25: all of them from truth tables on the bit-sliced predicate planes instead (no lookup per row)
 INFO_SLICED_PREBUILT = 1 << 26    # ... bit 26: a pre-built scan read the filter off the bit-sliced predicate planes (bits 4, 11 and 13 are set too)
 INFO_PLANE_AGG = 1 << 27          # ... bit 27: the aggregate was computed on the bit-sliced planes (bits 4, 11 and 13 are set too; bits 0, 1, 5 and 26 are clear)
+INFO_SUBTRIM = 1 << 28             # ... bit 28: the clustered planes are a sub-sorted form's and every run was trimmed by the sub column's leaf (bits 20 and 21 are set too)
 INFO_EVICTED = 1 << 24            # ... bit 24: planning this query evicted at least one derived layout (tables with a layout budget)
 
 

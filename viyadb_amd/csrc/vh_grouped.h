@@ -12,6 +12,12 @@
 // the place of the lane's row `bit` (which must be set in eq) is vh_grouped_pos(). The builder (group_bits_kernel, vh_small_kernels.h)
 // and the scan (vj_scan's grouped push, vh_jit_body.h) BOTH call this function and nothing else, so the two cannot drift apart;
 // tests/grouped_pos_host.cc runs it as plain C++ over synthetic tiles.
+//
+// The SUB-SORTED form (VhGrouped::sub_col >= 0; the second half of this file) orders every tile by (grouping value, sub key, row) instead,
+// the sub key being the field the bit-sliced projection keeps of one range-compared column. start[] means the same; a row's place no longer
+// follows from the row-order masks (vh_grouped_pos does not apply), so the form is read through its clustered planes only. Inside a run the
+// keys ascend, so the places that can pass a range leaf on the sub column are one stretch of the run: 64 boundary keys per tile, kfirst[w] =
+// the key at place 32 w, let the scan cut the run down to the words of that stretch (vh_gsub_trim). tests/gsub_host.cc runs all of it as plain C++.
 #pragma once
 #include <stdint.h>
 
@@ -64,3 +70,50 @@ VH_GROUP_HD uint32_t vh_gplanes_squeeze(uint32_t word, uint32_t goff, uint32_t g
 }
 // ... and where plane `plane` of the row-order projection lies in a word group (planes of the grouping field have no place)
 VH_GROUP_HD uint32_t vh_gplanes_plane(uint32_t plane, uint32_t goff, uint32_t gbits) { return plane < goff ? plane : plane - gbits; }
+
+// ---- the SUB-SORTED form: tiles ordered by (grouping value, sub key, row). The builder sorts vh_gsub_sort_word() of the tile's rows as plain
+// integers (the row bits make the order stable and total); rows at or beyond the tile's valid rows sort behind every valid one.
+#define VH_GSUB_MAX_BITS 16u         // the sub column's field: its boundary keys are uint16
+#define VH_GSUB_KEYS_BYTES (2u * VH_GROUP_WORDS)       // a tile's boundary keys: 128 bytes
+// relations a run can be trimmed by: the values of vh_relop (include/viya_hip.h), which has NE = 1 between them
+enum { VH_GSUB_EQ = 0, VH_GSUB_LT = 2, VH_GSUB_LE = 3, VH_GSUB_GT = 4, VH_GSUB_GE = 5 };
+VH_GROUP_HD bool vh_gsub_op_ok(int op) { return op == VH_GSUB_EQ || op == VH_GSUB_LT || op == VH_GSUB_LE || op == VH_GSUB_GT || op == VH_GSUB_GE; }
+// the composite key of a row (at most VH_GROUP_MAX_BITS + VH_GSUB_MAX_BITS = 20 bits), and the word the builder sorts (row < 2048)
+VH_GROUP_HD uint32_t vh_gsub_key(uint32_t gval, uint32_t sub, uint32_t sub_bits) { return (gval << sub_bits) | sub; }
+VH_GROUP_HD uint32_t vh_gsub_sort_word(uint32_t key, uint32_t row, bool valid) { return valid ? (key << 11) | row : 0x80000000u | row; }
+VH_GROUP_HD uint32_t vh_gsub_sorted_row(uint32_t sort_word) { return sort_word & (VH_GROUP_TILE - 1u); }
+VH_GROUP_HD uint32_t vh_gsub_sorted_sub(uint32_t sort_word, uint32_t sub_bits) { return (sort_word >> 11) & ((1u << sub_bits) - 1u); }
+// where a segment's boundary keys begin in its share of the header arena (behind the headers of its `tiles` tiles, 64-byte aligned), the
+// share's bytes with them, and where tile `tile`'s 64 keys lie
+VH_GROUP_HD uint64_t vh_gsub_keys_off(uint64_t tiles, uint32_t bits) { return (tiles * vh_grouped_hdr_bytes(bits) + 63u) / 64u * 64u; }
+VH_GROUP_HD uint64_t vh_gsub_hdr_stride(uint64_t tiles, uint32_t bits) { return vh_gsub_keys_off(tiles, bits) + tiles * VH_GSUB_KEYS_BYTES; }
+VH_GROUP_HD uint64_t vh_gsub_tile_off(uint64_t tiles, uint32_t bits, uint32_t tile) { return vh_gsub_keys_off(tiles, bits) + (uint64_t)tile * VH_GSUB_KEYS_BYTES; }
+// The stretch [*s2, *e2) of the run [start, end) that holds every place whose key satisfies `key op lit` (lit in field space). kfirst: the
+// tile's boundary keys; only entries of places inside the run are read. Keys ascend along the run, so a word w that begins inside the run
+// (32 w >= start) with kfirst[w] already past the literal ends the stretch at 32 w, and one with kfirst[w] still short of it lets the stretch
+// begin at 32 w — both found by binary search over the run's words (at most six steps each). A trimmed side is a multiple of 32, the other
+// the run's own bound; the stretch is conservative (the leaf is still evaluated on every word kept), never tight.
+VH_GROUP_HD void vh_gsub_trim(const uint16_t* kfirst, uint32_t start, uint32_t end, int op, uint32_t lit, uint32_t* s2, uint32_t* e2) {
+  *s2 = start; *e2 = end;
+  if (start >= end || !vh_gsub_op_ok(op)) return;
+  const uint32_t w0 = (start + 31u) >> 5, w1 = (end + 31u) >> 5;       // the words that BEGIN inside the run: w0 .. w1 (exclusive)
+  if (op == VH_GSUB_LT || op == VH_GSUB_LE || op == VH_GSUB_EQ) {      // the back: the first such word whose first key is past the literal
+    uint32_t lo = w0, hi = w1;
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      const uint32_t k = kfirst[mid];
+      if (op == VH_GSUB_LT ? k >= lit : k > lit) hi = mid; else lo = mid + 1u;
+    }
+    if (lo < w1) *e2 = lo * 32u;
+  }
+  if (op == VH_GSUB_GT || op == VH_GSUB_GE || op == VH_GSUB_EQ) {      // the front: the last such word whose first key is still short of it
+    uint32_t lo = w0, hi = w1;                                          // (lo: the first word whose first key is NOT short)
+    while (lo < hi) {
+      const uint32_t mid = (lo + hi) >> 1;
+      const uint32_t k = kfirst[mid];
+      if (op == VH_GSUB_GT ? k <= lit : k < lit) lo = mid + 1u; else hi = mid;
+    }
+    if (lo > w0) *s2 = (lo - 1u) * 32u;
+  }
+  if (*s2 > *e2) *s2 = *e2;
+}

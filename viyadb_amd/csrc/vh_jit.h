@@ -3,7 +3,9 @@
 // Compiler::Compile src/codegen/compiler.cc:97-144). Host side; the device-side frame is vh_jit_body.h.
 #pragma once
 #include "vh_internal.h"
+#include "vh_grouped.h"
 #include <string>
+static_assert(VH_GSUB_EQ == VH_OP_EQ && VH_GSUB_LT == VH_OP_LT && VH_GSUB_LE == VH_OP_LE && VH_GSUB_GT == VH_OP_GT && VH_GSUB_GE == VH_OP_GE, "vh_grouped.h names the relations by vh_relop's values");
 #include <vector>
 
 #define VJ_MAX_PRED 8       // distinct predicate columns held packed in registers
@@ -62,6 +64,10 @@ struct VhJitShape {
   // fields above it lie pp_bits[pp_group] planes lower in a word group). The scan then reads the run of the literal in every tile and nothing
   // else: no plane of pp_group (no other leaf reads it), no prefix over its masks. -1: off.
   int gp_slot = -1, gp_G = 0, gp_goff = 0;
+  // ... of a SUB-SORTED form (vh_grouped.h), every run TRIMMED to the words that can pass the one leaf on the sub column: `sub_slot` holds the
+  // tiles' boundary keys (128 bytes a tile), `sub_pred` is the leaf's predicate column, `sub_op` its relation (LT, LE, GT, GE or EQ) and
+  // `sub_lit` its literal. -1: off — the runs are read whole; these enter key() only when set.
+  int sub_slot = -1, sub_pred = -1, sub_op = 0, sub_lit = 0;
   // Streamed payload: every group / metric value of the plan is a bit field of ONE 4-byte record per row (a bit-field projection, VhPack::bits).
   // Instead of queueing a survivor's ROW and gathering its record afterwards (a random 128-byte line per survivor: at 5 % selectivity 81 % of
   // the projection's lines are fetched anyway, at the rate random lines come in), the scan streams the records with the predicate planes —

@@ -71,6 +71,7 @@ std::string VhJitShape::key() const {
   for (int i = 0; i < ng; ++i) col(g[i]);
   for (int j = 0; j < nm; ++j) col(m[j]);
   if (drain_depth) { k += "dd"; put(drain_depth); }      // (depth 0 keeps the names its kernels always had)
+  if (sub_slot >= 0) { k += "st"; put(sub_slot); put(sub_pred); put(sub_op); put(sub_lit); }      // (likewise: a scan that trims no run keeps its name)
   return k;
 }
 
@@ -122,7 +123,12 @@ static std::string vj_int_array(const char* name, int n, const std::vector<int>&
 
 std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
   std::string t;
-  t += "// generated by vh_jit.hip for one plan shape; the frame is vh_jit_body.h\n#define VH_HPART_KERNELS\n#include \"vh_jit_body.h\"\n#include \"vh_hpart.h\"\n";
+  // (a scan that trims the runs of a sub-sorted form says so ahead of the frame; every other shape's text is what it always was)
+  const bool subtrim = s.pp_sliced && s.pp_group >= 0 && s.pp_group < s.npred && !s.qpay && !s.lanes && s.gp_slot >= 0 && s.gp_G > 0 &&
+                       s.sub_slot >= 0 && s.sub_pred >= 0 && s.sub_pred < s.npred && s.sub_pred != s.pp_group && vh_gsub_op_ok(s.sub_op);
+  t += "// generated by vh_jit.hip for one plan shape; the frame is vh_jit_body.h\n#define VH_HPART_KERNELS\n";
+  if (subtrim) t += "#define VJ_SUBTRIM 1\n";
+  t += "#include \"vh_jit_body.h\"\n#include \"vh_hpart.h\"\n";
   t += "typedef uint32_t vj_u32x2 __attribute__((ext_vector_type(2)));\n#define vj_b(x) __builtin_amdgcn_ballot_w64(x)\n";
   // ---- packed predicate registers: stream p (a predicate column, or a plane of the bit-packed predicate projection) occupies
   //      v[base[p] .. base[p] + 4 * width) of every lane
@@ -241,6 +247,16 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
                       nva, s.pp_bits[p], (int)VH_OP_EQ, sbase[p], c.c_str(), neg.c_str());
     glit_fn = vj_fmt("  static __device__ __forceinline__ uint32_t glit(const Lits& L) {\n    const uint64_t c = %s;\n    return (%s || (c >> %d) != 0ull) ? ~0u : (uint32_t)c;\n  }\n",
                      c.c_str(), neg.c_str(), s.pp_bits[p]);
+  }
+  // a trimming scan: the sub column's literal in field space, ~0u when no value of the field equals it (the runs are then read whole)
+  if (subtrim) {
+    const int p = s.sub_pred, ty = s.pred[p].type;
+    const std::string l = lit_name(s.sub_lit, ty);
+    const bool sgn = ty == VH_I8 || ty == VH_I16 || ty == VH_I32 || ty == VH_I64;
+    const std::string c = vj_fmt("(uint64_t)%s%s", sgn ? "(int64_t)" : "", l.c_str()), neg = sgn ? "(" + l + " < 0)" : std::string("false");
+    glit_fn += vj_fmt("  static constexpr int SUB_SLOT = %d, SUB_OP = %d;\n", s.sub_slot, s.sub_op);
+    glit_fn += vj_fmt("  static __device__ __forceinline__ uint32_t sublit(const Lits& L) {\n    const uint64_t c = %s;\n    return (%s || (c >> %d) != 0ull) ? ~0u : (uint32_t)c;\n  }\n",
+                      c.c_str(), neg.c_str(), s.pp_bits[p]);
   }
   std::vector<std::pair<std::string, std::string>> st;      // (mask expression, bool expression)
   std::string set_decl;                                     // set leaves: one lookup per row slot and leaf, shared by the two expressions
@@ -843,6 +859,11 @@ static bool vj_canonical(int which, VhJitShape* s) {
   // the pipelined drain (VhJitShape::drain_depth): 25 / 26 = case 22 at depth 1 / 2; 27, 28, 29 = cases 21 (row-order planes over the grouped
   // records), 7 (the compressed 8-byte record) and 1 (arenas: no packed record, so depth 0 whatever is asked for) at the depth a query gets
   int depth = -1;
+  if (which == 33) {      // C3 on a SUB-SORTED form: case 25 whose runs are trimmed by the d3 leaf (boundary keys in slot 16)
+    if (!vj_canonical(25, s)) return false;
+    S.sub_slot = 16; S.sub_pred = 1; S.sub_op = VH_OP_LT; S.sub_lit = 1;
+    return true;
+  }
   switch (which) { case 25: which = 22; depth = 1; break; case 26: which = 22; depth = 2; break; case 27: which = 21; depth = -2; break; case 28: which = 7; depth = -2; break; case 29: which = 1; depth = -2; break; default: break; }
   if (depth != -1) {
     if (!vj_canonical(which, s)) return false;

@@ -700,6 +700,9 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
     constexpr uint32_t G = (uint32_t)J::GP_G;
     if (glit == ~0u) have = false;              // no value of the field equals the literal: nothing is queued (the headers are never indexed with it)
     const uint32_t nvals = 1u << J::G_BITS;
+#ifdef VJ_SUBTRIM
+    const uint32_t sublit = J::sublit(L);
+#endif
     // the next up to 64 tiles of this wave that lie in ONE segment and begin below its snapshot; their header loads are issued, not awaited
     auto collect = [&](uint32_t& c_n, uint32_t& c_seg, uint32_t& c_base, uint32_t& c_start, uint32_t& c_end) {
       c_n = 0; c_seg = seg; c_base = 0; c_start = 0; c_end = 0;
@@ -727,6 +730,14 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
         c_end = glit + 1u < nvals ? (uint32_t)h[glit + 1u] : valid;       // (the field's last value: the run ends with the tile's valid rows)
         if (c_end > valid) c_end = valid;                               // (a run never leaves the tile's block, whatever a header says)
         if (c_start > c_end) c_start = c_end;
+#ifdef VJ_SUBTRIM
+        // a sub-sorted form (vh_grouped.h): the run shrinks to the words that can pass the leaf on the sub column — everything behind this
+        // line sees a shorter run and nothing else. (Only boundary keys of places inside the run are read: 32 w < c_end <= valid.)
+        if (sublit != ~0u) {
+          const uint16_t* kf = reinterpret_cast<const uint16_t*>(P.colbase[J::SUB_SLOT] + (uint64_t)c_seg * P.colstride[J::SUB_SLOT] + (uint64_t)(c_base / VH_GROUP_TILE) * VH_GSUB_KEYS_BYTES);
+          vh_gsub_trim(kf, c_start, c_end, J::SUB_OP, sublit, &c_start, &c_end);
+        }
+#endif
       }
     };
     auto drain_gp = [&](uint32_t dseg, bool all) {

@@ -903,6 +903,9 @@ __global__ __launch_bounds__(256) void pack_bits_kernel(const VhPackBitsArgs A) 
 // 2048 rows stable-sorted by the low `gbits` bits of column `gsrc` (the field a bit-sliced predicate projection keeps of it), and the tile's
 // header start[0 .. 2^gbits) beside it. One block per job = per tile (J.first a multiple of 2048); only rows below J.seg_rows take part, so
 // a place never reaches the tile's valid rows. The tile's 8 KB are staged in LDS in their new order and leave as whole lines.
+// With a sub column (sub_bits != 0; vh_grouped.h) the order inside a run is (sub key, row) instead of row alone — the sub key being the
+// column's field of the clustered planes' word, which the rows hold in registers anyway — and the tile's 64 boundary keys are written
+// behind the segment's headers.
 struct VhGroupArgs {
   VhPackBitsArgs B;                    // the records: columns, fields, destination = the grouped arena (same stride as the ungrouped one)
   const char* gsrc; uint64_t gsrc_stride; uint32_t gesize, gbits;
@@ -913,6 +916,9 @@ struct VhGroupArgs {
   const char* psrc[VH_PACK_MAX_COLS]; uint64_t psrc_stride[VH_PACK_MAX_COLS];
   uint32_t pesize[VH_PACK_MAX_COLS], pbitoff[VH_PACK_MAX_COLS];
   char* planes; uint64_t planes_stride;
+  // the SUB-SORTED form (vh_grouped.h; sub_bits == 0: none, and it needs the planes): the sub column's field in the squeezed field word, and
+  // where the segment's boundary keys begin in its share of the header arena
+  uint32_t sub_off, sub_bits; uint64_t keys_off;
 };
 __global__ __launch_bounds__(256) void group_bits_kernel(const VhGroupArgs A) {
   constexpr uint32_t NL = VH_GROUP_TILE / 32u;             // lanes of the scan's wave step
@@ -922,6 +928,8 @@ __global__ __launch_bounds__(256) void group_bits_kernel(const VhGroupArgs A) {
   __shared__ uint32_t s_eq[1 << VH_GROUP_MAX_BITS][NL];       // value v, lane l: the lane's rows that hold v
   __shared__ uint16_t s_before[1 << VH_GROUP_MAX_BITS][NL];   // ... and how many rows of the lanes below it do
   __shared__ uint16_t s_total[1 << VH_GROUP_MAX_BITS], s_start[1 << VH_GROUP_MAX_BITS];
+  __shared__ uint32_t s_key[VH_GROUP_TILE];                // sub-sorted form: the rows' sort words, then sorted
+  __shared__ uint16_t s_place[VH_GROUP_TILE];              // ... and the place every row came to
   const VhJob J = A.B.jobs[blockIdx.x];
   const uint32_t seg = J.seg, tile_base = J.first, nvals = 1u << A.gbits;
   const uint32_t nvalid = J.seg_rows > tile_base ? (J.seg_rows - tile_base < VH_GROUP_TILE ? J.seg_rows - tile_base : VH_GROUP_TILE) : 0u;
@@ -992,12 +1000,39 @@ __global__ __launch_bounds__(256) void group_bits_kernel(const VhGroupArgs A) {
     reinterpret_cast<uint16_t*>(A.hdr + (uint64_t)seg * A.hdr_stride + vh_grouped_hdr_off(tile_base / VH_GROUP_TILE, A.gbits))[threadIdx.x] = (uint16_t)st;
   }
   __syncthreads();
+  // The sub-sorted form: the tile's rows sorted by (value, sub key, row) — a bitonic sort of vh_gsub_sort_word() in LDS, stable through the
+  // row bits; rows beyond the valid ones sort to the end. start[] above holds as it is (it counts values, whatever the order inside a run); a
+  // row's place is where its word comes to lie, and the boundary keys are read off every 32nd word.
+  const bool sub = A.sub_bits != 0u && A.planes != nullptr;       // (block-uniform)
+  if (sub) {
+#pragma unroll
+    for (uint32_t k = 0; k < NK; ++k) {
+      const uint32_t i = k * 256u + threadIdx.x;
+      s_key[i] = vh_gsub_sort_word(vh_gsub_key(r_val[k], (r_pw[k] >> A.sub_off) & ((1u << A.sub_bits) - 1u), A.sub_bits), i, i < nvalid);
+    }
+    __syncthreads();
+    for (uint32_t size = 2u; size <= VH_GROUP_TILE; size <<= 1) {
+      for (uint32_t stride = size >> 1; stride; stride >>= 1) {
+        for (uint32_t p = threadIdx.x; p < VH_GROUP_TILE / 2u; p += 256u) {
+          const uint32_t i = ((p & ~(stride - 1u)) << 1) | (p & (stride - 1u)), j = i | stride;       // (i < j < VH_GROUP_TILE)
+          const uint32_t a = s_key[i], b = s_key[j];
+          if ((a > b) == ((i & size) == 0u)) { s_key[i] = b; s_key[j] = a; }
+        }
+        __syncthreads();
+      }
+    }
+    for (uint32_t at = threadIdx.x; at < VH_GROUP_TILE; at += 256u) s_place[vh_gsub_sorted_row(s_key[at])] = (uint16_t)at;
+    if (threadIdx.x < VH_GROUP_WORDS)
+      reinterpret_cast<uint16_t*>(A.hdr + (uint64_t)seg * A.hdr_stride + A.keys_off + (uint64_t)(tile_base / VH_GROUP_TILE) * VH_GSUB_KEYS_BYTES)[threadIdx.x] =
+          (uint16_t)vh_gsub_sorted_sub(s_key[32u * threadIdx.x], A.sub_bits);
+    __syncthreads();
+  }
 #pragma unroll
   for (uint32_t k = 0; k < NK; ++k) {
     const uint32_t i = k * 256u + threadIdx.x;
     if (i >= nvalid) continue;
     const uint32_t v = r_val[k], l = i >> 5;
-    const uint32_t at = vh_grouped_pos(s_eq[v][l], s_before[v][l], s_start[v], i & 31u);      // (a permutation of [0, nvalid): every valid row has exactly one place)
+    const uint32_t at = sub ? (uint32_t)s_place[i] : vh_grouped_pos(s_eq[v][l], s_before[v][l], s_start[v], i & 31u);      // (a permutation of [0, nvalid): every valid row has exactly one place)
     s_out[at] = r_rec[k]; s_pout[at] = r_pw[k];
   }
   __syncthreads();

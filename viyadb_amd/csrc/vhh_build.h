@@ -180,9 +180,10 @@ static bool build_request_layout(vh_table* t, int kind, const std::vector<int>& 
 
 // The grouped form (VhGrouped) of projection `serial` by column `col`. It is no layout of its own but a second form of a projection that
 // exists, so its job is short: grouped_build under t->mu (build_run_grouped), the kernel enqueued on the library's stream like any refresh.
-static bool build_request_grouped(vh_table* t, uint64_t serial, uint64_t pp_serial, int col, uint32_t bits, const std::string& seen, const vh_plan* plan) {
-  const std::string key = "g:" + std::to_string(serial) + ":" + std::to_string(col) + ":" + std::to_string(bits) + ":" + std::to_string(pp_serial);
-  return build_queue(t, VB_GROUPED, key, [&](VhBuildJob& j) { j.cols.assign(1, col); j.gbits = bits; j.serial = serial; j.pp_serial = pp_serial; j.seen = seen; }, plan);
+// `sub_col`: the column a form built by this job is sub-sorted by (-1: none), decided where the job was asked for.
+static bool build_request_grouped(vh_table* t, uint64_t serial, uint64_t pp_serial, int col, uint32_t bits, int sub_col, const std::string& seen, const vh_plan* plan) {
+  const std::string key = "g:" + std::to_string(serial) + ":" + std::to_string(col) + ":" + std::to_string(bits) + ":" + std::to_string(pp_serial) + (sub_col >= 0 ? ":s" + std::to_string(sub_col) : std::string());
+  return build_queue(t, VB_GROUPED, key, [&](VhBuildJob& j) { j.cols.assign(1, col); j.cols.push_back(sub_col); j.gbits = bits; j.serial = serial; j.pp_serial = pp_serial; j.seen = seen; }, plan);
 }
 
 static void build_arenas_moving(vh_table* t) {
@@ -283,7 +284,7 @@ static int build_run_kernel(VhBuildJob* j) {
 // that is about to be replaced holds counts as free.
 // Under a layout budget the same two questions are put to it first, planes included and then without (derived_make_room: it may evict other
 // layouts, never `pk` or `pp`); a no counts in vh_table::declined unless this is vh_table_prepare, which the budget never refuses.
-static int grouped_room(vh_table* t, const VhPack* pk, const VhPredPack* pp = nullptr, uint32_t gbits = 0) {
+static int grouped_room(vh_table* t, const VhPack* pk, const VhPredPack* pp = nullptr, uint32_t gbits = 0, bool sub = false) {
   size_t free_b = 0, total_b = 0;
   const size_t need = (size_t)t->cap_seg * pk->rec.stride;
   const bool with_planes = pp && pp->sliced && pp->bits > gbits;
@@ -294,7 +295,8 @@ static int grouped_room(vh_table* t, const VhPack* pk, const VhPredPack* pp = nu
     const uint64_t credit = gr ? gr->rec.held + gr->hdr.held + gr->planes.held : 0;
     const uint64_t tiles = (t->segment_rows + VH_GROUP_TILE - 1) / VH_GROUP_TILE;
     const uint64_t base = VhBuf::bytes(t->cap_seg, pk->rec.stride) + VhBuf::bytes(t->cap_seg, (tiles * vh_grouped_hdr_bytes(gbits) + 63) / 64 * 64);
-    if (with_planes && derived_make_room(t, base + VhBuf::bytes(t->cap_seg, vh_gplanes_seg_bytes(t->segment_rows, vh_gplanes_group(pp->bits - gbits))), pk, pp, credit)) budget = 2;
+    const uint64_t keys = sub ? (uint64_t)t->cap_seg * tiles * VH_GSUB_KEYS_BYTES : 0;      // (a sub-sorted form's boundary keys come with its planes)
+    if (with_planes && derived_make_room(t, base + keys + VhBuf::bytes(t->cap_seg, vh_gplanes_seg_bytes(t->segment_rows, vh_gplanes_group(pp->bits - gbits))), pk, pp, credit)) budget = 2;
     else if (derived_make_room(t, base, pk, pp, credit)) budget = 1;
     else { ++t->declined; return 0; }
   }
@@ -316,11 +318,12 @@ static int build_run_grouped(VhBuildJob* j) {
     for (auto& q : t->packs) if (q->serial == j->serial) pk = q.get();
     VhPredPack* pp = nullptr;
     for (auto& q : t->predpacks) if (j->pp_serial && q->serial == j->pp_serial) pp = q.get();
-    if (pk && pk->grouped && (!pp || (pk->grouped->planes.ptr && pk->grouped->pp_serial == pp->serial))) return 0;          // (vh_table_prepare or the worker's own query was faster; one grouped form per projection)
-    const int room = pk ? grouped_room(t, pk, pp, j->gbits) : 0;
+    const int sub_col = j->cols.size() > 1 ? j->cols[1] : -1;
+    if (pk && pk->grouped && (!pp || (pk->grouped->planes.ptr && pk->grouped->pp_serial == pp->serial && (sub_col < 0 || pk->grouped->sub_col == sub_col)))) return 0;          // (vh_table_prepare or the worker's own query was faster; one grouped form per projection)
+    const int room = pk ? grouped_room(t, pk, pp, j->gbits, sub_col >= 0) : 0;
     if (pk && pk->grouped && room < 2) return 0;          // (no room for the planes it lacks: the records it has stay)
     if (room) {
-      if (grouped_build(t, pk, j->cols[0], j->gbits, room == 2 ? pp : nullptr) != VH_OK) { (void)hipGetLastError(); outcome = 1; }
+      if (grouped_build(t, pk, j->cols[0], j->gbits, room == 2 ? pp : nullptr, room == 2 ? sub_col : -1) != VH_OK) { (void)hipGetLastError(); outcome = 1; }
       else if (pk->grouped) outcome = 0;
     }
     if (outcome != 0) t->gather_seen[j->seen] = 0;      // the job came to nothing: the sightings start again

@@ -115,6 +115,7 @@ static void grouped_launch(const vh_table* t, const VhPack* pk, const VhJob* d_j
       A.psrc[c] = col.base; A.psrc_stride[c] = col.stride; A.pesize[c] = (uint32_t)col.esize; A.pbitoff[c] = gr->pp_bitoff[c];
     }
     A.planes = gr->planes.ptr; A.planes_stride = gr->planes.stride;
+    if (gr->sub_col >= 0) { A.sub_off = gr->sub_off; A.sub_bits = gr->sub_bits; A.keys_off = vh_gsub_keys_off((t->segment_rows + VH_GROUP_TILE - 1) / VH_GROUP_TILE, gr->bits); }
   }
   hipLaunchKernelGGL(group_bits_kernel, dim3((unsigned)njobs), dim3(256), 0, st, A);
 }
@@ -274,7 +275,12 @@ static void grouped_drop(vh_table* t, VhPack* pk) {      // (the caller made the
   buf_free(t, &gr->rec); buf_free(t, &gr->hdr); buf_free(t, &gr->planes);
   pk->grouped.reset();
 }
-static void grouped_no_planes(vh_table* t, VhGrouped* gr) {      // the grouped records alone answer from now on
+// The grouped records alone answer from now on — unless the form is sub-sorted: its places follow from no row-order formula, nothing can
+// read it without the planes, so the whole form goes (the caller made the table idle: derived_idle).
+static void grouped_no_planes(vh_table* t, VhPack* pk) {
+  VhGrouped* gr = pk->grouped.get();
+  if (!gr) return;
+  if (gr->sub_col >= 0) { grouped_drop(t, pk); return; }
   buf_free(t, &gr->planes);
   gr->planes.stride = 0; gr->G = 0; gr->pp_serial = 0;
 }
@@ -287,6 +293,16 @@ static bool grouped_planes_describe(const vh_table* t, VhGrouped* gr, const VhPr
   gr->G = vh_gplanes_group(pp->bits - gr->bits); gr->goff = pp->bitoff[at];
   gr->planes.stride = vh_gplanes_seg_bytes(t->segment_rows, gr->G);
   gr->pp_serial = pp->serial; gr->pp_cols = pp->cols; gr->pp_bitoff = pp->bitoff; gr->pp_bitw = pp->bitw;
+  return true;
+}
+// The sub-sort of a form whose planes were just described: `sub_col`'s field in the squeezed field word. false: the planes have no such field
+// (or it is the grouping column's, or wider than a boundary key) — the form stays in row order inside its runs.
+static bool grouped_sub_describe(VhGrouped* gr, const VhPredPack* pp, int sub_col) {
+  gr->sub_col = -1; gr->sub_bits = 0; gr->sub_off = 0;
+  if (!pp || sub_col < 0 || sub_col == gr->col || !gr->G) return false;
+  const size_t at = (size_t)(std::find(pp->cols.begin(), pp->cols.end(), sub_col) - pp->cols.begin());
+  if (at >= pp->cols.size() || pp->bitw[at] == 0 || pp->bitw[at] > VH_GSUB_MAX_BITS) return false;
+  gr->sub_col = sub_col; gr->sub_bits = pp->bitw[at]; gr->sub_off = vh_gplanes_plane(pp->bitoff[at], gr->goff, gr->bits);
   return true;
 }
 // Re-derive the tiles that hold a row journalled since the grouped form was last current: whole tiles (one changed row moves the places of
@@ -305,16 +321,17 @@ static int grouped_refresh(vh_table* t, VhPack* pk) {
     return (int)VH_OK;
   });
   if (rc == VH_NO_ROOM) { grouped_drop(t, pk); return VH_OK; }
-  if (gr->G && !gr->planes.ptr) grouped_no_planes(t, gr);      // (there was no room for the planes)
+  if (gr->G && !gr->planes.ptr) grouped_no_planes(t, pk);      // (there was no room for the planes; a sub-sorted form goes whole: the launch wrote it in row order)
   return rc;
 }
 // The grouped form of `pk` by column `col`, whose field in the bit-sliced planes has `bits` bits: built (or built again for another column or
 // width) and brought up to date. Bit-field records of 4 bytes only; nullptr and VH_OK where there is no room for it.
 // `pp`: the bit-sliced predicate projection whose other columns' bits are kept clustered beside the records (nullptr: records alone — no such
 // projection, or no room). A form whose planes belong to another projection than `pp` starts over: records, headers and planes are one launch.
-static int grouped_build(vh_table* t, VhPack* pk, int col, uint32_t bits, const VhPredPack* pp = nullptr) {
+// `sub_col`: the column whose field sub-sorts the runs (-1: none; taken only together with the planes); a form of another sub column starts over.
+static int grouped_build(vh_table* t, VhPack* pk, int col, uint32_t bits, const VhPredPack* pp = nullptr, int sub_col = -1) {
   if (!pk->bits || pk->rec_bytes != 4 || bits == 0 || bits > VH_GROUP_MAX_BITS || col < 0 || (size_t)col >= t->cols.size()) return VH_OK;
-  if (pk->grouped && (pk->grouped->col != col || pk->grouped->bits != bits || (pp && (!pk->grouped->planes.ptr || pk->grouped->pp_serial != pp->serial)))) {
+  if (pk->grouped && (pk->grouped->col != col || pk->grouped->bits != bits || (pp && (!pk->grouped->planes.ptr || pk->grouped->pp_serial != pp->serial)) || pk->grouped->sub_col != (pp ? sub_col : -1))) {
     if (int rc = derived_idle(t)) return rc;
     grouped_drop(t, pk);
   }
@@ -325,7 +342,7 @@ static int grouped_build(vh_table* t, VhPack* pk, int col, uint32_t bits, const 
     const uint64_t tiles = (t->segment_rows + VH_GROUP_TILE - 1) / VH_GROUP_TILE;
     gr->rec.stride = pk->rec.stride;
     gr->hdr.stride = (tiles * vh_grouped_hdr_bytes(bits) + 63) / 64 * 64;
-    (void)grouped_planes_describe(t, gr, pp);
+    if (grouped_planes_describe(t, gr, pp) && grouped_sub_describe(gr, pp, sub_col)) gr->hdr.stride = vh_gsub_hdr_stride(tiles, bits);
   }
   return grouped_refresh(t, pk);
 }
@@ -483,7 +500,7 @@ static void predpack_drop(vh_table* t, VhPredPack* pp) {
   derived_drop(t, &t->predpacks, pp, [&] {
     for (int q = 0; q < pp->nplanes; ++q) buf_free(t, &pp->plane[q]);
     for (auto& pk : t->packs)        // clustered planes derived from it go with it (the grouped records stay)
-      if (pk->grouped && pk->grouped->pp_serial == pp->serial) grouped_no_planes(t, pk->grouped.get());
+      if (pk->grouped && pk->grouped->pp_serial == pp->serial) grouped_no_planes(t, pk.get());
   });
 }
 static int predpack_refresh(vh_table* t, VhPredPack* pp) {

@@ -51,7 +51,9 @@ void QueryBuild::predpack_auto(bool want_sliced) {
 //     first such column in program order is the grouping column —
 // and the projection's grouped form by that column exists at the planes' epoch. Where the automatic layouts are built (vh_table_prepare, or the
 // VH_AUTO_PACK-th query of the shape; on a background-build table by the worker, see vhh_build.h) it is built under the same
-// "leaves a quarter of the device free" rule. VH_PLAN_NO_GROUPED keeps the ungrouped records: an A/B inside one process.
+// "leaves a quarter of the device free" rule — on a table of VH_SUBSORT_MIN_ROWS rows SUB-SORTED by the column of the filter's first range
+// leaf, whose runs the scan then trims (see below). VH_PLAN_NO_GROUPED keeps the ungrouped records: an A/B inside one process.
+#define VH_SUBSORT_MIN_ROWS (4ull << 20)      // rows a table must hold before a grouped form built for it is sub-sorted
 void QueryBuild::choose_grouped() {
   VhJitShape& js = jshape;
   if ((p->flags & VH_PLAN_NO_GROUPED) || !js.pp_sliced || lanes || js.qpay || !packed || !packed_use || !sliced_use || !packed_bits || packed_rec != 4 || P.nbitset) return;
@@ -86,35 +88,67 @@ void QueryBuild::choose_grouped() {
   const int gcol = jit_pred_col[gp];
   const uint32_t gbits = (uint32_t)js.pp_bits[gp];
   VhGrouped* gr = packed_use->grouped.get();
+  // The SUB column (vh_grouped.h): the column of the first leaf of the conjunction, in program order, that is a relation a run can be trimmed
+  // by (LT, LE, GT, GE, EQ) on a field of the planes other than the grouping column's, of at most VH_GSUB_MAX_BITS bits. A form built now is
+  // sub-sorted by it where the table holds VH_SUBSORT_MIN_ROWS rows (below that both paths are launch-bound, and the sub-sorted form gives up
+  // the records-only readers) — VH_TEST_SUBSORT=1 / 0 forces it on / off — and only together with its planes.
+  int sp = -1, sp_leaf = -1;
+  for (int k : leaves) {
+    if (g[k].kind() != VH_F_REL || !vh_gsub_op_ok((int)g[k].op())) continue;
+    const int ps = (int)g[k].pslot();
+    if (ps < js.npred && ps != gp && jit_pred_col[ps] >= 0 && js.pp_bits[ps] >= 1 && js.pp_bits[ps] <= (int)VH_GSUB_MAX_BITS) { sp = ps; sp_leaf = k; break; }
+  }
+  const int scol = sp >= 0 ? jit_pred_col[sp] : -1;
+  const char* const sub_hook = test_env("VH_TEST_SUBSORT");
+  int sub_want = -1;
+  if (scol >= 0 && sliced_use->bits > gbits) {
+    uint64_t rows = 0;
+    for (uint32_t s = 0; s < t->nseg; ++s) rows += t->seg_rows[s];
+    if (sub_hook ? atoi(sub_hook) != 0 : rows >= VH_SUBSORT_MIN_ROWS) sub_want = scol;
+  }
   // the form is built where it is missing, is another column's, or lacks the clustered planes of the bit-sliced projection this plan reads
   // (that projection was dropped and described again since): records, headers and planes come out of one launch, so it starts over
   const bool other = gr && (gr->col != gcol || gr->bits != gbits);
   const bool bare = gr && !other && sliced_use->bits > gbits && (!gr->planes.ptr || gr->pp_serial != sliced_use->serial);
+  // (one form per projection: a form sub-sorted by another column, or by none, serves this plan without trimming; only a prepared plan has it
+  // built again for its own sub column — or, under the hook that forces the sub-sort off, without one)
+  const bool resub = gr && !other && !bare && g_preparing && gr->sub_col != sub_want && (sub_want >= 0 || (sub_hook && !atoi(sub_hook)));
   auto build = [&]() {
     const int auto_after = g_preparing ? 1 : knobs().auto_pack;
     if (auto_after <= 0) return;
     if (other && !g_preparing) return;         // (one grouped form per projection: only a prepared plan replaces another column's)
-    const std::string sig = "g:" + std::to_string(packed_use->serial) + ":" + std::to_string(gcol) + (bare ? ":" + std::to_string(sliced_use->serial) : std::string());
+    const std::string sig = "g:" + std::to_string(packed_use->serial) + ":" + std::to_string(gcol) + (bare ? ":" + std::to_string(sliced_use->serial) : std::string()) + (resub ? ":s" + std::to_string(sub_want) : std::string());
     // background build mode: the worker's own query (build_warm), run because the layouts this plan's sightings asked for now exist, builds the
     // form here, off every caller's path; a caller's query that finds projection and planes without it asks for a job after its own sightings
     const bool bg = build_background(t), own = bg && g_build_worker;
     if (!own) {
       if (g_build_quiet) return;
       if (++t->gather_seen[sig] < (uint32_t)auto_after) return;
-      if (bg) { build_pending |= build_request_grouped(t, packed_use->serial, sliced_use->serial, gcol, gbits, sig, p); return; }
+      if (bg) { build_pending |= build_request_grouped(t, packed_use->serial, sliced_use->serial, gcol, gbits, sub_want, sig, p); return; }
     }
-    const int room = grouped_room(t, packed_use, sliced_use, gbits);
-    if (!room || (bare && room < 2)) { t->gather_seen[sig] = 0; return; }      // (a form that lacks only its planes is kept where there is no room for them)
-    if (grouped_build(t, packed_use, gcol, gbits, room == 2 ? sliced_use : nullptr) != VH_OK) { (void)hipGetLastError(); return; }
+    const int room = grouped_room(t, packed_use, sliced_use, gbits, sub_want >= 0);
+    if (!room || ((bare || resub) && room < 2)) { t->gather_seen[sig] = 0; return; }      // (a form that lacks only its planes, or its sub-sort, is kept where there is no room for them)
+    if (grouped_build(t, packed_use, gcol, gbits, room == 2 ? sliced_use : nullptr, room == 2 ? sub_want : -1) != VH_OK) { (void)hipGetLastError(); return; }
     if (!bg) ++t->inline_builds;
   };
-  if (!gr || other || bare) {
+  if (!gr || other || bare || resub) {
     build();
     gr = packed_use->grouped.get();
     if (!gr || gr->col != gcol || gr->bits != gbits) return;
   }
   // as current as the planes whose bits give the places, and as the table: anything else is a stale layout
   if (!gr->rec.ptr || !gr->hdr.ptr || gr->applied_epoch != t->sync_epoch || sliced_use->applied_epoch != t->sync_epoch || packed_use->applied_epoch != t->sync_epoch) return;
+  // Whether the plan reads the CLUSTERED planes is settled first: a sub-sorted form can be read through them alone (a place follows from no
+  // row-order formula there), so a plan that may not — VH_PLAN_NO_GPLANES, a second leaf on the grouping column, a snapshot that cuts into a
+  // built tile — leaves the form alone and gathers the ungrouped records of the projection, which always exist.
+  bool planes_ok = !(p->flags & VH_PLAN_NO_GPLANES) && gr->planes.ptr && gr->G && gr->pp_serial == sliced_use->serial && P.nslots + 1 < VH_MAX_SLOTS;
+  if (planes_ok) {
+    int reads = 0;
+    for (const VhProgOp& o : g) if (o.kind() != VH_F_AND && o.kind() != VH_F_OR && o.kind() != VH_F_TRUE && (int)o.pslot() == gp) ++reads;
+    planes_ok = reads == 1;
+  }
+  for (uint32_t s = 0; s < nseg && planes_ok; ++s) if (x->h_segrows[s] != (uint32_t)t->seg_rows[s] && x->h_segrows[s] % VH_GROUP_TILE != 0) planes_ok = false;
+  if (gr->sub_col >= 0 && !planes_ok) return;
   for (int s = 0; s < P.nslots; ++s) if (slot_rec[s] == 0 && slot_bits[s] == 4) P.colbase[s] = gr->rec.ptr;      // (a bit record's members all start at the record)
   P.colbase[P.nslots] = gr->hdr.ptr; P.colstride[P.nslots] = gr->hdr.stride; P.colpitch[P.nslots] = vh_grouped_hdr_bytes(gbits);
   js.pp_group = gp; js.pp_group_hdr = P.nslots++; js.pp_group_lit = (int)g[leaf_of[gp]].lit();
@@ -126,14 +160,38 @@ void QueryBuild::choose_grouped() {
   //   * every segment's snapshot is the rows the form was built with or a multiple of the tile (0 included): places have lost their row
   //     numbers, so a snapshot that cuts into a built tile cannot be honoured — such a plan keeps the row-order planes, as before.
   // VH_PLAN_NO_GPLANES keeps the row-order planes: an A/B inside one process.
-  if ((p->flags & VH_PLAN_NO_GPLANES) || !gr->planes.ptr || !gr->G || gr->pp_serial != sliced_use->serial || P.nslots >= VH_MAX_SLOTS) return;
-  int reads = 0;
-  for (const VhProgOp& o : g) if (o.kind() != VH_F_AND && o.kind() != VH_F_OR && o.kind() != VH_F_TRUE && (int)o.pslot() == gp) ++reads;
-  if (reads != 1) return;
-  for (uint32_t s = 0; s < nseg; ++s) if (x->h_segrows[s] != (uint32_t)t->seg_rows[s] && x->h_segrows[s] % VH_GROUP_TILE != 0) return;
+  if (!planes_ok) return;
   P.colbase[P.nslots] = gr->planes.ptr; P.colstride[P.nslots] = gr->planes.stride; P.colpitch[P.nslots] = 4u * gr->G;
   js.gp_slot = P.nslots++; js.gp_G = (int)gr->G; js.gp_goff = (int)gr->goff;
   gplanes = true;
+  // The scan TRIMS its runs (vh_gsub_trim) when the form is sub-sorted, exactly one leaf of the whole program reads its sub column (the rule
+  // the grouping column has), that leaf is a relation of the top-level AND a run can be trimmed by, and its literal is a value of the field —
+  // otherwise the runs are read whole, which is right for any order inside them. VH_TEST_NO_SUBTRIM=1 reads a sub-sorted form without
+  // trimming: an A/B inside one process.
+  if (gr->sub_col < 0 || P.nslots >= VH_MAX_SLOTS) return;
+  if (const char* e = test_env("VH_TEST_NO_SUBTRIM")) if (atoi(e)) return;
+  sp = -1; sp_leaf = -1;
+  for (int k : leaves) {
+    const int ps = (int)g[k].pslot();
+    if (g[k].kind() == VH_F_REL && vh_gsub_op_ok((int)g[k].op()) && ps < js.npred && ps != gp && jit_pred_col[ps] == gr->sub_col) { sp = ps; sp_leaf = k; break; }
+  }
+  if (sp < 0 || (uint32_t)js.pp_bits[sp] != gr->sub_bits) return;
+  int sreads = 0;
+  for (const VhProgOp& o : g) if (o.kind() != VH_F_AND && o.kind() != VH_F_OR && o.kind() != VH_F_TRUE && (int)o.pslot() == sp) ++sreads;
+  if (sreads != 1) return;
+  {   // the literal in field space: a non-negative integer below 2^bits
+    const VhProgOp& lf = g[sp_leaf];
+    const int ty = (int)lf.type(), es = vh_elem_size(ty);
+    if (vh_elem_float(ty) || (int)lf.lit() >= VH_INLINE_LITS) return;
+    uint64_t v = P.ilits[lf.lit()];
+    if (es < 8) v &= (1ull << (8 * es)) - 1ull;
+    if (vh_elem_signed(ty) && es < 8) v = (uint64_t)((int64_t)(v << (64 - 8 * es)) >> (64 - 8 * es));
+    if ((vh_elem_signed(ty) && (int64_t)v < 0) || (v >> gr->sub_bits) != 0ull) return;
+  }
+  const uint64_t tiles = (t->segment_rows + VH_GROUP_TILE - 1) / VH_GROUP_TILE;
+  P.colbase[P.nslots] = gr->hdr.ptr + vh_gsub_keys_off(tiles, gbits); P.colstride[P.nslots] = gr->hdr.stride; P.colpitch[P.nslots] = VH_GSUB_KEYS_BYTES;
+  js.sub_slot = P.nslots++; js.sub_pred = sp; js.sub_op = (int)g[sp_leaf].op(); js.sub_lit = (int)g[sp_leaf].lit();
+  subtrim = true;
 }
 
 int vh_jit_drain_depth(const VhJitShape& s) {
@@ -859,7 +917,7 @@ int QueryBuild::launch() {
   if (jk) { narrowed = jshape.pp_nplanes || jshape.pp_sliced; for (int k = 0; k < jshape.npred; ++k) narrowed |= jshape.pred[k].width != vh_elem_size(jshape.pred[k].type); }
   r->hpart = hpart;
   r->info.reserved = (hpart ? 64 : 0) | (fastj || jk ? 1 : 0) | (lanes ? 2 : 0) | (P.lds_hash_slots ? 4 : 0) | (packed ? 8 : 0) | (fastj && narrowed ? 16 : 0) | (jk ? 32 : 0) | (packed && packed_compressed ? 128 : 0) | (hpart && hp_pack ? 256 : 0) | (mode == VH_MODE_DENSE_PART && P.gid_bits ? 1024 : 0) | (jk && (jshape.pp_nplanes || jshape.pp_sliced) ? 2048 : 0) | (jk && jshape.qpay ? 4096 : 0) | (jk && jshape.pp_sliced ? 8192 : 0) | (mode == VH_MODE_DENSE_PART && P.gid_bits && P.tuple4 ? 16384 : 0)
-                   | (has_set ? 1u << 22 : 0) | (has_set && set_search ? 1u << 23 : 0) | (jk && has_set && set_truth && jshape.pp_sliced ? 1u << 25 : 0) | (build_pending ? 1u << 19 : 0) | (jk && grouped ? 1u << 20 : 0) | (jk && grouped && gplanes ? 1u << 21 : 0) | (packed && packed_bits ? 32768 : 0) | (packed ? (uint32_t)(31 - __builtin_clz(std::max<uint32_t>(packed_rec, 2)) - 1) << 16 : 0);
+                   | (has_set ? 1u << 22 : 0) | (has_set && set_search ? 1u << 23 : 0) | (jk && has_set && set_truth && jshape.pp_sliced ? 1u << 25 : 0) | (build_pending ? 1u << 19 : 0) | (jk && grouped ? 1u << 20 : 0) | (jk && grouped && gplanes ? 1u << 21 : 0) | (jk && grouped && gplanes && subtrim ? 1u << 28 : 0) | (packed && packed_bits ? 32768 : 0) | (packed ? (uint32_t)(31 - __builtin_clz(std::max<uint32_t>(packed_rec, 2)) - 1) << 16 : 0);
   r->fast_scan = (r->info.reserved & 1u) != 0;
   // the pre-built scan over the bit-sliced planes: bit 26, with the bits of a predicate projection's bit-sliced form (and of the sets' truth tables);
   // no register-resident kernel, no lanes form, no compiled kernel ran

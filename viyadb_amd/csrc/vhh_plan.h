@@ -287,6 +287,7 @@ struct QueryBuild {
   bool budget_room(uint64_t need);               // an automatic build of `need` bytes fits the table's layout budget, after evictions if need be (false: declined, counted)
   bool grouped = false;                          // the records come from the projection's grouped form (vh_result_info.reserved bit 20)
   bool gplanes = false;                          // ... and the predicate bits from the clustered planes beside them (bit 21)
+  bool subtrim = false;                          // ... of a sub-sorted form, every run trimmed to the words that can pass the sub column's leaf (bit 28)
   void choose_grouped();                         // compile_kernel: point a qualifying plan at the grouped records (building them where the automatic layouts are built)
   std::vector<int> pp_cols;                      // the filter's columns (ascending) when every leaf reads a fixed-width column: what a predicate projection must hold
   int pp_boff[VJ_MAX_PRED] = {}, pp_bbits[VJ_MAX_PRED] = {}, pp_soff[VJ_MAX_PRED] = {}, pp_sbits[VJ_MAX_PRED] = {};      // predicate column k's bit field in the byte-plane / bit-sliced projection noted in jshape

@@ -75,6 +75,11 @@ struct VhGrouped : VhLayout {
   VhBuf planes; uint32_t G = 0;
   uint64_t pp_serial = 0; uint32_t goff = 0;
   std::vector<int> pp_cols; std::vector<uint8_t> pp_bitoff, pp_bitw;
+  // The SUB-SORTED form (vh_grouped.h): every tile ordered by (value of `col`, field of `sub_col`, row), 64 boundary keys per tile behind the
+  // segment's headers in `hdr` (whose stride grows by them). sub_col == -1: the form in row order inside a run, byte for byte as it ever was.
+  // The sub key is taken from the clustered planes' field word (sub_off: the field's bit there), so a sub-sorted form always has its planes:
+  // a place follows from no row-order formula any more, and a form that loses its planes is dropped whole (grouped_no_planes).
+  int sub_col = -1; uint32_t sub_bits = 0, sub_off = 0;
 };
 // Payload projection (vh_table_pack): a row-major copy of a few columns, see pack_kernel.
 struct VhPack : VhLayout {

@@ -106,6 +106,12 @@ class AggResult:
         """The aggregate was computed on the bit-sliced planes (PLAN2_PLANE_AGG / VH_PLANE_AGG=1): derived from `flags`, no field of its own."""
         return bool(self.flags & capi.INFO_PLANE_AGG)
 
+    @property
+    def sub_trimmed(self) -> bool:
+        """The grouped form is sub-sorted and the scan trimmed every run to the words that can pass the sub column's leaf (bit 28; bits 20
+        and 21 are set too): derived from `flags`, like plane_agg."""
+        return bool(self.flags & capi.INFO_SUBTRIM)
+
 
 class DeviceTable:
     """vh_table: the HBM mirror of a db::Table's segment store."""
