@@ -320,7 +320,9 @@ typedef struct vh_result_info {
                                         are clear, and so are the projection's bits 3, 7 and 15-18: no payload is gathered);
                                 bit 28: the grouped form is SUB-SORTED by the column of a range leaf (tiles ordered by grouping value, then that
                                         column's field, then row) and the scan TRIMMED every run to the words that can pass the leaf, found
-                                        through 64 boundary keys per tile (bits 20 and 21 are set too) */
+                                        through 64 boundary keys per tile (bits 20 and 21 are set too);
+                                bit 29: the scan over the clustered planes filled every wave's group of up to 64 tiles ACROSS segment boundaries
+                                        and queued a survivor as its record's table-wide index (bits 20 and 21 are set too) */
   uint64_t returned_groups;  /* rows vh_result_copy delivers (= ngroups without HAVING) */
 } vh_result_info;
 
@@ -800,6 +802,9 @@ VH_API int vh_measure_read_bandwidth(uint64_t bytes, int32_t iters, double* byte
  * (0..24, see vj_canonical) into `text`, compiles it with hipRTC for gfx950 — no GPU needed — and stores the code object at `hsaco_path`
  * (NULL: nowhere). VH_E_INVALID: no such shape; VH_E_UNSUPPORTED: the compile failed (`text` then starts with the log). */
 VH_API int vh_jit_selftest(int32_t which, const char* hsaco_path, char* text, uint64_t text_bytes);
+/* The name a query's kernel of canonical shape `which` would carry ("viya_jit_scan_" + eight hex digits of the shape's key): shapes that
+ * differ in a member that enters the key have different names. VH_E_INVALID: no such shape. */
+VH_API int vh_jit_selftest_name(int32_t which, char* name, uint64_t name_bytes);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,8 @@ group is sunk) against the same plan with VH_TEST_DRAIN_DEPTH=0 (one drain after
 round the median, min and max of the kernel time (scan + phase 2) of 20 queries. The legs must have run different code objects (the
 kernel's name carries the shape's hash, and the depth is part of the shape): anything else is an error.
 A second test knob can be swept the same way (the resident-block cap: `VH_TEST_BLOCKS_PER_CU 3,4,5`; the wave scans as shuffles:
-`VH_JIT_FLAGS -DVH_WAVE_SCAN_SHFL=1,default`); "default" leaves the knob unset.
+`VH_JIT_FLAGS -DVH_WAVE_SCAN_SHFL=1,default`; the clustered scan's tile groups kept inside a segment: `VH_TEST_NO_GPSPAN 1,default`; longer
+units: `VH_TEST_UNIT_ROWS 32768,131072,262144`); "default" leaves the knob unset.
 usage: python tools/drain_ab.py [segments=1000] [rounds=3] [knob=VH_TEST_DRAIN_DEPTH] [values=0,default]"""
 import json, os, sys, time
 os.environ["VH_TEST_HOOKS"] = "1"            # the gate in front of the library's test hooks (viya_hip.hip test_env)

@@ -150,6 +150,7 @@ INFO_INSET_SLICED = 1 << 25       # ... bit 25: all of them from truth tables on
 INFO_SLICED_PREBUILT = 1 << 26    # ... bit 26: a pre-built scan read the filter off the bit-sliced predicate planes (bits 4, 11 and 13 are set too)
 INFO_PLANE_AGG = 1 << 27          # ... bit 27: the aggregate was computed on the bit-sliced planes (bits 4, 11 and 13 are set too; bits 0, 1, 5 and 26 are clear)
 INFO_SUBTRIM = 1 << 28             # ... bit 28: the clustered planes are a sub-sorted form's and every run was trimmed by the sub column's leaf (bits 20 and 21 are set too)
+INFO_GPSPAN = 1 << 29              # ... bit 29: the clustered scan's tile groups spanned segments, its queue held table-wide record indexes (bits 20 and 21 are set too)
 INFO_EVICTED = 1 << 24            # ... bit 24: planning this query evicted at least one derived layout (tables with a layout budget)
 
 
@@ -252,6 +253,7 @@ SYMBOLS = {
     "vh_result_free": (None, [_VP]),
     "vh_measure_read_bandwidth": (C.c_int, [C.c_uint64, C.c_int32, C.POINTER(C.c_double)]),
     "vh_jit_selftest": (C.c_int, [C.c_int32, C.c_char_p, C.c_char_p, C.c_uint64]),
+    "vh_jit_selftest_name": (C.c_int, [C.c_int32, C.c_char_p, C.c_uint64]),
 }
 
 _lib = None

@@ -117,3 +117,20 @@ VH_GROUP_HD void vh_gsub_trim(const uint16_t* kfirst, uint32_t start, uint32_t e
   }
   if (*s2 > *e2) *s2 = *e2;
 }
+
+// ---- tile groups that SPAN segments (VhJitShape::gp_span): the clustered scan keeps, per tile, values with the segment already folded in, so
+// that a group of tiles — and the queue of survivors behind it — may cross segments. With rec_units = (the records' segment stride) / 4 and
+// pl_units = (the planes' segment stride) / 16:
+//     a record's table-wide INDEX    seg * rec_units + place in the segment          (byte offset from the arena's base: 4 x index),
+//     a tile's planes, in 16-byte units    seg * pl_units + tile * (a tile's block / 16),
+// both in 32 bits. The host lets a plan span when the strides divide and no index or unit of the scanned segments reaches `bound` (2^32; a
+// test knob lowers it); tests/gspan_host.cc checks the sums against the per-segment addresses as plain C++.
+#define VH_GSPAN_BOUND (1ull << 32)
+VH_GROUP_HD bool vh_gspan_ok(uint64_t nseg, uint64_t rec_stride, uint64_t planes_stride, uint64_t bound) {
+  if (rec_stride % 4u || planes_stride % 16u || bound > VH_GSPAN_BOUND) return false;
+  return nseg * (rec_stride / 4u) <= bound && nseg * (planes_stride / 16u) <= bound;
+}
+VH_GROUP_HD uint32_t vh_gspan_rec(uint32_t seg, uint32_t rec_units, uint32_t place) { return seg * rec_units + place; }
+VH_GROUP_HD uint32_t vh_gspan_tile(uint32_t seg, uint32_t pl_units, uint32_t tile, uint32_t G) { return seg * pl_units + tile * (VH_GROUP_WORDS * (G / 4u)); }
+// byte offset, from the planes' base, of word `word` of the tile whose planes begin at unit `tile_unit` (G is a multiple of 4)
+VH_GROUP_HD uint64_t vh_gspan_word_off(uint32_t tile_unit, uint32_t word, uint32_t G) { return (uint64_t)(tile_unit + word * (G / 4u)) * 16u; }

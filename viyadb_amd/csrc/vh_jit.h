@@ -68,6 +68,10 @@ struct VhJitShape {
   // tiles' boundary keys (128 bytes a tile), `sub_pred` is the leaf's predicate column, `sub_op` its relation (LT, LE, GT, GE or EQ) and
   // `sub_lit` its literal. -1: off — the runs are read whole; these enter key() only when set.
   int sub_slot = -1, sub_pred = -1, sub_op = 0, sub_lit = 0;
+  // ... whose tile groups SPAN segments (vh_grouped.h, vh_gspan_*): a wave fills its group of up to 64 tiles whatever segments they lie in, a
+  // queued survivor is its record's table-wide index, and the drain pipeline is flushed once, after the wave's last group. Set by the host
+  // where the strides divide and the indexes fit 32 bits; 0: a group ends at a segment change. Enters key() only when set.
+  int gp_span = 0;
   // Streamed payload: every group / metric value of the plan is a bit field of ONE 4-byte record per row (a bit-field projection, VhPack::bits).
   // Instead of queueing a survivor's ROW and gathering its record afterwards (a random 128-byte line per survivor: at 5 % selectivity 81 % of
   // the projection's lines are fetched anyway, at the rate random lines come in), the scan streams the records with the predicate planes —
@@ -86,6 +90,8 @@ struct VhJitShape {
 // Bytes of the one packed record a survivor of this shape gathers (4 or 8), 0 for every other payload: arenas, wider records or more than one,
 // streamed records, row ids, the hashed partitioning (its drain takes two survivors per lane: vj_drain2), the no-compaction form.
 int vh_jit_rec_bytes(const VhJitShape& s);
+// Whether a shape's tile groups may span segments (gp_span): the clustered planes, every survivor value a bit field of one 4-byte record.
+bool vh_jit_span_ok(const VhJitShape& s);
 #define VH_DRAIN_DEPTH_MAX 2
 #define VH_DRAIN_DEPTH_DEFAULT 1       // (measured: profiles/r09/NOTES.md)
 // The depth a shape is compiled with: the default, or VH_TEST_DRAIN_DEPTH (a test hook, read when the shape is built: switched between

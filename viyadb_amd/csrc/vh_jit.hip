@@ -72,6 +72,7 @@ std::string VhJitShape::key() const {
   for (int j = 0; j < nm; ++j) col(m[j]);
   if (drain_depth) { k += "dd"; put(drain_depth); }      // (depth 0 keeps the names its kernels always had)
   if (sub_slot >= 0) { k += "st"; put(sub_slot); put(sub_pred); put(sub_op); put(sub_lit); }      // (likewise: a scan that trims no run keeps its name)
+  if (gp_span) { k += "gs"; put(gp_span); }      // (likewise: a scan whose groups end with the segment keeps its name)
   return k;
 }
 
@@ -94,6 +95,18 @@ int vh_jit_rec_bytes(const VhJitShape& s) {
   }
   if (b0->bits) return b0->bits == 4 || b0->bits == 8 ? b0->bits : 0;
   return b0->pitch == 4 && dwords == 1 ? 4 : b0->pitch == 8 && dwords == 3 ? 8 : 0;      // (the whole record in ONE aligned load, as gather() has it)
+}
+
+// Tile groups may span segments (VhJitShape::gp_span) where the scan reads the clustered planes and every value of a survivor is a bit field
+// of ONE 4-byte record — the grouped one: a queue entry is then that record's table-wide index and nothing else asks for the segment.
+bool vh_jit_span_ok(const VhJitShape& s) {
+  if (!s.pp_sliced || s.pp_group < 0 || s.pp_group >= s.npred || s.qpay || s.lanes || s.gp_slot < 0 || s.gp_G <= 0 || s.gp_G % 4 || s.ng + s.nm == 0) return false;
+  const VhJitCol& b0 = s.ng ? s.g[0] : s.m[0];
+  for (int i = 0; i < s.ng + s.nm; ++i) {
+    const VhJitCol& c = i < s.ng ? s.g[i] : s.m[i - s.ng];
+    if (c.rowid || c.bitset || c.rec < 0 || c.rec != b0.rec || c.bits != 4 || c.pitch != 4) return false;
+  }
+  return true;
 }
 
 // ------------------------------------------------------------------ source text
@@ -128,6 +141,9 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
                        s.sub_slot >= 0 && s.sub_pred >= 0 && s.sub_pred < s.npred && s.sub_pred != s.pp_group && vh_gsub_op_ok(s.sub_op);
   t += "// generated by vh_jit.hip for one plan shape; the frame is vh_jit_body.h\n#define VH_HPART_KERNELS\n";
   if (subtrim) t += "#define VJ_SUBTRIM 1\n";
+  // (... and so does one whose tile groups span segments)
+  const bool gpspan = s.gp_span && vh_jit_span_ok(s);
+  if (gpspan) t += "#define VJ_GPSPAN 1\n";
   t += "#include \"vh_jit_body.h\"\n#include \"vh_hpart.h\"\n";
   t += "typedef uint32_t vj_u32x2 __attribute__((ext_vector_type(2)));\n#define vj_b(x) __builtin_amdgcn_ballot_w64(x)\n";
   // ---- packed predicate registers: stream p (a predicate column, or a plane of the bit-packed predicate projection) occupies
@@ -258,6 +274,8 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
     glit_fn += vj_fmt("  static __device__ __forceinline__ uint32_t sublit(const Lits& L) {\n    const uint64_t c = %s;\n    return (%s || (c >> %d) != 0ull) ? ~0u : (uint32_t)c;\n  }\n",
                       c.c_str(), neg.c_str(), s.pp_bits[p]);
   }
+  // a spanning scan: the slot whose stride carries a record's segment into its table-wide index (the one rec_load / gather read through)
+  if (gpspan) glit_fn += vj_fmt("  static constexpr int SPAN_SLOT = %d;\n", s.ng ? s.g[0].slot : s.m[0].slot);
   std::vector<std::pair<std::string, std::string>> st;      // (mask expression, bool expression)
   std::string set_decl;                                     // set leaves: one lookup per row slot and leaf, shared by the two expressions
   int nz = 0;
@@ -864,6 +882,11 @@ static bool vj_canonical(int which, VhJitShape* s) {
     S.sub_slot = 16; S.sub_pred = 1; S.sub_op = VH_OP_LT; S.sub_lit = 1;
     return true;
   }
+  if (which == 34) {      // ... whose tile groups span segments
+    if (!vj_canonical(33, s)) return false;
+    S.gp_span = 1;
+    return true;
+  }
   switch (which) { case 25: which = 22; depth = 1; break; case 26: which = 22; depth = 2; break; case 27: which = 21; depth = -2; break; case 28: which = 7; depth = -2; break; case 29: which = 1; depth = -2; break; default: break; }
   if (depth != -1) {
     if (!vj_canonical(which, s)) return false;
@@ -1018,6 +1041,13 @@ static bool vj_canonical(int which, VhJitShape* s) {
     }
     default: return false;
   }
+}
+
+extern "C" VH_API int vh_jit_selftest_name(int32_t which, char* name, uint64_t name_bytes) {
+  VhJitShape S;
+  if (!vj_canonical(which, &S) || !name || !name_bytes) return VH_E_INVALID;
+  snprintf(name, (size_t)name_bytes, "%s", kernel_name_of(S.key()).c_str());
+  return VH_OK;
 }
 
 extern "C" VH_API int vh_jit_selftest(int32_t which, const char* hsaco_path, char* text, uint64_t text_bytes) {

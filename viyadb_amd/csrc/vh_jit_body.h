@@ -190,7 +190,8 @@ struct VjPend {
   uint32_t n0 = 0, n1 = 0;
 };
 // `all`: a segment change, the end of the wave's work: everything queued AND everything pending is sunk, in the order it left the queue, under
-// `seg` — every pending entry is a place of that segment, because every segment change comes through here with `all` set. A wave that gives up
+// `seg` — every pending entry is a place of that segment, because every segment change comes through here with `all` set (a scan whose
+// groups span segments queues table-wide indexes and says segment 0 throughout: it comes here with `all` once). A wave that gives up
 // (MODE == HASH, V.H.dead) simply never comes back: what it holds is dropped with the attempt.
 template <class J>
 __device__ __forceinline__ void vj_drain_pipe(const VhPlanDev& P, uint32_t seg, const uint32_t* q, uint32_t& cnt, bool all, int lane, VjPend<J>& Q, char* lds, uint64_t xoff,
@@ -696,6 +697,11 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
     // found through 64 slots of the wave's queue and a running maximum (fetch) — and puts the next batch's loads in flight before it drains this batch's
     // survivors. The next group's headers travel while this group's batches run. The same tiles in the same order as the row-order scan
     // (unit decomposition, counters, flush at a segment change, vj_drain): the host cannot tell the two apart.
+    // SPANNING groups (VJ_GPSPAN; vh_grouped.h, vh_gspan_*): a block's next unit lies gridDim.x units on, as a rule in another segment, so a
+    // group that ends with the segment is the few tiles of one unit — one batch with idle lanes, nothing to prefetch, and a flushed drain
+    // pipeline behind it. Here a group is filled whatever segments its tiles lie in: a lane keeps, in the place of its tile's segment and first
+    // row, where the tile's planes begin (in 16-byte units of the planes' arena) and the table-wide index of its first record; a queue entry
+    // is a record's table-wide index, read under segment 0, and only the wave's last group flushes. The same tiles in the same order still.
     static_assert(J::GROUPED && J::SLICED && !J::LANES && J::QPAY == 0, "clustered planes belong to the grouped records");
     constexpr uint32_t G = (uint32_t)J::GP_G;
     if (glit == ~0u) have = false;              // no value of the field equals the literal: nothing is queued (the headers are never indexed with it)
@@ -703,14 +709,22 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
 #ifdef VJ_SUBTRIM
     const uint32_t sublit = J::sublit(L);
 #endif
-    // the next up to 64 tiles of this wave that lie in ONE segment and begin below its snapshot; their header loads are issued, not awaited
+#ifdef VJ_GPSPAN
+    constexpr bool kSpan = true;
+    static_assert(G % 4u == 0u, "spanning groups: a word group is whole 16-byte units of planes");
+    const uint32_t rec_units = (uint32_t)(P.colstride[J::SPAN_SLOT] >> 2), pl_units = (uint32_t)(P.colstride[J::GP_SLOT] >> 4);
+#else
+    constexpr bool kSpan = false;
+#endif
+    // the next up to 64 tiles of this wave that lie in ONE segment (spanning groups: in any) and begin below its snapshot; their header loads
+    // are issued, not awaited. Spanning groups hand back per lane, in c_seg and c_base, the tile's planes unit and its first record's index.
     auto collect = [&](uint32_t& c_n, uint32_t& c_seg, uint32_t& c_base, uint32_t& c_start, uint32_t& c_end) {
       c_n = 0; c_seg = seg; c_base = 0; c_start = 0; c_end = 0;
-      uint32_t c_rows = 0;
-      while (have && c_n < 64u && (c_n == 0u || seg == c_seg)) {
+      uint32_t c_rows = 0, l_seg = 0;
+      while (have && c_n < 64u && (kSpan || c_n == 0u || seg == c_seg)) {
         if (wave_base < seg_rows) {
           if (c_n == 0u) c_seg = seg;
-          if ((uint32_t)lane == c_n) { c_base = wave_base; c_rows = seg_rows; }
+          if ((uint32_t)lane == c_n) { c_base = wave_base; c_rows = seg_rows; l_seg = seg; }
           ++c_n;
         }
         wave_base += kStepRows;
@@ -723,8 +737,9 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
           if (have) { seg_rows = P.seg_rows[seg]; wave_base = useg * P.unit_rows + wave * kWaveRows; }
         }
       }
+      const uint32_t h_seg = kSpan ? l_seg : c_seg;      // (the segment the lane's tile lies in: the group's, or the lane's own)
       if ((uint32_t)lane < c_n) {
-        const uint16_t* h = reinterpret_cast<const uint16_t*>(P.colbase[J::G_HDR] + (uint64_t)c_seg * P.colstride[J::G_HDR] + vh_grouped_hdr_off(c_base / VH_GROUP_TILE, J::G_BITS));
+        const uint16_t* h = reinterpret_cast<const uint16_t*>(P.colbase[J::G_HDR] + (uint64_t)h_seg * P.colstride[J::G_HDR] + vh_grouped_hdr_off(c_base / VH_GROUP_TILE, J::G_BITS));
         const uint32_t valid = c_rows - c_base < VH_GROUP_TILE ? c_rows - c_base : VH_GROUP_TILE;
         c_start = h[glit];
         c_end = glit + 1u < nvals ? (uint32_t)h[glit + 1u] : valid;       // (the field's last value: the run ends with the tile's valid rows)
@@ -734,11 +749,15 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
         // a sub-sorted form (vh_grouped.h): the run shrinks to the words that can pass the leaf on the sub column — everything behind this
         // line sees a shorter run and nothing else. (Only boundary keys of places inside the run are read: 32 w < c_end <= valid.)
         if (sublit != ~0u) {
-          const uint16_t* kf = reinterpret_cast<const uint16_t*>(P.colbase[J::SUB_SLOT] + (uint64_t)c_seg * P.colstride[J::SUB_SLOT] + (uint64_t)(c_base / VH_GROUP_TILE) * VH_GSUB_KEYS_BYTES);
+          const uint16_t* kf = reinterpret_cast<const uint16_t*>(P.colbase[J::SUB_SLOT] + (uint64_t)h_seg * P.colstride[J::SUB_SLOT] + (uint64_t)(c_base / VH_GROUP_TILE) * VH_GSUB_KEYS_BYTES);
           vh_gsub_trim(kf, c_start, c_end, J::SUB_OP, sublit, &c_start, &c_end);
         }
 #endif
       }
+#ifdef VJ_GPSPAN
+      c_seg = vh_gspan_tile(l_seg, pl_units, c_base / VH_GROUP_TILE, G);
+      c_base = vh_gspan_rec(l_seg, rec_units, c_base);
+#endif
     };
     auto drain_gp = [&](uint32_t dseg, bool all) {
       if constexpr (kPipe) { vj_drain_pipe<J>(P, dseg, q, cnt, all, lane, pend, lds, xoff, nfresh, V); return; }
@@ -759,8 +778,9 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
       const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
       uint32_t b_n, b_seg, b_base, b_start, b_end;
       collect(b_n, b_seg, b_base, b_start, b_end);
-      const bool flush = !b_n || b_seg != a_seg;        // queue entries are places of segment a_seg
-      const char* const pseg = P.colbase[J::GP_SLOT] + (uint64_t)a_seg * P.colstride[J::GP_SLOT];
+      const bool flush = !b_n || (!kSpan && b_seg != a_seg);        // queue entries are places of segment a_seg (spanning groups: table-wide indexes)
+      const uint32_t d_seg = kSpan ? 0u : a_seg;
+      const char* const pseg = P.colbase[J::GP_SLOT] + (uint64_t)d_seg * P.colstride[J::GP_SLOT];
       uint32_t vg[J::NVG ? J::NVG : 1];
       uint32_t i_place = 0, i_mask = 0;                  // the lane's item of the batch in flight: its word's first place in the segment, its in-run mask
       auto fetch = [&](uint32_t k0) {
@@ -785,12 +805,23 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
 #endif
         const bool act = k < total;
         t &= 63u;
+#ifdef VJ_GPSPAN
+        // (four shuffles: the run's bounds travel in one word — both are at most 2048 — and its first word follows from its start)
+        const uint32_t t_excl = (uint32_t)__shfl((int)(incl - nw), (int)t), t_run = (uint32_t)__shfl((int)(a_start | (a_end << 16)), (int)t);
+        const uint32_t t_base = (uint32_t)__shfl((int)a_base, (int)t), t_unit = (uint32_t)__shfl((int)a_seg, (int)t);
+        const uint32_t t_start = t_run & 0xFFFFu, t_end = t_run >> 16, t_first = vh_gplanes_first_word(t_start);
+#else
         const uint32_t t_excl = (uint32_t)__shfl((int)(incl - nw), (int)t), t_first = (uint32_t)__shfl((int)first, (int)t);
         const uint32_t t_base = (uint32_t)__shfl((int)a_base, (int)t), t_start = (uint32_t)__shfl((int)a_start, (int)t), t_end = (uint32_t)__shfl((int)a_end, (int)t);
+#endif
         const uint32_t word = act ? t_first + (k - t_excl) : 0u;
         i_place = t_base + 32u * word;
         i_mask = act ? vh_gplanes_word_mask(word, t_start, t_end) : 0u;
+#ifdef VJ_GPSPAN
+        if (act) J::gp_load(pseg + vh_gspan_word_off(t_unit, word, G), vg);
+#else
         if (act) J::gp_load(pseg + vh_gplanes_off(t_base / VH_GROUP_TILE, word, G), vg);
+#endif
         else {
 #pragma unroll
           for (int z = 0; z < (J::NVG ? J::NVG : 1); ++z) vg[z] = 0u;
@@ -804,12 +835,12 @@ __device__ __forceinline__ void vj_scan(const VhPlanDev& P) {
         vj_push_mask(q, cnt, lane < 32 ? m : 0u, place, h.excl, h.tot_lo);      // (two halves by lanes: at most 1 024 places join the queue between two drains)
         npassed += h.tot_lo + h.tot_hi;
         __builtin_amdgcn_wave_barrier();
-        drain_gp(a_seg, false);
+        drain_gp(d_seg, false);
         vj_push_mask(q, cnt, lane < 32 ? 0u : m, place, h.excl, h.tot_hi);
         __builtin_amdgcn_wave_barrier();
-        drain_gp(a_seg, flush && k0 + 64u >= total);
+        drain_gp(d_seg, flush && k0 + 64u >= total);
       }
-      if (!total && flush) drain_gp(a_seg, true);
+      if (!total && flush) drain_gp(d_seg, true);
       a_n = b_n; a_seg = b_seg; a_base = b_base; a_start = b_start; a_end = b_end;
       if (MODE == VH_MODE_HASH && V.H.dead) a_n = 0u;     // this wave saw the table overflow: the attempt is void (see scan_agg_kernel)
     }

@@ -164,6 +164,7 @@ void QueryBuild::choose_grouped() {
   P.colbase[P.nslots] = gr->planes.ptr; P.colstride[P.nslots] = gr->planes.stride; P.colpitch[P.nslots] = 4u * gr->G;
   js.gp_slot = P.nslots++; js.gp_G = (int)gr->G; js.gp_goff = (int)gr->goff;
   gplanes = true;
+  choose_gpspan();
   // The scan TRIMS its runs (vh_gsub_trim) when the form is sub-sorted, exactly one leaf of the whole program reads its sub column (the rule
   // the grouping column has), that leaf is a relation of the top-level AND a run can be trimmed by, and its literal is a value of the field —
   // otherwise the runs are read whole, which is right for any order inside them. VH_TEST_NO_SUBTRIM=1 reads a sub-sorted form without
@@ -192,6 +193,27 @@ void QueryBuild::choose_grouped() {
   P.colbase[P.nslots] = gr->hdr.ptr + vh_gsub_keys_off(tiles, gbits); P.colstride[P.nslots] = gr->hdr.stride; P.colpitch[P.nslots] = VH_GSUB_KEYS_BYTES;
   js.sub_slot = P.nslots++; js.sub_pred = sp; js.sub_op = (int)g[sp_leaf].op(); js.sub_lit = (int)g[sp_leaf].lit();
   subtrim = true;
+}
+
+// Tile groups that SPAN segments (vh_grouped.h, vh_gspan_*; vj_scan's clustered branch): a wave's group of up to 64 tiles no longer ends at a
+// segment change — with units of 32 768 rows every unit of a block lies in another segment, which made a group four tiles — a queued survivor
+// is its record's table-wide index and the drain pipeline is flushed once per wave. The scan takes the form when the records' and the
+// planes' segment strides divide by 4 and 16 and every index of the scanned segments fits 32 bits (VH_TEST_GPSPAN_BOUND lowers the bound:
+// tests); compile_kernel takes it back for a plan whose survivors read anything but the one 4-byte record the queue indexes (vh_jit_span_ok;
+// choose_grouped's first lines rule that out already), so no reader needs the segment. VH_TEST_NO_GPSPAN=1 keeps the groups inside a segment: an A/B
+// inside one process.
+void QueryBuild::choose_gpspan() {
+  if (const char* e = test_env("VH_TEST_NO_GPSPAN")) if (atoi(e)) return;
+  uint64_t bound = VH_GSPAN_BOUND;
+  if (const char* e = test_env("VH_TEST_GPSPAN_BOUND")) bound = std::min<uint64_t>(bound, strtoull(e, nullptr, 10));
+  uint64_t rec_stride = 0;
+  bool one = true;
+  auto rec_slot = [&](int s) { if (!rec_stride) rec_stride = P.colstride[s]; one &= P.colstride[s] == rec_stride && P.colpitch[s] == 4; };
+  for (int i = 0; i < P.ngroup; ++i) rec_slot((int)P.g[i].slot());
+  for (int j = 0; j < P.nmetric; ++j) rec_slot((int)P.m[j].slot());
+  if (!rec_stride || !one || !vh_gspan_ok(nseg, rec_stride, P.colstride[jshape.gp_slot], bound)) return;
+  jshape.gp_span = 1;
+  gpspan = true;
 }
 
 int vh_jit_drain_depth(const VhJitShape& s) {
@@ -301,6 +323,7 @@ int QueryBuild::compile_kernel() {
       if (!c.rowid && !c.bitset) { c.slot = (int)m.slot(); c.pitch = (int)P.colpitch[m.slot()]; c.rec = slot_rec[m.slot()]; c.off = slot_recoff[m.slot()]; c.stored = slot_stored[m.slot()]; c.bits = slot_bits[m.slot()]; }
     }
     js.drain_depth = vh_jit_drain_depth(js);      // (last: it goes by the columns above)
+    if (js.gp_span && !vh_jit_span_ok(js)) { js.gp_span = 0; gpspan = false; }      // (the spanning queue indexes ONE 4-byte record)
     if (jit_try) {
       std::string jerr;
       // background build mode: a lookup. A shape nobody compiled yet (or that is being compiled) is the worker's: this query is planned for the
@@ -917,7 +940,7 @@ int QueryBuild::launch() {
   if (jk) { narrowed = jshape.pp_nplanes || jshape.pp_sliced; for (int k = 0; k < jshape.npred; ++k) narrowed |= jshape.pred[k].width != vh_elem_size(jshape.pred[k].type); }
   r->hpart = hpart;
   r->info.reserved = (hpart ? 64 : 0) | (fastj || jk ? 1 : 0) | (lanes ? 2 : 0) | (P.lds_hash_slots ? 4 : 0) | (packed ? 8 : 0) | (fastj && narrowed ? 16 : 0) | (jk ? 32 : 0) | (packed && packed_compressed ? 128 : 0) | (hpart && hp_pack ? 256 : 0) | (mode == VH_MODE_DENSE_PART && P.gid_bits ? 1024 : 0) | (jk && (jshape.pp_nplanes || jshape.pp_sliced) ? 2048 : 0) | (jk && jshape.qpay ? 4096 : 0) | (jk && jshape.pp_sliced ? 8192 : 0) | (mode == VH_MODE_DENSE_PART && P.gid_bits && P.tuple4 ? 16384 : 0)
-                   | (has_set ? 1u << 22 : 0) | (has_set && set_search ? 1u << 23 : 0) | (jk && has_set && set_truth && jshape.pp_sliced ? 1u << 25 : 0) | (build_pending ? 1u << 19 : 0) | (jk && grouped ? 1u << 20 : 0) | (jk && grouped && gplanes ? 1u << 21 : 0) | (jk && grouped && gplanes && subtrim ? 1u << 28 : 0) | (packed && packed_bits ? 32768 : 0) | (packed ? (uint32_t)(31 - __builtin_clz(std::max<uint32_t>(packed_rec, 2)) - 1) << 16 : 0);
+                   | (has_set ? 1u << 22 : 0) | (has_set && set_search ? 1u << 23 : 0) | (jk && has_set && set_truth && jshape.pp_sliced ? 1u << 25 : 0) | (build_pending ? 1u << 19 : 0) | (jk && grouped ? 1u << 20 : 0) | (jk && grouped && gplanes ? 1u << 21 : 0) | (jk && grouped && gplanes && subtrim ? 1u << 28 : 0) | (jk && grouped && gplanes && gpspan ? 1u << 29 : 0) | (packed && packed_bits ? 32768 : 0) | (packed ? (uint32_t)(31 - __builtin_clz(std::max<uint32_t>(packed_rec, 2)) - 1) << 16 : 0);
   r->fast_scan = (r->info.reserved & 1u) != 0;
   // the pre-built scan over the bit-sliced planes: bit 26, with the bits of a predicate projection's bit-sliced form (and of the sets' truth tables);
   // no register-resident kernel, no lanes form, no compiled kernel ran

@@ -288,7 +288,9 @@ struct QueryBuild {
   bool grouped = false;                          // the records come from the projection's grouped form (vh_result_info.reserved bit 20)
   bool gplanes = false;                          // ... and the predicate bits from the clustered planes beside them (bit 21)
   bool subtrim = false;                          // ... of a sub-sorted form, every run trimmed to the words that can pass the sub column's leaf (bit 28)
-  void choose_grouped();                         // compile_kernel: point a qualifying plan at the grouped records (building them where the automatic layouts are built)
+  bool gpspan = false;                           // ... whose tile groups span segments, the queue holding table-wide record indexes (bit 29)
+  void choose_gpspan();                          // choose_grouped: the strides divide and the indexes fit 32 bits (vh_gspan_ok)
+  void choose_grouped();                       // compile_kernel: point a qualifying plan at the grouped records (building them where the automatic layouts are built)
   std::vector<int> pp_cols;                      // the filter's columns (ascending) when every leaf reads a fixed-width column: what a predicate projection must hold
   int pp_boff[VJ_MAX_PRED] = {}, pp_bbits[VJ_MAX_PRED] = {}, pp_soff[VJ_MAX_PRED] = {}, pp_sbits[VJ_MAX_PRED] = {};      // predicate column k's bit field in the byte-plane / bit-sliced projection noted in jshape
   void predpack_auto(bool want_sliced);          // counts this query towards an unasked predicate projection of the form it would have used

@@ -112,6 +112,12 @@ class AggResult:
         and 21 are set too): derived from `flags`, like plane_agg."""
         return bool(self.flags & capi.INFO_SUBTRIM)
 
+    @property
+    def gp_spanned(self) -> bool:
+        """The clustered scan filled its tile groups across segment boundaries and queued table-wide record indexes (bit 29; bits 20 and
+        21 are set too): derived from `flags`, like plane_agg."""
+        return bool(self.flags & capi.INFO_GPSPAN)
+
 
 class DeviceTable:
     """vh_table: the HBM mirror of a db::Table's segment store."""
