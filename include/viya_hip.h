@@ -283,7 +283,7 @@ typedef struct vh_result_info {
   int32_t ngroup_cols;
   int32_t nmetrics;
   int32_t has_hidden_count;  /* AVG selected without COUNT (store.cc:126-129)*/
-  float scan_kernel_ms;      /* HIP-event time of the scan/aggregate kernel  */
+  float scan_kernel_ms;      /* HIP-event time of the scan/aggregate kernel; a fused member of a batch (bit 30 below): of the fused launch, the same value for every member of its group */
   float total_ms;            /* HIP-event time launch .. results in host mem */
   uint64_t algorithmic_bytes;/* B_ref of SURVEY §8(d) for this query         */
   uint32_t retries;          /* hash-table regrows                           */
@@ -322,7 +322,9 @@ typedef struct vh_result_info {
                                         column's field, then row) and the scan TRIMMED every run to the words that can pass the leaf, found
                                         through 64 boundary keys per tile (bits 20 and 21 are set too);
                                 bit 29: the scan over the clustered planes filled every wave's group of up to 64 tiles ACROSS segment boundaries
-                                        and queued a survivor as its record's table-wide index (bits 20 and 21 are set too) */
+                                        and queued a survivor as its record's table-wide index (bits 20 and 21 are set too);
+                                bit 30: the result was filled by a FUSED launch of a batch (vh_query_agg_batch: scan_agg_planes_batch_kernel answered
+                                        several members at once; bit 27 and its company are set too, bits 0, 1, 5 and 26 are clear) */
   uint64_t returned_groups;  /* rows vh_result_copy delivers (= ngroups without HAVING) */
 } vh_result_info;
 
@@ -531,6 +533,37 @@ VH_API int vh_segment_stats(vh_table* t, uint32_t seg, int32_t col,
 
 /* The hot path. vh_query_agg = vh_query_launch + vh_result_finalize. */
 VH_API int vh_query_agg(vh_table* t, const vh_plan* plan, vh_result** out);
+
+/* A batch of aggregates over ONE table, answered in one call: what a dashboard fires at once. out[i] is a finalised result that equals what
+ * vh_query_agg(t, plans[i], ..) returns for the same state of the table — rows, ngroups, scanned_recs, scanned_segments, passed_recs and
+ * returned_groups, after HAVING and top-N; every vh_result_* call works on it and vh_result_free frees it. Every result holds an execution
+ * context, as a single result does (VH_MAX_EXEC bounds the results alive at once; a table without a free context answers as for vh_query_agg).
+ * All members are planned and enqueued within ONE hold of the table's lock: they see one state of the table (a plan of more than
+ * VH_MAX_METRIC - 1 metrics is answered behind the others by vh_query_agg's passes, and so is whatever a member's re-plan runs).
+ *
+ * Fusion. A member that would take the aggregate on the bit-sliced planes as a single query (the rule above, "Aggregates on the bit-sliced
+ * planes": it is unchanged, and still opt-in through VH_PLAN2_PLANE_AGG / VH_PLANE_AGG=1) is a candidate. Candidates with the same value
+ * projection V, the same memory scope of their table updates, the same number of snapshot segments and chunks per segment form a group, in
+ * plan order, of at most VH_BATCH_MAX members whose LDS tables together take at most 48 KB; the candidate that would pass either bound opens
+ * the next group. A group of two or more is answered by ONE launch of scan_agg_planes_batch_kernel: one walk over the chunks, one load of V's
+ * plane words, one launch and one wait; each member keeps its own filter (or none), its own projection F, its own snapshot and skipped
+ * segments, and its own LDS table. Such a result has vh_result_info.reserved bit 30 set beside bit 27's, vh_result_kernel names
+ * scan_agg_planes_batch_kernel<256, S>, and its scan_kernel_ms is the FUSED launch's time, the same for every member of the group (so the
+ * members' values must not be added up; vh_batch_info.fused_kernel_ms is the sum over the launches). A group of one, and every member that
+ * is no candidate, runs as the single query it is: the flags and the kernel name its vh_query_agg would give, bit 30 clear. A fused member
+ * that has to be planned again (a value synced in beyond the planned range) is answered alone by vh_query_agg's re-plan loop; the others stand.
+ *
+ * Failure is all-or-nothing: the call returns the first failing member's code, vh_last_error() begins with "plan <i>: ", every result
+ * already made is freed and every out[i] is NULL. n == 0 returns VH_OK; n > VH_BATCH_MAX, a null plan, a null `out` or a null table return
+ * VH_E_INVALID. On a table with a layout budget the whole batch is one use of the layouts it reads: nothing a member reads is evicted for
+ * another member, the budget is restored once before the call returns, and bit 24 is on every result if anything was evicted. */
+#define VH_BATCH_MAX 8
+typedef struct vh_batch_info {
+  uint32_t nplans, fused_groups, fused_members, singles;   /* members in all / fused launches / members they answered / members answered singly */
+  float fused_kernel_ms;     /* HIP-event time of the fused launches, summed */
+  uint32_t reserved;
+} vh_batch_info;
+VH_API int vh_query_agg_batch(vh_table* t, const vh_plan* const* plans, uint32_t n, vh_result** out /* n */, vh_batch_info* info /* may be NULL */);
 /* Launch only: partial aggregate stays in HBM (multi-GPU: reduce, then finalise). */
 VH_API int vh_query_launch(vh_table* t, const vh_plan* plan, vh_result** out);
 VH_API int vh_result_device_buffers(vh_result* r, vh_device_buffer* bufs,

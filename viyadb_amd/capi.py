@@ -151,7 +151,17 @@ INFO_SLICED_PREBUILT = 1 << 26    # ... bit 26: a pre-built scan read the filter
 INFO_PLANE_AGG = 1 << 27          # ... bit 27: the aggregate was computed on the bit-sliced planes (bits 4, 11 and 13 are set too; bits 0, 1, 5 and 26 are clear)
 INFO_SUBTRIM = 1 << 28             # ... bit 28: the clustered planes are a sub-sorted form's and every run was trimmed by the sub column's leaf (bits 20 and 21 are set too)
 INFO_GPSPAN = 1 << 29              # ... bit 29: the clustered scan's tile groups spanned segments, its queue held table-wide record indexes (bits 20 and 21 are set too)
+INFO_BATCH_FUSED = 1 << 30         # ... bit 30: the result was filled by a fused launch of a batch (vh_query_agg_batch; bit 27 and its company are set too)
 INFO_EVICTED = 1 << 24            # ... bit 24: planning this query evicted at least one derived layout (tables with a layout budget)
+
+
+BATCH_MAX = 8                     # VH_BATCH_MAX: members of one vh_query_agg_batch call
+
+
+class BatchInfo(C.Structure):
+    """vh_batch_info: how a batch was answered. fused_kernel_ms is the sum over the fused launches."""
+    _fields_ = [("nplans", C.c_uint32), ("fused_groups", C.c_uint32), ("fused_members", C.c_uint32), ("singles", C.c_uint32),
+                ("fused_kernel_ms", C.c_float), ("reserved", C.c_uint32)]
 
 
 class BuildInfo(C.Structure):
@@ -222,6 +232,7 @@ SYMBOLS = {
     "vh_table_layout_drop": (C.c_int, [_VP, C.c_uint64]),
     "vh_segment_stats": (C.c_int, [_VP, C.c_uint32, C.c_int32, C.POINTER(AnyNum), C.POINTER(AnyNum)]),
     "vh_query_agg": (C.c_int, [_VP, C.POINTER(Plan), C.POINTER(_VP)]),
+    "vh_query_agg_batch": (C.c_int, [_VP, C.POINTER(C.POINTER(Plan)), C.c_uint32, C.POINTER(_VP), C.POINTER(BatchInfo)]),
     "vh_query_launch": (C.c_int, [_VP, C.POINTER(Plan), C.POINTER(_VP)]),
     "vh_result_device_buffers": (C.c_int, [_VP, C.POINTER(DeviceBuffer), C.c_int32, C.POINTER(C.c_int32)]),
     "vh_result_finalize": (C.c_int, [_VP]),

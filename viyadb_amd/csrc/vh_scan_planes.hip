@@ -9,6 +9,7 @@
 #include "vh_sliced.h"
 #include "vh_bits_agg.h"
 #include "vh_wave_scan.h"
+#include "vh_plane_agg.h"
 
 // VhPlanDev by value as for every scan kernel, the two projections' places by value behind it; program and descriptor lie in the plan block
 // and are read through restrict pointers of their own (vh_sliced.h).
@@ -59,32 +60,7 @@ __global__ __launch_bounds__(BLOCK) void scan_agg_planes_kernel(const VhPlanDev 
         if ((need >> p) & 1u) v[p] = VH_BITS_LOAD(planes + (uint64_t)p * V.pitch + woff);
     }
 
-    uint32_t seen = 0u;
-#pragma unroll 1
-    for (uint32_t g = 0; g < G; ++g) {
-      if (__ballot((mask & ~seen) != 0u) == 0ull) break;      // every passing row of the wave's chunk has found its group
-      const uint32_t mg = ((valid >> g) & 1ull) ? (mask & vh_bits_match(v, care, D->pat[g])) : 0u;
-      seen |= mg;
-      if (__ballot(mg != 0u) == 0ull) continue;
-      const bool in = mg != 0u;
-#pragma unroll 1
-      for (int j = 0; j < P.nmetric; ++j) {
-        const VhMetricDev& m = P.m[j];
-        const int sop = (int)m.sop();
-        const uint32_t off = D->moff[j], nb = D->mbits[j];
-        // the lanes' partial results combined by DPP scans (vh_wave_scan.h; all lanes are active here): lane 63 ends up with the wave's. A
-        // field's value is an unsigned number of at most 32 bits, so MAX takes 0 from a lane without a row of g and MIN is the complement
-        // of the MAX of the complements.
-        uint64_t total;
-        bool empty;
-        if (sop == SOP_ADD32 || sop == SOP_ADD64) total = vh_wave_incl_add((unsigned long long)vh_bits_sum_at(v, off, nb, mg));
-        else if (sop == SOP_MIN_I32 || sop == SOP_MIN_U32 || sop == SOP_MIN_I64 || sop == SOP_MIN_U64) total = (uint32_t)~vh_wave_incl_max(in ? ~vh_bits_min_at(v, off, nb, mg, &empty) : 0u);
-        else total = vh_wave_incl_max(in ? vh_bits_max_at(v, off, nb, mg, &empty) : 0u);
-        if (lane == 63) vh_state_update<__HIP_MEMORY_SCOPE_WORKGROUP>(lds + m.lds_off, g, sop, total);
-      }
-      if (lane == 63) reinterpret_cast<uint8_t*>(lds + P.lds_present_off)[g] = 1;
-    }
-    range_err |= (mask & ~seen) != 0u;
+    range_err |= vh_plane_agg_groups(P, D, care, valid, G, lds, v, mask, lane);      // (vh_plane_agg.h: the loop over the group ids, shared with the batch kernel)
   }
 
   if (__ballot(range_err) != 0ull && lane == 0) atomicOr(P.counters + 2, VH_ERR_RANGE);

@@ -1,7 +1,7 @@
 // vh_sliced.h — what the PRE-BUILT readers of the bit-sliced predicate planes share on the device: the kernel arguments that name the planes
 // and carry the filter program (vh_bits_eval.h), and a lane's pass mask for its word of a chunk (vh_sliced_walk.h). Included by the select
 // kernels (vh_small_kernels.h), by the aggregate scan over the planes (vh_scan_sliced.hip) and by the one that also aggregates on them
-// (vh_scan_planes.hip).
+// (vh_scan_planes.hip) and its form for a fused batch (vh_scan_planes_batch.hip).
 #pragma once
 #include "vh_internal.h"
 #include "vh_bits_eval.h"
@@ -48,6 +48,19 @@ struct VhPlaneAggRef {
   const VhBitsProg* B;            // nullptr: no filter
   const VhPlaneAggDesc* D;
   VhSlicedPlanes F, V;
+};
+// One member of a fused batch (vh_scan_planes_batch.hip: scan_agg_planes_batch_kernel): what scan_agg_planes_kernel takes as arguments for one
+// query, without V — the members of a group share it — and with the place of the member's LDS table in the launch's dynamic LDS. An array of
+// them lies in device memory (the plans do not fit the kernel arguments) and is read through a restrict pointer, for the reason given above.
+// Program and descriptor lie IN the member, by value: read through a pointer that was itself loaded from the array, the compiler no longer
+// knows them for unclobbered — it took vector loads and turned every branch of the interpreter, which is on plan data, into a divergent one
+// (952 exec-mask branches against the single kernel's 412; measured 25 % slower than the single queries: profiles/r18/NOTES.md).
+struct VhBatchMember {
+  VhPlanDev P;
+  VhBitsProg B;                   // (all zeros: no filter — D.has_filter says)
+  VhPlaneAggDesc D;
+  VhSlicedPlanes F;
+  uint32_t lds_base, pad;         // bytes, a multiple of 16
 };
 
 #if defined(__HIPCC__)

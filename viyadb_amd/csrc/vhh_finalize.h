@@ -479,20 +479,18 @@ static int query_agg_multipass(vh_table* t, const vh_plan* plan, vh_result** out
 
 static int place_layouts(vh_table* t, const vh_plan* plan, vh_result_info* info_out, double budget_ms);
 static bool placing_now();
-extern "C" int vh_query_agg(vh_table* t, const vh_plan* plan, vh_result** out) {
-  if (!t || !plan || !out) return vh_fail(VH_E_INVALID, "null argument");
-  VH_ENTER();
-  if (plan->nmetrics > VH_MAX_METRIC - 1 && plan->metrics) return query_agg_multipass(t, plan, out);
-  VhExec* x = nullptr;
-  if (int rc = exec_acquire(t, &x, !placing_now())) return rc;      // (a placement's own queries never wait for a context: its caller may hold the last one — no placement then)
+// The attempts of ONE query on context x: plan and launch, finalise, and where the verdict asks for it plan again (replan_after). It takes the
+// context over: the result owns it, or it is released. `first`: an attempt that is launched already and not finalised yet — a member of a
+// batch, whose re-plan is this loop too — in place of the first plan.
+static int query_agg_attempts(vh_table* t, VhExec* x, const vh_plan* plan, vh_result** out, vh_result* first = nullptr) {
   VhReplan rp;
   int rc = VH_OK;
   for (uint32_t attempt = 0; attempt < 12; ++attempt) {
-    vh_result* r = nullptr;
+    vh_result* r = attempt == 0 ? first : nullptr;
     const auto h0 = std::chrono::steady_clock::now();
     // planned and launched under the table lock; the wait for the device and the read-back happen outside it, so
     // queries of other threads on this table run meanwhile (each on its own context)
-    {
+    if (!r) {
       std::lock_guard<std::mutex> lk(t->mu);
       g_heavy.allow_mark = true;        // (this caller can run the second pass over heavy ranges: it holds the plan when the verdict is in)
       VhLaunchOpts o;
@@ -523,6 +521,165 @@ extern "C" int vh_query_agg(vh_table* t, const vh_plan* plan, vh_result** out) {
   (void)hipStreamSynchronize(x->stream());
   exec_release(t, x);
   return rc;
+}
+
+extern "C" int vh_query_agg(vh_table* t, const vh_plan* plan, vh_result** out) {
+  if (!t || !plan || !out) return vh_fail(VH_E_INVALID, "null argument");
+  VH_ENTER();
+  if (plan->nmetrics > VH_MAX_METRIC - 1 && plan->metrics) return query_agg_multipass(t, plan, out);
+  VhExec* x = nullptr;
+  if (int rc = exec_acquire(t, &x, !placing_now())) return rc;      // (a placement's own queries never wait for a context: its caller may hold the last one — no placement then)
+  return query_agg_attempts(t, x, plan, out);
+}
+
+// ------------------------------------------------------------------ a batch of aggregates (include/viya_hip.h, vh_query_agg_batch)
+// The scans the members' plans handed over (QueryBuild::launch), enqueued: vh_batch.h forms the groups; a group's members are answered by ONE
+// launch of scan_agg_planes_batch_kernel on the stream of its first member, the lead; a candidate that stays alone gets the launch its plan
+// would have made. Behind either, each member's own tail on its own stream (query_scan_tail). t->mu is held, and so is the batch's tick.
+struct VhBatchGroups { uint32_t n = 0; int32_t of[VH_BATCH_MAX]; uint32_t lead[VH_BATCH_MAX]; };
+static int batch_launch_scans(VhBatchFuse& F, uint32_t n, VhBatchGroups* G, uint32_t* failed) {
+  VhFuseDesc d[VH_BATCH_MAX] = {};
+  for (uint32_t i = 0; i < n; ++i) {
+    const VhDeferredScan& s = F.scan[i];
+    if (!s.r) continue;
+    d[i].candidate = 1; d[i].scope = s.xcd_private ? 1u : 0u; d[i].v_serial = s.v_serial; d[i].nseg = (uint32_t)s.P.nseg; d[i].chunks_per_seg = s.chunks_per_seg;
+    d[i].lds_bytes = (uint32_t)((s.lds_table + 15) / 16 * 16);
+  }
+  G->n = vh_batch_group(d, n, G->of);
+  for (uint32_t i = 0; i < n; ++i) {      // alone after all: the single query's launch
+    const VhDeferredScan& s = F.scan[i];
+    if (!s.r || G->of[i] >= 0) continue;
+    *failed = i;
+    VhScanLaunch L;
+    L.grid = s.grid; L.lds = s.lds_table; L.stream = s.x->stream();
+    vh_launch_scan_planes(s.P, s.A, s.chunks_per_seg, L, s.xcd_private);
+    if (int rc = query_scan_tail(s.r, s.x)) return rc;
+  }
+  for (uint32_t g = 0; g < G->n; ++g) {
+    uint32_t m[VH_BATCH_MAX], cnt = 0;
+    for (uint32_t i = 0; i < n; ++i) if (G->of[i] == (int32_t)g) m[cnt++] = i;
+    const VhDeferredScan& lead = F.scan[m[0]];
+    G->lead[g] = m[0]; *failed = m[0];
+    VhExec* lx = lead.x;
+    if (int rc = exec_batch(lx)) return rc;
+    hipStream_t ls = lx->stream();
+    uint32_t lds = 0;
+    int grid = 0;
+    for (uint32_t k = 0; k < cnt; ++k) {      // the lead's stream behind every member's clears and uploads; the members' array, staged
+      const VhDeferredScan& s = F.scan[m[k]];
+      if (s.x->stream() != ls) HIP_TRY(hipStreamWaitEvent(ls, s.x->ev[1], 0));
+      VhBatchMember& M = lx->h_batch[k];
+      M.P = s.P; M.B = s.B; M.D = s.D; M.F = s.A.F; M.lds_base = lds; M.pad = 0;
+      lds += d[m[k]].lds_bytes;
+      grid = std::max(grid, s.grid);
+    }
+    HIP_TRY(hipMemcpyAsync(lx->d_batch, lx->h_batch, cnt * sizeof(VhBatchMember), hipMemcpyHostToDevice, ls));
+    HIP_TRY(hipEventRecord(lx->ev_batch[0], ls));
+    char nm[160] = "";
+    VhScanLaunch L;
+    L.name = nm; L.name_cap = sizeof(nm);
+    vh_launch_scan_planes_batch(lx->d_batch, cnt, lead.A.V, lead.chunks_per_seg, L, lead.xcd_private);      // (its name)
+    L = VhScanLaunch{};
+    L.grid = grid; L.lds = lds; L.stream = ls;
+    vh_launch_scan_planes_batch(lx->d_batch, cnt, lead.A.V, lead.chunks_per_seg, L, lead.xcd_private);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(lx->ev_batch[1], ls));
+    for (uint32_t k = 0; k < cnt; ++k) {      // every member's stream behind the launch, then its own tail there
+      const VhDeferredScan& s = F.scan[m[k]];
+      *failed = m[k];
+      if (s.x->stream() != ls) HIP_TRY(hipStreamWaitEvent(s.x->stream(), lx->ev_batch[1], 0));
+      s.r->kernel = nm;
+      s.r->info.reserved |= 1u << 30;
+      if (int rc = query_scan_tail(s.r, s.x)) return rc;
+    }
+  }
+  return VH_OK;
+}
+
+extern "C" int vh_query_agg_batch(vh_table* t, const vh_plan* const* plans, uint32_t n, vh_result** out, vh_batch_info* info) {
+  if (info) *info = vh_batch_info{};
+  if (!t) return vh_fail(VH_E_INVALID, "null argument");
+  if (n > VH_BATCH_MAX) return vh_fail(VH_E_INVALID, "a batch of %u plans (max %d)", n, VH_BATCH_MAX);
+  if (n == 0) return VH_OK;
+  if (!plans || !out) return vh_fail(VH_E_INVALID, "null argument");
+  for (uint32_t i = 0; i < n; ++i) out[i] = nullptr;
+  for (uint32_t i = 0; i < n; ++i) if (!plans[i]) return vh_fail(VH_E_INVALID, "plan %u: null plan", i);
+  if (!g_ctx.inited) return vh_fail(VH_E_INVALID, "vh_init has not been called");
+  VH_ENTER();
+  const char* const nf = test_env("VH_TEST_NO_BATCH_FUSE");      // tests, probe: every member answered singly (an A/B inside one process)
+  const bool no_fuse = nf && atoi(nf) != 0;
+  VhExec* xs[VH_BATCH_MAX] = {};          // a member's context while no result owns it
+  vh_result* rs[VH_BATCH_MAX] = {};       // a member's launched attempt (it owns the context)
+  bool wide[VH_BATCH_MAX] = {};           // more metrics than one pass carries: vh_query_agg's passes, behind the others
+  auto fail = [&](int rc, uint32_t i) {   // all or nothing
+    char msg[sizeof(g_err)];
+    snprintf(msg, sizeof(msg), "%s", g_err);
+    for (uint32_t k = 0; k < n; ++k) {
+      if (out[k]) { delete out[k]; out[k] = nullptr; }
+      if (rs[k]) { delete rs[k]; rs[k] = nullptr; }
+      else if (xs[k]) { (void)hipStreamSynchronize(xs[k]->stream()); exec_release(t, xs[k]); }
+      xs[k] = nullptr;
+    }
+    (void)hipGetLastError();
+    return vh_fail(rc, "plan %u: %.480s", i, msg);
+  };
+  for (uint32_t i = 0; i < n; ++i) {
+    wide[i] = plans[i]->nmetrics > VH_MAX_METRIC - 1 && plans[i]->metrics;
+    if (wide[i]) continue;
+    if (int rc = exec_acquire(t, &xs[i], !placing_now())) { xs[i] = nullptr; return fail(rc, i); }
+  }
+  std::unique_ptr<VhBatchFuse> fuse(new VhBatchFuse());
+  VhBatchGroups G;
+  for (uint32_t i = 0; i < n; ++i) G.of[i] = -1;
+  int rc = VH_OK;
+  uint32_t failed = 0;
+  bool evicted = false;
+  {
+    // every member planned and enqueued within ONE hold of the lock — one state of the table — and under ONE tick (PlanTick, vhh_launch.h):
+    // it ends, and trims a layout budget, behind the last fused launch and before the lock is released
+    std::lock_guard<std::mutex> lk(t->mu);
+    {
+      PlanTick tick(t, nullptr, false);
+      for (uint32_t i = 0; i < n && !rc; ++i) {
+        if (wide[i]) continue;
+        failed = i;
+        fuse->member = i;
+        g_heavy.allow_mark = true;
+        VhLaunchOpts o;
+        o.fuse = no_fuse ? nullptr : fuse.get();
+        rc = query_launch_locked(t, xs[i], plans[i], &rs[i], o);
+        g_heavy = VhHeavyCtx{};
+        if (rc) { rs[i] = nullptr; break; }
+        rs[i]->exec = xs[i];
+      }
+      if (!rc) rc = batch_launch_scans(*fuse, n, &G, &failed);
+    }
+    evicted = t->layout_budget != 0 && g_plan_evicted;
+  }
+  if (rc) return fail(rc, failed);
+  // outside the lock: every member's wait and read-back, and its re-plan where the verdict asks for one, by vh_query_agg's own loop
+  for (uint32_t i = 0; i < n; ++i) {
+    if (wide[i]) rc = query_agg_multipass(t, plans[i], &out[i]);
+    else {
+      vh_result* r = rs[i];
+      rs[i] = nullptr; xs[i] = nullptr;      // (the loop takes context and attempt over)
+      rc = query_agg_attempts(t, r->exec, plans[i], &out[i], r);
+    }
+    if (rc) { out[i] = nullptr; return fail(rc, i); }
+  }
+  vh_batch_info bi{};
+  bi.nplans = n; bi.fused_groups = G.n;
+  for (uint32_t g = 0; g < G.n; ++g) {      // (every member's stream waited for the launch's end: the events have completed)
+    float ms = 0;
+    (void)hipEventElapsedTime(&ms, fuse->scan[G.lead[g]].x->ev_batch[0], fuse->scan[G.lead[g]].x->ev_batch[1]);
+    bi.fused_kernel_ms += ms;
+    for (uint32_t i = 0; i < n; ++i)
+      if (G.of[i] == (int32_t)g && (out[i]->info.reserved & (1u << 30))) { out[i]->info.scan_kernel_ms = ms; ++bi.fused_members; }      // (a member that was planned again is a single query's result)
+  }
+  bi.singles = n - bi.fused_members;
+  if (evicted) for (uint32_t i = 0; i < n; ++i) out[i]->info.reserved |= 1u << 24;
+  if (info) *info = bi;
+  return VH_OK;
 }
 
 // A place for the derived layouts a plan reads (vhh_derived.h, derived_move): up to `prepare_place` other places tried, each measured with three

@@ -835,6 +835,27 @@ int QueryBuild::layout_scratch() {
   return VH_OK;
 }
 
+// What follows a query's scan on its stream: the event behind the scan, whether the result takes the one-launch tail, and the merge of a dense
+// result's private copies where it does not. launch() ends with it; a batch calls it for a member whose scan it launched itself — fused with
+// others', or alone after all (vh_query_agg_batch, vhh_finalize.h).
+static int query_scan_tail(vh_result* r, VhExec* x) {
+  const VhPlanDev& P = r->plan;
+  hipStream_t st = x->stream();
+  HIP_TRY(hipEventRecord(x->ev[2], st));
+  HIP_TRY(hipGetLastError());
+  // a small dense result that will go straight into pinned host memory (result_finalize's `direct`): its whole tail is one launch there
+  // ... bounded by the states that ONE block then reads (entries x private copies x metrics), not by the entries alone: beyond ~64 K of them
+  // the three parallel launches it replaces are the faster tail
+  r->small_tail = r->mode != VH_MODE_HASH && r->out_cap <= VH_SMALL_TAIL_MAX && r->out_region_bytes <= (8u << 20) && !r->topk_active && !r->hp_chunks &&
+                  (uint64_t)r->out_cap * (uint64_t)std::max(1, r->nxcd) * (uint64_t)std::max(1, (int)P.nmetric) <= VH_SMALL_TAIL_STATES &&
+                  !r->device_rows && !knobs().no_direct_emit && !test_env("VH_TEST_NO_SMALL_TAIL");
+  if (r->mode != VH_MODE_HASH && r->nxcd > 1) {
+    r->unmerged = true;
+    if (!r->small_tail) { if (int mrc = merge_copies_now(r, st)) return mrc; }
+  }
+  return VH_OK;
+}
+
 int QueryBuild::launch() {
   int rc = VH_OK;
   // ---------------- init + launch
@@ -973,6 +994,15 @@ int QueryBuild::launch() {
   if (g_heavy.only && !from_tuples && g_heavy.epoch != t->sync_epoch)       // the table has moved on since the first pass: its rows are no longer the rows that pass saw
     return vh_fail(VH_E_RANGE, "second pass over heavy ranges: the table changed since the first pass");      // (heavy_pass_finish gives up; the caller re-plans the whole query)
   if (from_tuples) {
+  } else if (P.total_units && plane_agg && o.fuse) {
+    // A member of a batch whose scan may share a fused launch (vh_query_agg_batch): everything up to ev[1] is enqueued; the scan and what
+    // follows it are the batch's to launch, once it knows the groups. The plan goes by value: it is complete here.
+    VhDeferredScan& d = o.fuse->scan[o.fuse->member];
+    d.r = r; d.x = x; d.P = P; d.A = pagg_ref; d.B = pagg_filter ? planes_prog : VhBitsProg{}; d.D = pagg_desc; d.grid = grid; d.lds_table = lds_table; d.xcd_private = nxcd > 1; d.v_serial = pagg_v->serial;
+    d.chunks_per_seg = (uint32_t)std::max<uint64_t>(1, (t->padded_rows + VH_SLICED_CHUNK_ROWS - 1) / VH_SLICED_CHUNK_ROWS);
+    *out = holder.release();
+    done = true;
+    return VH_OK;
   } else if (P.total_units) {
     scan_dispatch(VhScanLaunch{grid});
     if (hpart) {
@@ -1006,49 +1036,43 @@ int QueryBuild::launch() {
       }
     }
   }
-  HIP_TRY(hipEventRecord(x->ev[2], st));
-  HIP_TRY(hipGetLastError());
-  // a small dense result that will go straight into pinned host memory (result_finalize's `direct`): its whole tail is one launch there
-  // ... bounded by the states that ONE block then reads (entries x private copies x metrics), not by the entries alone: beyond ~64 K of them
-  // the three parallel launches it replaces are the faster tail
-  r->small_tail = mode != VH_MODE_HASH && r->out_cap <= VH_SMALL_TAIL_MAX && r->out_region_bytes <= (8u << 20) && !r->topk_active && !r->hp_chunks &&
-                  (uint64_t)r->out_cap * (uint64_t)std::max(1, nxcd) * (uint64_t)std::max(1, (int)P.nmetric) <= VH_SMALL_TAIL_STATES &&
-                  !o.device_rows && !knobs().no_direct_emit && !test_env("VH_TEST_NO_SMALL_TAIL");
-  if (mode != VH_MODE_HASH && nxcd > 1) {
-    r->unmerged = true;
-    if (!r->small_tail) { if (int mrc = merge_copies_now(r, st)) return mrc; }
-  }
+  if (int trc = query_scan_tail(r, x)) return trc;
   *out = holder.release();
   done = true;
   return VH_OK;
 }
 
+// One tick per query (a plan that starts over keeps it): what the layouts this plan reads are stamped with (layout_use). When the outermost
+// holder ends, a budget that a refresh pushed past — the table grew, a projection was rebuilt wider — is restored at the cost of layouts
+// this plan does not read, and the result says whether anything was evicted on its behalf.
+// A sharded query's summary pass and the heavy second pass of a hashed partitioning are further passes of ONE query: they take a tick of
+// their own (what they hold is safe from their own builds) but count as no use, and what they evict is reported on the query's result.
+// A BATCH (vh_query_agg_batch) holds the outer tick itself, over all its members' plans and its fused launches: every layout any member
+// reads carries the one stamp, so no later member's build and no trim evicts the planes of a scan that is not enqueued yet — table_quiesce
+// would find that member's stream idle and free them under the kernel to come. Its members' own ticks are passive (g_plan_depth); the trim
+// runs once, when the batch's tick ends, still under the table's lock; g_plan_evicted then tells the batch what to report (out == nullptr).
+struct PlanTick {
+  vh_table* t; vh_result** out; bool outer, further, was_unstamped;
+  PlanTick(vh_table* t_, vh_result** out_, bool further_) : t(t_), out(out_), outer(g_plan_depth++ == 0), further(further_), was_unstamped(g_plan_unstamped) {
+    if (!outer) return;
+    ++t->use_tick;
+    g_plan_evicted = g_plan_carry; g_plan_carry = false;
+    g_plan_unstamped = further;
+    if (g_preparing && !further) g_prepare_reads.clear();
+  }
+  ~PlanTick() {
+    --g_plan_depth;
+    if (!outer) return;
+    g_plan_unstamped = was_unstamped;
+    if (!t->layout_budget) return;
+    derived_trim(t, true);
+    if (further) g_plan_carry = g_plan_evicted;
+    else if (g_plan_evicted && out && *out) (*out)->info.reserved |= 1u << 24;
+  }
+};
 static int query_launch_locked(vh_table* t, VhExec* x, const vh_plan* p, vh_result** out, const VhLaunchOpts& o) {
   if (int src = sync_resolve(t)) return src;      // a batched sync may still be on its way: its rows and its share of the stats, before anything is planned
-  // One tick per query (a plan that starts over keeps it): what the layouts this plan reads are stamped with (layout_use). When the outermost
-  // call returns, a budget that a refresh pushed past — the table grew, a projection was rebuilt wider — is restored at the cost of layouts
-  // this plan does not read, and the result says whether anything was evicted on its behalf.
-  // A sharded query's summary pass and the heavy second pass of a hashed partitioning are further passes of ONE query: they take a tick of
-  // their own (what they hold is safe from their own builds) but count as no use, and what they evict is reported on the query's result.
-  struct Tick {
-    vh_table* t; vh_result** out; bool outer, further, was_unstamped;
-    Tick(vh_table* t_, vh_result** out_, bool further_) : t(t_), out(out_), outer(g_plan_depth++ == 0), further(further_), was_unstamped(g_plan_unstamped) {
-      if (!outer) return;
-      ++t->use_tick;
-      g_plan_evicted = g_plan_carry; g_plan_carry = false;
-      g_plan_unstamped = further;
-      if (g_preparing && !further) g_prepare_reads.clear();
-    }
-    ~Tick() {
-      --g_plan_depth;
-      if (!outer) return;
-      g_plan_unstamped = was_unstamped;
-      if (!t->layout_budget) return;
-      derived_trim(t, true);
-      if (further) g_plan_carry = g_plan_evicted;
-      else if (g_plan_evicted && out && *out) (*out)->info.reserved |= 1u << 24;
-    }
-  } tick(t, out, o.summary_out != nullptr || g_heavy.only != nullptr);
+  PlanTick tick(t, out, o.summary_out != nullptr || g_heavy.only != nullptr);
   QueryBuild b(t, x, p, out, o);
   int (QueryBuild::* const steps[])() = {&QueryBuild::shape_filter, &QueryBuild::snapshot_segments, &QueryBuild::shape_groups, &QueryBuild::shape_metrics,
                                          &QueryBuild::choose_organisation, &QueryBuild::plan_hashed_partitioning, &QueryBuild::choose_projection,

@@ -196,6 +196,20 @@ struct VhAgreed {
 };
 // What a failed attempt asks of the next one (replan_after in vhh_finalize.h, merge_summaries in vh_sharded.h) ...
 struct VhReplan { uint64_t cap_override = 0, part_override = 0; bool force_hash = false, no_part = false; uint32_t hp_passes = 0; bool no_hpart = false; };
+// A batch's fuse state (vh_query_agg_batch, vhh_finalize.h). QueryBuild::launch() hands the scan of a member that settled on the aggregate on
+// the planes over to it instead of launching: the plan as the kernel takes it, the kernel's view of program, descriptor and projections, the
+// grid and the LDS table the single launch would have had, and what the fuse key is made of (vh_batch.h).
+struct VhDeferredScan {
+  vh_result* r = nullptr;      // nullptr: this member's scan was launched by its own plan (no candidate), or it has no plan yet
+  VhExec* x = nullptr;
+  VhPlanDev P{};
+  VhPlaneAggRef A{};
+  VhBitsProg B{};             // the program A.B points at, as staged (all zeros: no filter)
+  VhPlaneAggDesc D{};         // ... and the descriptor behind A.D
+  int grid = 0; size_t lds_table = 0;
+  bool xcd_private = false; uint32_t chunks_per_seg = 0; uint64_t v_serial = 0;
+};
+struct VhBatchFuse { VhDeferredScan scan[VH_BATCH_MAX]; uint32_t member = 0; };      // member: the one being planned
 // ... and how query_launch_locked is asked for a plan, beyond table, context and the plan itself: every caller names the members it sets.
 struct VhLaunchOpts {
   VhReplan rp;
@@ -203,6 +217,7 @@ struct VhLaunchOpts {
   VhSummary* summary_out = nullptr;     // a sharded query's first half: report what this rank's planner looks at and stop
   const VhAgreed* ag = nullptr;         // ... and its second: plan with the figures all ranks agreed on
   bool device_rows = false;             // emitted rows must (also) exist in device memory: they are exchanged or gathered next
+  VhBatchFuse* fuse = nullptr;          // a member of vh_query_agg_batch: a scan that may share a fused launch is handed over, not launched
 };
 
 // Heavy ranges of the hashed partitioning (VhPlanDev::heavy_mark / heavy_only), per calling thread: vh_query_agg lets its plans mark heavy ranges

@@ -34,6 +34,12 @@ struct VhExec {
   hipStream_t aux = nullptr, copy = nullptr;
   hipEvent_t ev_fork = nullptr, ev_chunk[VH_HP_CHUNKS] = {};
   unsigned long long* h_chunk = nullptr;        // pinned: rows of chunk c, written by publish_count_kernel
+  // the LEAD context of a fused group of a batch (vh_query_agg_batch): the members' array as scan_agg_planes_batch_kernel reads it, staged in
+  // pinned memory and copied to the device on this context's stream, and the events around the fused launch; created on first use (exec_batch).
+  // Not in `scratch`, which ensure_scratch may move, and not per table: two threads may run batches on one table at once, and the kernel
+  // runs after the table's lock is released.
+  VhBatchMember* h_batch = nullptr; VhBatchMember* d_batch = nullptr;
+  hipEvent_t ev_batch[2] = {nullptr, nullptr};
   bool busy = false;
   // an externally owned stream (vh_set_stream) carries all work; otherwise every context has its own
   hipStream_t stream() const { return g_ctx.stream != g_ctx.own_stream ? g_ctx.stream : own_stream; }
@@ -297,6 +303,9 @@ static void exec_free(VhExec* x) {
   if (x->h_chunk) (void)hipHostFree(x->h_chunk);
   if (x->aux) (void)hipStreamDestroy(x->aux);
   if (x->copy) (void)hipStreamDestroy(x->copy);
+  if (x->h_batch) (void)hipHostFree(x->h_batch);
+  if (x->d_batch) (void)hipFree(x->d_batch);
+  for (auto& e : x->ev_batch) if (e) (void)hipEventDestroy(e);
   if (x->own_stream) (void)hipStreamDestroy(x->own_stream);
 }
 // A free context of the table's pool, a new one while the pool may grow, else wait for one to come back.
@@ -330,6 +339,13 @@ static int exec_streaming(VhExec* x) {       // what a streamed result needs on 
   HIP_TRY(hipEventCreateWithFlags(&x->ev_fork, hipEventDisableTiming));
   for (auto& e : x->ev_chunk) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
   HIP_TRY(hipHostMalloc((void**)&x->h_chunk, VH_HP_CHUNKS * sizeof(unsigned long long), hipHostMallocCoherent));
+  return VH_OK;
+}
+static int exec_batch(VhExec* x) {           // what the lead context of a fused group needs on top of a context's stream; once per context
+  if (x->ev_batch[1]) return VH_OK;
+  if (!x->h_batch) HIP_TRY(hipHostMalloc((void**)&x->h_batch, VH_BATCH_MAX * sizeof(VhBatchMember), hipHostMallocDefault));
+  if (!x->d_batch) HIP_TRY(hipMalloc((void**)&x->d_batch, VH_BATCH_MAX * sizeof(VhBatchMember)));
+  for (auto& e : x->ev_batch) if (!e) HIP_TRY(hipEventCreate(&e));
   return VH_OK;
 }
 static void exec_release(vh_table* t, VhExec* x) {

@@ -13,6 +13,7 @@
 #include "vh_launch.h"
 #include "vh_jit.h"
 #include "vh_hpart.h"
+#include "vh_batch.h"
 
 #include <sched.h>
 #include <algorithm>

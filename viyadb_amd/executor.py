@@ -107,6 +107,12 @@ class AggResult:
         return bool(self.flags & capi.INFO_PLANE_AGG)
 
     @property
+    def batch_fused(self) -> bool:
+        """The result was filled by a fused launch of a batch (query_agg_batch; bit 30, bit 27 and its company are set too): derived from
+        `flags`, like plane_agg."""
+        return bool(self.flags & capi.INFO_BATCH_FUSED)
+
+    @property
     def sub_trimmed(self) -> bool:
         """The grouped form is sub-sorted and the scan trimmed every run to the words that can pass the sub column's leaf (bit 28; bits 20
         and 21 are set too): derived from `flags`, like plane_agg."""
@@ -449,6 +455,23 @@ class DeviceTable:
             return self._collect(res, plan, copy)
         finally:
             self.lib.vh_result_free(res)
+
+    def query_agg_batch(self, plans: Sequence[AggPlan], copy: bool = True) -> Tuple[List[AggResult], capi.BatchInfo]:
+        """Up to capi.BATCH_MAX aggregates in one call (vh_query_agg_batch): results in plan order, each equal to query_agg's of the same
+        plan, and how the batch was answered. Members that take the aggregate on the bit-sliced planes share fused launches
+        (AggResult.batch_fused). All or nothing: a failing member fails the call."""
+        n = len(plans)
+        built = [self._build_plan(p) for p in plans]
+        ptrs = (C.POINTER(capi.Plan) * max(1, n))(*[C.pointer(b[0]) for b in built])
+        res = (C.c_void_p * max(1, n))()
+        info = capi.BatchInfo()
+        capi.check(self.lib.vh_query_agg_batch(self.handle, ptrs, n, res, C.byref(info)))
+        try:
+            return [self._collect(C.c_void_p(res[i]), plans[i], copy) for i in range(n)], info
+        finally:
+            for i in range(n):
+                if res[i]:
+                    self.lib.vh_result_free(C.c_void_p(res[i]))
 
     # ---- select: the passing rows themselves, in storage order, through the reference's skip/limit window
     def query_select(self, filter: Sequence, cols: Sequence[int], skip: int = 0, limit: int = 0,
