@@ -810,6 +810,30 @@ VH_API int vh_result_get_info(vh_result* r, vh_result_info* info);
 /* Symbol(s) of the scan kernel(s) this query launched, spelled as rocprofv3 prints them ("scan_agg_fast_kernel<4, 256, 4, 3> +
  * part_agg_kernel<1024>"): what a profile of the same command must show. Valid until vh_result_free. */
 VH_API const char* vh_result_kernel(vh_result* r);
+/* Which kernels ended the query (test support: the tail is chosen by sizes a caller cannot see). Filled when the result is finalised, readable
+ * until vh_result_free; all zero for a result that is not finalised or was joined from several passes. */
+enum vh_tail_kind {
+  VH_TAIL_NONE = 0,       /* the aggregation kernel wrote the rows itself (hashed partitioning without HAVING / top-N) */
+  VH_TAIL_FUSED = 1,      /* small_tail_kernel: private copies, emission and header in one launch                     */
+  VH_TAIL_EMIT2 = 2,      /* emit_groups_kernel<2>                                                                    */
+  VH_TAIL_EMIT16 = 3      /* emit_groups_kernel<16>                                                                   */
+};
+enum vh_tail_merge {
+  VH_MERGE_NONE = 0,      /* one table, or every group lives in one copy by construction: nothing was added up        */
+  VH_MERGE_KERNEL = 1,    /* dense_merge_kernel added the private copies                                              */
+  VH_MERGE_FUSED = 2      /* the fused tail added them                                                                */
+};
+typedef struct vh_tail_info {
+  int32_t kind;               /* enum vh_tail_kind                                                                    */
+  int32_t direct;             /* 1: rows and header were written into pinned host memory by the kernels               */
+  int32_t merged;             /* enum vh_tail_merge                                                                   */
+  int32_t copies;             /* private copies of a dense table (1: a single table)                                  */
+  uint64_t entries;           /* table entries the emission walks (dense: G; hash: capacity + 1)                      */
+  uint32_t states_per_entry;  /* metric states per entry, a hidden count included                                     */
+  uint32_t reserved;
+  uint64_t region_bytes;      /* header + output columns as laid out for `entries` rows                               */
+} vh_tail_info;
+VH_API int vh_result_tail(vh_result* r, vh_tail_info* out);
 /* Element type (enum vh_elem) of the state column vh_result_view / vh_result_copy deliver for metric j of the plan: the metric column's own type;
  * VH_U64 for a count distinct and for the virtual row id — VH_U32 for a count distinct over 32-bit ids when the plan carried VH_PLAN_CARD32. < 0: no such metric. */
 VH_API int vh_result_state_elem(vh_result* r, int32_t metric);

@@ -882,20 +882,22 @@ def decode_value(table: Table, col: Column, value: str):
 _CMP = {"eq": np.equal, "ne": np.not_equal, "lt": np.less, "le": np.less_equal, "gt": np.greater, "ge": np.greater_equal}
 
 
-def eval_filter(table: Table, f, getcol) -> np.ndarray:
+def eval_filter(table: Table, f, getcol, decode=None) -> np.ndarray:
     """ComparisonBuilder (filter.cc:206-261): comparisons in the column's own type,
     composites bitwise & / | without short circuit. `getcol(col)` returns the array the
-    predicate sees (bitset metrics: cardinalities)."""
+    predicate sees (bitset metrics: cardinalities). `decode(table, col, value)`: how a literal is
+    decoded (default: decode_value, the reference's ValueDecoder)."""
+    decode = decode or decode_value
     if isinstance(f, Empty):
         return None  # "true"
     if isinstance(f, Rel):
         col = table.column(f.column)
-        lit = decode_value(table, col, f.value)
+        lit = decode(table, col, f.value)
         return _CMP[f.op](getcol(col), lit)
     if isinstance(f, In):
         col = table.column(f.column)
         arr = getcol(col)
-        lits = [decode_value(table, col, v) for v in f.values]
+        lits = [decode(table, col, v) for v in f.values]
         if f.equal:
             r = np.zeros(len(arr), dtype=bool)
             for l in lits:
@@ -907,7 +909,7 @@ def eval_filter(table: Table, f, getcol) -> np.ndarray:
         if not lits:
             raise Unsupported("IN with no values generates '()' in the reference")
         return r
-    parts = [eval_filter(table, c, getcol) for c in f.filters]
+    parts = [eval_filter(table, c, getcol, decode) for c in f.filters]
     r = None
     for p in parts:
         if p is None:

@@ -383,7 +383,7 @@ def test_rollup_rules_at_query_time(micro):
 @pytest.mark.parametrize("flags", [0, 1, 64, 1 | (1 << 18) | (1 << 20)])      # (the last: hashed partitioning where the plan allows it — its groups then go through the list of records, not straight into the output columns)
 def test_having_on_device(typed, flags):
     """HAVING evaluated by the group-emission kernel. Keys, SUM, AVG (raw sum), MIN/MAX, IN, nested and/or."""
-    from tests.planner import capi_anynum
+    from tests.having import apply_keep, having_nodes, keep_mask
     tab, dt = typed
     cases = [
         ({"dimensions": ["s8", "flag"], "metrics": ["count", "long_sum", "double_max", "int_avg"]},
@@ -398,31 +398,11 @@ def test_having_on_device(typed, flags):
         aq = vo.parse_query(tab, q)
         st = vo.scan_aggregate(aq, now=NOW)
         total = st.ngroups
-        # oracle side: the same ComparisonBuilder semantics on the aggregated tuples (post_agg.cc:77-83)
-        cols = {oc.col.name: st.keys[k] for k, oc in enumerate(aq.dim_cols)}
-        cols.update({oc.col.name: st.states[k] for k, oc in enumerate(aq.metric_cols)})
-        keep = vo.eval_filter(tab, aq.having, lambda c: cols[c.name])
-        st.keys = [k[keep] for k in st.keys]
-        st.states = [s[keep] for s in st.states]
-        if st.hidden_count is not None:
-            st.hidden_count = st.hidden_count[keep]
+        # oracle side: the same ComparisonBuilder semantics on the aggregated tuples (post_agg.cc:77-83) — tests/having.py
+        keep = keep_mask(tab, aq, st)
+        apply_keep(st, keep)
         plan = plan_from_query(tab, aq, now=NOW, flags=flags)
-        names = [oc.col.name for oc in aq.dim_cols] + [oc.col.name for oc in aq.metric_cols]
-        nodes = []
-
-        def walk(f):
-            if isinstance(f, vo.Rel):
-                c = tab.column(f.column)
-                nodes.append(("rel", names.index(f.column), {"eq": 0, "ne": 1, "lt": 2, "le": 3, "gt": 4, "ge": 5}[f.op], capi_anynum(c, vo.decode_value(tab, c, f.value))))
-            elif isinstance(f, vo.In):
-                c = tab.column(f.column)
-                nodes.append(("in", names.index(f.column), f.equal, [capi_anynum(c, vo.decode_value(tab, c, v)) for v in f.values]))
-            else:
-                for ch in f.filters:
-                    walk(ch)
-                nodes.append((f.op, len(f.filters)))
-        walk(aq.having)
-        plan.having = nodes
+        plan.having = having_nodes(tab, aq)
         res = dt.query_agg(plan)
         assert res.ngroups == total and res.returned == int(keep.sum()), (q, res.ngroups, total, res.returned, int(keep.sum()))
         res.ngroups = res.returned

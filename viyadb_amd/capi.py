@@ -86,6 +86,17 @@ class ResultInfo(C.Structure):
                 ("reserved", C.c_uint32), ("returned_groups", C.c_uint64)]
 
 
+TAIL_NONE, TAIL_FUSED, TAIL_EMIT2, TAIL_EMIT16 = range(4)      # enum vh_tail_kind
+TAIL_KIND_NAMES = ["none", "fused", "emit2", "emit16"]
+MERGE_NONE, MERGE_KERNEL, MERGE_FUSED = range(3)                # enum vh_tail_merge
+
+
+class TailInfo(C.Structure):
+    """vh_tail_info: which kernels ended the query (vh_result_tail)."""
+    _fields_ = [("kind", C.c_int32), ("direct", C.c_int32), ("merged", C.c_int32), ("copies", C.c_int32),
+                ("entries", C.c_uint64), ("states_per_entry", C.c_uint32), ("reserved", C.c_uint32), ("region_bytes", C.c_uint64)]
+
+
 class SelectPlan(C.Structure):
     _fields_ = [("filter", C.POINTER(FilterNode)), ("nfilter", C.c_int32),
                 ("lits", C.POINTER(AnyNum)), ("nlits", C.c_int32),
@@ -258,6 +269,7 @@ SYMBOLS = {
     "vh_table_build_wait": (C.c_int, [_VP, C.c_uint32, C.POINTER(BuildInfo)]),
     "vh_table_build_info": (C.c_int, [_VP, C.POINTER(BuildInfo)]),
     "vh_result_kernel": (C.c_char_p, [_VP]),
+    "vh_result_tail": (C.c_int, [_VP, C.POINTER(TailInfo)]),
     "vh_result_state_elem": (C.c_int, [_VP, C.c_int32]),
     "vh_result_copy": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(C.c_uint64)]),
     "vh_result_view": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(C.POINTER(C.c_uint64))]),

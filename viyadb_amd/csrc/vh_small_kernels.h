@@ -3,6 +3,7 @@
 #pragma once
 #include "vh_kernels.h"
 #include "vh_topk_key.h"
+#include "vh_having.h"
 #include "vhh_layout_math.h"
 #include "vh_bits_eval.h"
 #include "vh_sliced.h"
@@ -98,27 +99,6 @@ struct VhEmitArgs {
   uint64_t hlits[VH_MAX_HAVING_LITS];
 };
 
-__device__ __forceinline__ bool vh_cmp_bits(int type, uint64_t a, uint64_t b, int op) {
-  int r;  // -1 / 0 / +1 / 2 (unordered)
-#define VH_C(T) { const T x = vh_lit<T>(a), y = vh_lit<T>(b); r = x < y ? -1 : (x > y ? 1 : (x == y ? 0 : 2)); }
-  switch (type) {
-    case VH_U8: VH_C(uint8_t) break;   case VH_U16: VH_C(uint16_t) break;
-    case VH_U32: VH_C(uint32_t) break; case VH_U64: VH_C(uint64_t) break;
-    case VH_I8: VH_C(int8_t) break;    case VH_I16: VH_C(int16_t) break;
-    case VH_I32: VH_C(int32_t) break;  case VH_I64: VH_C(int64_t) break;
-    case VH_F32: VH_C(float) break;    default: VH_C(double) break;
-  }
-#undef VH_C
-  switch (op) {
-    case VH_OP_EQ: return r == 0;
-    case VH_OP_NE: return r != 0;
-    case VH_OP_LT: return r == -1;
-    case VH_OP_LE: return r == -1 || r == 0;
-    case VH_OP_GT: return r == 1;
-    default: return r == 1 || r == 0;
-  }
-}
-
 __device__ __forceinline__ void vh_store_elem(void* base, int type, uint64_t idx, uint64_t bits) {
   switch (type) {
     case VH_U8: case VH_I8: reinterpret_cast<uint8_t*>(base)[idx] = (uint8_t)bits; break;
@@ -161,32 +141,9 @@ __device__ __forceinline__ bool vh_emit_have(const VhEmitArgs& A, uint64_t i, bo
     }
   }
   present = have;
-  if (have && A.nhaving) {   // postfix, bitwise & / | like the filter
-    bool st[VH_MAX_STACK];
-    int sp = 0;
-    for (int pc = 0; pc < A.nhaving; ++pc) {
-      const VhProgOp o = A.hprog[pc];
-      if (o.kind() == VH_F_TRUE) st[sp++] = true;
-      else if (o.kind() == VH_F_AND || o.kind() == VH_F_OR) {
-        bool a = st[--sp];
-        for (int k = 1; k < o.count(); ++k) { const bool b = st[--sp]; a = o.kind() == VH_F_AND ? (a & b) : (a | b); }
-        st[sp++] = a;
-      } else {
-        const uint64_t v = o.slot() < A.ngroup ? vh_emit_key(A, i, o.slot()) : vh_emit_state(A, i, o.slot() - A.ngroup);
-        bool r;
-        if (o.kind() == VH_F_REL) r = vh_cmp_bits(A.htype[pc], v, A.hlits[o.lit()], o.op());
-        else {
-          r = !o.op();
-          for (int k = 0; k < o.count(); ++k) {
-            const bool e = vh_cmp_bits(A.htype[pc], v, A.hlits[o.lit() + k], o.op() ? VH_OP_EQ : VH_OP_NE);
-            r = o.op() ? (r | e) : (r & e);
-          }
-        }
-        st[sp++] = r;
-      }
-    }
-    have = st[0];
-  }
+  if (have && A.nhaving)      // the postfix program over this entry's key columns and raw states (vh_having.h)
+    have = vh_having_eval(A.hprog, A.nhaving, A.htype, A.hlits,
+                          [&](int c) { return c < A.ngroup ? vh_emit_key(A, i, c) : vh_emit_state(A, i, c - A.ngroup); });
   return have;
 }
 

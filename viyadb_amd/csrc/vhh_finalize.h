@@ -126,10 +126,14 @@ static int result_finalize(vh_result* r, int* retry, const vh_plan* plan) {
     hipLaunchKernelGGL(small_tail_kernel, dim3(1), dim3(1024), 0, st, M, A, reinterpret_cast<unsigned long long*>(x->h_out[slot]),
                        reinterpret_cast<const unsigned long long*>(x->scratch + r->out_region_off));
     r->unmerged = false;
+    r->tail.kind = VH_TAIL_FUSED;
+    if (M.nxcd > 1) r->tail.merged = VH_MERGE_FUSED;
   }
-  else if (r->hp_direct && r->nhaving == 0 && !r->topk_active) { /* hp_aggregate_kernel wrote the output columns and counted the rows */ }
-  else if (A.n <= (4u << 20)) hipLaunchKernelGGL(emit_groups_kernel<2>, dim3((unsigned)((A.n + 256 * 2 - 1) / (256 * 2))), dim3(256), 0, st, A);
-  else hipLaunchKernelGGL(emit_groups_kernel<16>, dim3((unsigned)((A.n + 256 * 16 - 1) / (256 * 16))), dim3(256), 0, st, A);
+  else if (r->hp_direct && r->nhaving == 0 && !r->topk_active) { r->tail.kind = VH_TAIL_NONE; /* hp_aggregate_kernel wrote the output columns and counted the rows */ }
+  else if (A.n <= (4u << 20)) { r->tail.kind = VH_TAIL_EMIT2; hipLaunchKernelGGL(emit_groups_kernel<2>, dim3((unsigned)((A.n + 256 * 2 - 1) / (256 * 2))), dim3(256), 0, st, A); }
+  else { r->tail.kind = VH_TAIL_EMIT16; hipLaunchKernelGGL(emit_groups_kernel<16>, dim3((unsigned)((A.n + 256 * 16 - 1) / (256 * 16))), dim3(256), 0, st, A); }
+  r->tail.direct = direct ? 1 : 0; r->tail.copies = std::max(1, r->nxcd); r->tail.entries = r->out_cap;
+  r->tail.states_per_entry = (uint32_t)P.nmetric; r->tail.region_bytes = r->out_region_bytes;
   HIP_TRY(hipGetLastError());
   if (r->topk_active) {
     // radix select of the top_k-th best sort key among the emitted rows (8 x 8 bits, no host round trip), then keep

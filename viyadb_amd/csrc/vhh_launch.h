@@ -16,6 +16,7 @@ static int merge_copies_now(vh_result* r, hipStream_t st) {
   hipLaunchKernelGGL(dense_merge_kernel, dim3((unsigned)((r->plan.G + 255) / 256)), dim3(256), 0, st, A);
   HIP_TRY(hipGetLastError());
   r->unmerged = false;
+  r->tail.merged = VH_MERGE_KERNEL;
   return VH_OK;
 }
 

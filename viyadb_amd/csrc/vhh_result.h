@@ -113,6 +113,7 @@ struct vh_result {
   int nxcd = 1;
   bool small_tail = false;             // a small dense result that goes straight into pinned host memory: merge + emission + header are ONE launch (small_tail_kernel)
   bool unmerged = false;               // ... which also adds the private copies up: until then (or until merge_copies_now, in front of a cross-GPU reduce) nobody has
+  vh_tail_info tail{};                 // which kernels ended the query (vh_result_tail): filled by result_finalize, `merged` by whoever adds the copies up
   std::vector<int> metric_elem;        // output element type per device metric (P.m order)
   std::vector<int> group_elem;
   std::string group_sig;
@@ -165,6 +166,12 @@ extern "C" int vh_result_get_info(vh_result* r, vh_result_info* info) {
 }
 
 extern "C" const char* vh_result_kernel(vh_result* r) { return r ? r->kernel.c_str() : ""; }
+
+extern "C" int vh_result_tail(vh_result* r, vh_tail_info* out) {
+  if (!r || !out) return vh_fail(VH_E_INVALID, "null argument");
+  *out = r->tail;
+  return VH_OK;
+}
 
 extern "C" int vh_result_state_elem(vh_result* r, int32_t metric) {
   if (!r || metric < 0 || (size_t)metric >= r->user_metric.size()) return -1;

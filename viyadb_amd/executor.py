@@ -102,6 +102,12 @@ class AggResult:
     sliced_prebuilt: bool = False  # a pre-built scan read the filter off the bit-sliced predicate planes (PLAN_SLICED_PREBUILT / VH_SLICED_PREBUILT=1)
 
     @property
+    def tail(self):
+        """capi.TailInfo: which kernels ended the query (vh_result_tail) — kind, direct, merged, copies, entries, states_per_entry,
+        region_bytes. Set by _collect; no field of its own (None for a record built by hand)."""
+        return getattr(self, "_tail", None)
+
+    @property
     def plane_agg(self) -> bool:
         """The aggregate was computed on the bit-sliced planes (PLAN2_PLANE_AGG / VH_PLANE_AGG=1): derived from `flags`, no field of its own."""
         return bool(self.flags & capi.INFO_PLANE_AGG)
@@ -435,17 +441,21 @@ class DeviceTable:
 
         states = [view(spp[j], state_elem(j)) for j in range(len(plan.metrics))]
         hidden = view(C.cast(hp, C.c_void_p).value, np.uint64) if info.has_hidden_count else None
-        return AggResult(keys, states, hidden, int(info.ngroups), int(info.scanned_recs), int(info.scanned_segments),
-                         int(info.passed_recs), capi.PATH_NAMES[info.path], float(info.scan_kernel_ms),
-                         float(info.total_ms), int(info.algorithmic_bytes), int(info.retries), bool(info.reserved & 1),
-                         bool(info.reserved & 2), bool(info.reserved & 8), int(ng), (self.lib.vh_result_kernel(res) or b"").decode(),
-                         bool(info.reserved & 16), bool(info.reserved & 32), bool(info.reserved & 64), bool(info.reserved & 128), bool(info.reserved & 256),
-                         bool(info.reserved & 2048), bool(info.reserved & 8192), bool(info.reserved & 4096), int(info.reserved),
-                         bool(info.reserved & 16384), bool(info.reserved & 32768),
-                         (2 << ((info.reserved >> 16) & 7)) if info.reserved & 8 else 0,
-                         bool(info.reserved & capi.INFO_GROUPED_PAYLOAD), bool(info.reserved & capi.INFO_GROUPED_PLANES),
-                         bool(info.reserved & capi.INFO_INSET), bool(info.reserved & capi.INFO_INSET_SEARCH),
-                         bool(info.reserved & capi.INFO_INSET_SLICED), bool(info.reserved & capi.INFO_SLICED_PREBUILT))
+        tail = capi.TailInfo()
+        capi.check(self.lib.vh_result_tail(res, C.byref(tail)))
+        out = AggResult(keys, states, hidden, int(info.ngroups), int(info.scanned_recs), int(info.scanned_segments),
+                        int(info.passed_recs), capi.PATH_NAMES[info.path], float(info.scan_kernel_ms),
+                        float(info.total_ms), int(info.algorithmic_bytes), int(info.retries), bool(info.reserved & 1),
+                        bool(info.reserved & 2), bool(info.reserved & 8), int(ng), (self.lib.vh_result_kernel(res) or b"").decode(),
+                        bool(info.reserved & 16), bool(info.reserved & 32), bool(info.reserved & 64), bool(info.reserved & 128), bool(info.reserved & 256),
+                        bool(info.reserved & 2048), bool(info.reserved & 8192), bool(info.reserved & 4096), int(info.reserved),
+                        bool(info.reserved & 16384), bool(info.reserved & 32768),
+                        (2 << ((info.reserved >> 16) & 7)) if info.reserved & 8 else 0,
+                        bool(info.reserved & capi.INFO_GROUPED_PAYLOAD), bool(info.reserved & capi.INFO_GROUPED_PLANES),
+                        bool(info.reserved & capi.INFO_INSET), bool(info.reserved & capi.INFO_INSET_SEARCH),
+                        bool(info.reserved & capi.INFO_INSET_SLICED), bool(info.reserved & capi.INFO_SLICED_PREBUILT))
+        out._tail = tail
+        return out
 
     def query_agg(self, plan: AggPlan, copy: bool = True) -> AggResult:
         p, keep = self._build_plan(plan)
