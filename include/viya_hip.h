@@ -274,6 +274,21 @@ typedef struct vh_result vh_result;
 enum vh_path { VH_PATH_SCALAR = 0, VH_PATH_DENSE_LDS = 1, VH_PATH_DENSE_GLOBAL = 2,
                VH_PATH_HASH = 3, VH_PATH_DENSE_PART = 4 };
 
+/* What ran, one name per bit of vh_result_info.reserved (each bit's meaning is told at the field below). The values are ABI. */
+enum vh_info_bits {
+  VH_INFO_FAST = 1u << 0, VH_INFO_LANES = 1u << 1, VH_INFO_LDS_HASH = 1u << 2, VH_INFO_PACKED = 1u << 3,
+  VH_INFO_NARROW = 1u << 4, VH_INFO_JIT = 1u << 5, VH_INFO_HPART = 1u << 6, VH_INFO_PACKED_COMPRESSED = 1u << 7,
+  VH_INFO_HP_PACKED = 1u << 8, /* (bit 9 is never set) */ VH_INFO_TUPLE1 = 1u << 10, VH_INFO_PREDPACK = 1u << 11,
+  VH_INFO_STREAMED_PAYLOAD = 1u << 12, VH_INFO_SLICED = 1u << 13, VH_INFO_TUPLE4 = 1u << 14, VH_INFO_PACK_BITS = 1u << 15,
+  VH_INFO_REC_SHIFT = 16, VH_INFO_REC_MASK = 7u << 16,      /* bits 16-18: a number, not a flag */
+  VH_INFO_BUILD_PENDING = 1u << 19, VH_INFO_GROUPED_PAYLOAD = 1u << 20, VH_INFO_GROUPED_PLANES = 1u << 21, VH_INFO_INSET = 1u << 22,
+  VH_INFO_INSET_SEARCH = 1u << 23, VH_INFO_EVICTED = 1u << 24, VH_INFO_INSET_SLICED = 1u << 25, VH_INFO_SLICED_PREBUILT = 1u << 26,
+  VH_INFO_PLANE_AGG = 1u << 27, VH_INFO_SUBTRIM = 1u << 28, VH_INFO_GPSPAN = 1u << 29, VH_INFO_BATCH_FUSED = 1u << 30,
+  /* what the code asks for together: the filter was read off the bit-sliced planes; everything that describes a payload projection */
+  VH_INFO_ON_PLANES = VH_INFO_NARROW | VH_INFO_PREDPACK | VH_INFO_SLICED,
+  VH_INFO_PROJECTION = VH_INFO_PACKED | VH_INFO_PACKED_COMPRESSED | VH_INFO_PACK_BITS | VH_INFO_REC_MASK
+};
+
 typedef struct vh_result_info {
   uint64_t ngroups;          /* agg_map.size()  -> stats.aggregated_recs     */
   uint64_t scanned_recs;     /* scan.cc:44 — every segment, skipped or not   */
@@ -287,43 +302,46 @@ typedef struct vh_result_info {
   float total_ms;            /* HIP-event time launch .. results in host mem */
   uint64_t algorithmic_bytes;/* B_ref of SURVEY §8(d) for this query         */
   uint32_t retries;          /* hash-table regrows                           */
-  uint32_t reserved;         /* bit 0: the register-resident fast scan kernel ran; bit 1: its no-compaction "lanes" variant;
-                                bit 2: LDS front table of the hash path; bit 3: payload gathered from a projection (vh_table_pack);
-                                bit 4: predicate columns streamed from narrow copies (vh_table_narrow);
-                                bit 5: a scan kernel compiled for this plan shape ran (vh_jit.hip);
-                                bit 6: hashed partitioning of the hash path (vh_hpart.h);
-                                bit 7: the projection's records are compressed (integers at the width their values need);
-                                bit 8: the hashed partitioning's tuples were packed (16 bytes: payload, two ids and their count in one word);
+  uint32_t reserved;         /* enum vh_info_bits above.
+                                bit 0: VH_INFO_FAST — the register-resident fast scan kernel ran;
+                                bit 1: VH_INFO_LANES — its no-compaction "lanes" variant;
+                                bit 2: VH_INFO_LDS_HASH — LDS front table of the hash path;
+                                bit 3: VH_INFO_PACKED — payload gathered from a projection (vh_table_pack);
+                                bit 4: VH_INFO_NARROW — predicate columns streamed from narrow copies (vh_table_narrow);
+                                bit 5: VH_INFO_JIT — a scan kernel compiled for this plan shape ran (vh_jit.hip);
+                                bit 6: VH_INFO_HPART — hashed partitioning of the hash path (vh_hpart.h);
+                                bit 7: VH_INFO_PACKED_COMPRESSED — the projection's records are compressed (integers at the width their values need);
+                                bit 8: VH_INFO_HP_PACKED — the hashed partitioning's tuples were packed (16 bytes: payload, two ids and their count in one word);
                                 bit 9: (rounds 3-5: a tuple pool placed by measurement; the search is gone, the bit is never set);
-                                bit 10: DENSE_PART wrote one-word tuples (gid and values packed into 8 bytes);
-                                bit 11: predicate columns streamed as byte planes of a bit-packed predicate projection (vh_table_predpack; bit 4 is set too);
-                                bit 13: ... of its BIT-SLICED form (comparisons bit-serial on 32 rows per lane);
-                                bit 12: the payload was STREAMED — 4-byte bit-field records beside the predicate columns, a survivor's record queued in its
-                                        row's place — not gathered (bits 3 and 7 are set too);
-                                bit 14: DENSE_PART's one-word tuples were FOUR bytes (bit 10 is set too);
-                                bit 15: the projection's records are bit fields (bits 3 and 7 are set too);
-                                bits 16-18: log2 of the projection's record bytes, less one (4 bytes: 1 ... 64 bytes: 5; 0 when bit 3 is clear);
-                                bit 20: the payload records were gathered from the projection's GROUPED form (bits 3, 7, 13 and 15 are set too);
-                                bit 21: ... and the predicate bits were read from the planes CLUSTERED in the tiles' grouped order: only the words of
-                                        the run of the `==` literal in every tile (bit 20 is set too);
-                                bit 22: the filter's VH_F_INSET leaves were evaluated by set lookup;
-                                bit 23: ... at least one of them by binary search in a sorted array (the others, or all: one bit of a bitmap);
-                                bit 25: ... or, instead of a lookup per row, all of them from truth tables on the bit-sliced predicate planes
+                                bit 10: VH_INFO_TUPLE1 — DENSE_PART wrote one-word tuples (gid and values packed into 8 bytes);
+                                bit 11: VH_INFO_PREDPACK — predicate columns streamed as byte planes of a bit-packed predicate projection (vh_table_predpack; bit 4 is set too);
+                                bit 12: VH_INFO_STREAMED_PAYLOAD — the payload was STREAMED — 4-byte bit-field records beside the predicate columns, a survivor's
+                                        record queued in its row's place — not gathered (bits 3 and 7 are set too);
+                                bit 13: VH_INFO_SLICED — ... of the predicate projection's BIT-SLICED form (comparisons bit-serial on 32 rows per lane; bit 11 is set too);
+                                bit 14: VH_INFO_TUPLE4 — DENSE_PART's one-word tuples were FOUR bytes (bit 10 is set too);
+                                bit 15: VH_INFO_PACK_BITS — the projection's records are bit fields (bits 3 and 7 are set too);
+                                bits 16-18: VH_INFO_REC_MASK — log2 of the projection's record bytes, less one (4 bytes: 1 ... 64 bytes: 5; 0 when bit 3 is clear);
+                                bit 19: VH_INFO_BUILD_PENDING — (VH_BUILD_BACKGROUND tables) a kernel compile or a layout build for this query's shape is queued or
+                                        running: this query ran on what existed (the pre-built kernels, the arenas, layouts already there);
+                                bit 20: VH_INFO_GROUPED_PAYLOAD — the payload records were gathered from the projection's GROUPED form (bits 3, 7, 13 and 15 are set too);
+                                bit 21: VH_INFO_GROUPED_PLANES — ... and the predicate bits were read from the planes CLUSTERED in the tiles' grouped order: only the
+                                        words of the run of the `==` literal in every tile (bit 20 is set too);
+                                bit 22: VH_INFO_INSET — the filter's VH_F_INSET leaves were evaluated by set lookup;
+                                bit 23: VH_INFO_INSET_SEARCH — ... at least one of them by binary search in a sorted array (the others, or all: one bit of a bitmap);
+                                bit 24: VH_INFO_EVICTED — (tables with a layout budget) planning this query evicted at least one derived layout;
+                                bit 25: VH_INFO_INSET_SLICED — ... or, instead of a lookup per row, all of the set leaves from truth tables on the bit-sliced predicate planes
                                         (bits 13 and 22 are set too; bit 23 still tells the form of the ordinary tables, which are uploaded all the same);
-                                bit 19: (VH_BUILD_BACKGROUND tables) a kernel compile or a layout build for this query's shape is queued or running:
-                                        this query ran on what existed (the pre-built kernels, the arenas, layouts already there);
-                                bit 24: (tables with a layout budget) planning this query evicted at least one derived layout;
-                                bit 26: a PRE-BUILT scan read the filter off the bit-sliced predicate planes (VH_PLAN_SLICED_PREBUILT: bits 4, 11
+                                bit 26: VH_INFO_SLICED_PREBUILT — a PRE-BUILT scan read the filter off the bit-sliced predicate planes (VH_PLAN_SLICED_PREBUILT: bits 4, 11
                                         and 13 are set too, bits 22 and 25 when the filter has VH_F_INSET leaves; bits 0, 1 and 5 are clear);
-                                bit 27: the aggregate was computed ON the bit-sliced planes, sums and min / max by popcount (VH_PLAN2_PLANE_AGG:
+                                bit 27: VH_INFO_PLANE_AGG — the aggregate was computed ON the bit-sliced planes, sums and min / max by popcount (VH_PLAN2_PLANE_AGG:
                                         bits 4, 11 and 13 are set too, bits 22 and 25 when the filter has VH_F_INSET leaves; bits 0, 1, 5 and 26
                                         are clear, and so are the projection's bits 3, 7 and 15-18: no payload is gathered);
-                                bit 28: the grouped form is SUB-SORTED by the column of a range leaf (tiles ordered by grouping value, then that
+                                bit 28: VH_INFO_SUBTRIM — the grouped form is SUB-SORTED by the column of a range leaf (tiles ordered by grouping value, then that
                                         column's field, then row) and the scan TRIMMED every run to the words that can pass the leaf, found
                                         through 64 boundary keys per tile (bits 20 and 21 are set too);
-                                bit 29: the scan over the clustered planes filled every wave's group of up to 64 tiles ACROSS segment boundaries
+                                bit 29: VH_INFO_GPSPAN — the scan over the clustered planes filled every wave's group of up to 64 tiles ACROSS segment boundaries
                                         and queued a survivor as its record's table-wide index (bits 20 and 21 are set too);
-                                bit 30: the result was filled by a FUSED launch of a batch (vh_query_agg_batch: scan_agg_planes_batch_kernel answered
+                                bit 30: VH_INFO_BATCH_FUSED — the result was filled by a FUSED launch of a batch (vh_query_agg_batch: scan_agg_planes_batch_kernel answered
                                         several members at once; bit 27 and its company are set too, bits 0, 1, 5 and 26 are clear) */
   uint64_t returned_groups;  /* rows vh_result_copy delivers (= ngroups without HAVING) */
 } vh_result_info;

@@ -28,7 +28,7 @@ typedef struct vdb_stats {          /* query::QueryStats (src/query/stats.h:35-5
   double compile_time, whole_time, scan_kernel_ms, device_total_ms;
   int32_t path, build_pending;      /* build_pending: background builds are on and a compile / layout build for this query's shape is queued or running */
   double compile_ms;                /* the build worker's compiles for the query's table so far (0 with inline builds) */
-  uint32_t device_flags, retries;   /* vh_result_info.reserved of the query's device run (include/viya_hip.h: compiled kernel, layouts read, set lookups ...) and its re-plans */
+  uint32_t device_flags, retries;   /* vh_result_info.reserved of the query's device run (enum vh_info_bits of include/viya_hip.h: VH_INFO_JIT a compiled kernel, the layouts read, set lookups ...) and its re-plans */
 } vdb_stats;
 
 VDB_API int vdb_open(const char* config_json, int device, vdb** out);        /* db::Database(config) */

@@ -45,8 +45,8 @@ struct Session;
 struct Stats {
   uint64_t scanned_segments, scanned_recs, aggregated_recs, output_recs;      /* query::QueryStats (src/query/stats.h:35-58) */
   /* what the device path ran on, for a maintainer's logs (the reference reports compile_time separately for the same reason): the flags of
-   * vh_result_info.reserved — bit 5 a scan kernel compiled for the plan shape, bit 3 a payload projection, bit 4 narrow predicate copies,
-   * bit 9 a tuple pool placed by vh_table_prepare, ... (include/viya_hip.h) —, re-plans of this query, and the kernels' time */
+   * vh_result_info.reserved — VH_INFO_JIT a scan kernel compiled for the plan shape, VH_INFO_PACKED a payload projection, VH_INFO_NARROW
+   * narrow predicate copies, ... (enum vh_info_bits, include/viya_hip.h) —, re-plans of this query, and the kernels' time */
   uint32_t device_flags, retries;
   double scan_kernel_ms;
   double sync_ms;            /* host time Run spent bringing the mirror up to date (assembling and enqueueing the batch; 0.00x when nothing changed) */

@@ -76,7 +76,7 @@ def history(tw, background):
         bi = tw.dt.build_info()
         print(f"query {i}: flags {res.flags:#x} queued {bi.jobs_queued} running {bi.jobs_running} inline {bi.inline_builds}", flush=True)
         if background:
-            assert not res.flags & 32, "a compiled kernel ran while the worker was held"
+            assert not res.flags & capi.INFO_JIT, "a compiled kernel ran while the worker was held"
             assert res.flags & PENDING, f"query {i}: the pending bit is clear"
             assert bi.inline_builds == 0
             assert bi.jobs_queued >= 1
@@ -93,9 +93,9 @@ def history(tw, background):
     res = tw.query("last query", st)
     bi = tw.dt.build_info()
     print(f"last query: flags {res.flags:#x} inline {bi.inline_builds}", flush=True)
-    assert res.flags & 32, f"no compiled kernel in the steady state: {res.flags:#x}"
-    for bit in (3, 15, 13):
-        assert res.flags & (1 << bit), f"bit {bit} clear in the steady state: {res.flags:#x}"
+    assert res.flags & capi.INFO_JIT, f"no compiled kernel in the steady state: {res.flags:#x}"
+    for name in ("PACKED", "PACK_BITS", "SLICED"):
+        assert res.flags & getattr(capi, "INFO_" + name), f"{name} clear in the steady state: {res.flags:#x}"
     if background:
         assert not res.flags & PENDING
         assert bi.compile_ms > 0 and bi.kernels_compiled >= 1
@@ -132,11 +132,6 @@ def wait_running(dt, seconds=30):
 
 
 PRED_COLS, M0, COUNT = [2, 3, 4], 7, 9      # C3: the filter's columns d2, d3, d4; SUM(m0) and COUNT
-
-
-def rec_bytes(flags):
-    code = (flags >> 16) & 7
-    return (2 << code) if flags & 8 else 0      # bits 16-18: log2 of the record bytes, less one
 
 
 def passing_row(cols):
@@ -182,16 +177,16 @@ def case_sync_during_build():
     only_metrics = [a if tw.w.columns[ci].kind >= 16 else None for ci, a in enumerate(tw.cols[1])]
     tw.dt.sync_batch([(3, 200_000, 50_000, SEG, tw.cols[3], 0), (1, 1000, 4000, SEG, only_metrics, capi.SYNC_METRICS_ONLY)])
     res = tw.query("during the hold")
-    assert not res.flags & 8 and res.flags & PENDING, f"{res.flags:#x}"
+    assert not res.flags & capi.INFO_PACKED and res.flags & PENDING, f"{res.flags:#x}"
     hold(None)
     bi = tw.dt.build_wait(WAIT_MS)
     print(f"first half: layouts {bi.layouts_built} done {bi.jobs_done} declined {bi.jobs_declined} restarts {bi.layout_restarts} failed {bi.jobs_failed}", flush=True)
     assert bi.layouts_built == before.layouts_built + 1 and bi.jobs_failed == 0 and bi.jobs_declined == 0
     res = tw.query("after the sync")
-    print(f"flags {res.flags:#x} record bytes {rec_bytes(res.flags)}", flush=True)
-    assert res.flags & 8 and res.flags & 32 and not res.flags & PENDING, f"no projection in use: {res.flags:#x}"
+    print(f"flags {res.flags:#x} record bytes {capi.info_rec_bytes(res.flags)}", flush=True)
+    assert res.flags & capi.INFO_PACKED and res.flags & capi.INFO_JIT and not res.flags & PENDING, f"no projection in use: {res.flags:#x}"
     assert tw.dt.build_info().inline_builds == 0
-    narrow_bytes = rec_bytes(res.flags)
+    narrow_bytes = capi.info_rec_bytes(res.flags)
     assert narrow_bytes == 4, "C3's projection is a 4-byte bit-field record"
 
     # ---- a value that outgrows its field, in a row that passes the filter, while the next projection waits before it publishes
@@ -211,12 +206,12 @@ def case_sync_during_build():
           f"restarts {bi.layout_restarts} failed {bi.jobs_failed}", flush=True)
     for label in ("after the wide value", "after the wide value, again"):
         res = tw.query(label)                     # (the oracle's rows include the wide value's group)
-        print(f"{label}: flags {res.flags:#x} record bytes {rec_bytes(res.flags)}", flush=True)
-        assert not res.flags & 8 or rec_bytes(res.flags) > narrow_bytes, f"a projection at the stale width is in use: {res.flags:#x}"
+        print(f"{label}: flags {res.flags:#x} record bytes {capi.info_rec_bytes(res.flags)}", flush=True)
+        assert not res.flags & capi.INFO_PACKED or capi.info_rec_bytes(res.flags) > narrow_bytes, f"a projection at the stale width is in use: {res.flags:#x}"
     bi = tw.dt.build_wait(WAIT_MS)
     res = tw.query("after the rebuild")
-    print(f"after the rebuild: flags {res.flags:#x} record bytes {rec_bytes(res.flags)}", flush=True)
-    assert not res.flags & 8 or rec_bytes(res.flags) > narrow_bytes
+    print(f"after the rebuild: flags {res.flags:#x} record bytes {capi.info_rec_bytes(res.flags)}", flush=True)
+    assert not res.flags & capi.INFO_PACKED or capi.info_rec_bytes(res.flags) > narrow_bytes
     bi = tw.dt.build_info()
     # the projection the held job built was not kept as it was: it was voided at its first refresh and replaced (one more published), or declined
     assert bi.layouts_built + bi.jobs_declined >= before.layouts_built + before.jobs_declined + 1
@@ -236,14 +231,14 @@ def case_hashed_partitioning():
     hold("start")
     res, _ = run(tab, dt, q, flags=HP)
     print(f"pending: flags {res.flags:#x} path {res.path} kernel {res.kernel}", flush=True)
-    assert res.path == "hash" and not res.flags & 64 and not res.flags & 32 and res.flags & PENDING, f"{res.flags:#x}"
+    assert res.path == "hash" and not res.flags & capi.INFO_HPART and not res.flags & capi.INFO_JIT and res.flags & PENDING, f"{res.flags:#x}"
     assert dt.build_info().jobs_queued >= 1
     hold(None)
     bi = dt.build_wait(WAIT_MS)
     assert bi.kernels_compiled >= 1 and bi.jobs_failed == 0
     res, _ = run(tab, dt, q, flags=HP)
     print(f"ready: flags {res.flags:#x} kernel {res.kernel}", flush=True)
-    assert res.flags & 64 and res.flags & 32 and not res.flags & PENDING, f"{res.flags:#x}"
+    assert res.flags & capi.INFO_HPART and res.flags & capi.INFO_JIT and not res.flags & PENDING, f"{res.flags:#x}"
     assert dt.build_info().inline_builds == 0
     dt.close()
 
@@ -356,7 +351,7 @@ def case_lifetimes():
     print(f"prepare: compiled {bi.kernels_compiled} cached {bi.kernels_cached} done {bi.jobs_done}", flush=True)
     assert bi.kernels_compiled == 1, "the held shape was compiled by the worker, once"
     res = d.query("d after prepare")
-    assert res.flags & 32
+    assert res.flags & capi.INFO_JIT
     d.close()
     hold("start")
     a = Twin(background=True)

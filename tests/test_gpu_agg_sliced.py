@@ -34,8 +34,8 @@ METRIC = {"m0": 7, "m1": 8, "count": 9, "m3": 10, "m4": 11}
 PREBUILT = capi.PLAN_SLICED_PREBUILT
 BASE = capi.PLAN_NO_JIT | capi.PLAN_NO_LANES
 BIT26 = capi.INFO_SLICED_PREBUILT
-ON_PLANES = 1 << 4 | 1 << 11 | 1 << 13           # vh_result_info.reserved: narrowed, a predicate projection, its bit-sliced form
-OFF = 1 << 0 | 1 << 1 | 1 << 5                   # a register-resident kernel, its lanes form, a compiled kernel
+ON_PLANES = capi.INFO_ON_PLANES      # vh_result_info.reserved: narrowed, a predicate projection, its bit-sliced form
+OFF = capi.INFO_FAST | capi.INFO_LANES | capi.INFO_JIT      # a register-resident kernel, its lanes form, a compiled kernel
 SETS = capi.INFO_INSET | capi.INFO_INSET_SLICED
 OPS = [("eq", capi.OP_EQ), ("ne", capi.OP_NE), ("lt", capi.OP_LT), ("le", capi.OP_LE), ("gt", capi.OP_GT), ("ge", capi.OP_GE)]
 SUM_COUNT = ("m0", "count")
@@ -134,7 +134,7 @@ def both(h, filt, dims=(D2,), metrics=SUM_COUNT, flags=0, seg_rows=None, on=True
 
 def expect_flags(a, b, on, sets, label):
     assert bool(a.flags & BIT26) == on and a.sliced_prebuilt == on, (label, hex(a.flags), a.kernel)
-    assert not a.flags & (1 << 5) and not a.jit, (label, hex(a.flags))
+    assert not a.flags & capi.INFO_JIT and not a.jit, (label, hex(a.flags))
     if on:
         assert a.flags & ON_PLANES == ON_PLANES and not a.flags & OFF, (label, hex(a.flags))
         assert a.kernel.startswith("scan_agg_sliced_kernel<"), (label, a.kernel)

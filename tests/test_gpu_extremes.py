@@ -145,7 +145,7 @@ def test_extreme_keys(edge, dims, flags):
     tab, dt = edge
     res, st = run(tab, dt, X.key_query(dims), flags)
     if res.path == "hash" and not res.hpart:      # the LDS front table takes one-word keys only (packed by element width, vhh_plan.h)
-        assert bool(res.flags & 4) == (X.key_words(tab, dims) == 1), (dims, res.flags)
+        assert bool(res.flags & capi.INFO_LDS_HASH) == (X.key_words(tab, dims) == 1), (dims, res.flags)
     if dims in (["d_long"], ["d_ulong"], ["d_float"], ["d_double"]) and not flags & capi.PLAN_FORCE_GLOBAL:
         assert res.path == "hash", (dims, res.path)      # INT64_MIN..INT64_MAX / a u64 range past 2^63: the digit extent overflows
 
@@ -280,7 +280,7 @@ def test_dense_part_tuple_widths(total, one_word, four):
     try:
         res, _ = run(tab, dt, TUPLE_Q, capi.PLAN_FORCE_PART | capi.PLAN_FORCE_JIT)
         assert res.path == "dense_part" and res.retries == 0, (res.path, res.retries)
-        assert bool(res.flags & 1024) == one_word and res.tuple4 == four, (total, res.flags, res.kernel)
+        assert bool(res.flags & capi.INFO_TUPLE1) == one_word and res.tuple4 == four, (total, res.flags, res.kernel)
     finally:
         dt.close()
 
@@ -443,6 +443,6 @@ def test_one_word_tuples_recover_from_a_wide_value(monkeypatch):
             monkeypatch.setenv("VH_TEST_TUPLE_BITS", k)
             res, _ = run(tab, dt, q, capi.PLAN_FORCE_PART | capi.PLAN_FORCE_JIT, label="tuple bits -" + k)
             monkeypatch.delenv("VH_TEST_TUPLE_BITS")
-            assert res.retries >= 1 and not res.flags & 1024 and not res.tuple4, (res.retries, res.flags)
+            assert res.retries >= 1 and not res.flags & capi.INFO_TUPLE1 and not res.tuple4, (res.retries, res.flags)
     finally:
         dt.close()

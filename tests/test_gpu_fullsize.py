@@ -92,13 +92,14 @@ def test_c3_headline_configuration_is_what_bench_times(c3_full):
     derived layouts for whatever follows.)"""
     from oracle import viya_oracle as vo
     from tests.parity import build_oracle_table, compare
+    from viyadb_amd import capi
     w, t = c3_full
     plan = _plan(w)
     flags = t.warm(plan)
     res = t.query_agg(plan)
     assert res.flags == flags or (res.flags ^ flags) & ~512 == 0        # (bit 9, the placed pool, belongs to the context that ran)
     assert res.path == "dense_part" and res.jit and res.packed and res.packed_compressed and res.predpack and res.sliced and res.narrow, (res.flags, res.kernel)
-    assert res.flags & 1024, "one-word tuples"
+    assert res.flags & capi.INFO_TUPLE1, "one-word tuples"
     assert res.scanned_recs == 1_000_000_000 and res.ngroups == 100_000
     other = t.query_agg(_plan(w, flags=1))
     kf, sf = _canon(res)
@@ -135,7 +136,7 @@ def test_one_word_tuples_replan_when_an_upsert_outgrows_their_bits():
                                flags=capi.PLAN_FORCE_JIT | capi.PLAN_FORCE_PART | capi.PLAN_FORCE_PACK)
         res = t.query_agg(plan())
         compare(res, vo.scan_aggregate(vo.parse_query(ot, w.query)), "before")
-        assert res.jit and res.path == "dense_part" and res.flags & 1024 and res.packed_compressed
+        assert res.jit and res.path == "dense_part" and res.flags & capi.INFO_TUPLE1 and res.packed_compressed
         # m0 (long_sum, values < 1001: 10 bits) of a few rows that PASS the filter in three segments becomes 2^40 + x; count of one row 77
         items = []
         for s in (1, 4, 6):

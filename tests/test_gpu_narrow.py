@@ -37,7 +37,7 @@ def test_workloads_through_narrow_copies(name, flags):
         res = dt.query_agg(plan)
         st = vo.scan_aggregate(vo.parse_query(build_oracle_table(w, 3, 199_993), w.query))
         compare(res, st, f"{name} narrow flags={flags}")
-        generic = bool(flags & 8)
+        generic = bool(flags & capi.PLAN_NO_FAST)
         assert res.narrow == (name == "C3" and not generic), (res.narrow, res.kernel)
         res = dt.query_agg(AggPlan(filter=w.plan.filter, groups=w.plan.groups, metrics=w.plan.metrics, flags=flags | capi.PLAN_NO_NARROW,
                                    groups_hint=w.plan.groups_hint))

@@ -229,7 +229,7 @@ def test_prepare_pays_the_first_use_costs_up_front():
     cold, warm = synth.create_device_table(w, 3, 100_000), synth.create_device_table(w, 3, 100_000)
     try:
         flags = warm.warm(plan)
-        assert flags & 8 and flags & 16, flags                    # bit 3: projection, bit 4: narrow predicate copies
+        assert flags & capi.INFO_PACKED and flags & capi.INFO_NARROW, flags      # bit 3: projection, bit 4: narrow predicate copies
         first = warm.query_agg(plan)
         compare(first, st, "prepared")
         assert first.packed and first.narrow

@@ -40,8 +40,8 @@ METRIC = {"m0": M0, "m1": M1, "count": COUNT, "m3": M3, "m4": M4}
 FLAG2 = capi.PLAN2_PLANE_AGG
 BASE = capi.PLAN_NO_JIT
 BIT27 = capi.INFO_PLANE_AGG
-ON_PLANES = 1 << 4 | 1 << 11 | 1 << 13               # vh_result_info.reserved: narrowed, a predicate projection, its bit-sliced form
-OFF = 1 << 0 | 1 << 1 | 1 << 5 | 1 << 26             # a register-resident kernel, its lanes form, a compiled kernel, the pre-built scan over the planes
+ON_PLANES = capi.INFO_ON_PLANES      # vh_result_info.reserved: narrowed, a predicate projection, its bit-sliced form
+OFF = capi.INFO_FAST | capi.INFO_LANES | capi.INFO_JIT | capi.INFO_SLICED_PREBUILT      # a register-resident kernel, its lanes form, a compiled kernel, the pre-built scan over the planes
 SETS = capi.INFO_INSET | capi.INFO_INSET_SLICED
 KERNEL = "scan_agg_planes_kernel<"
 C3F = AND(REL(D2, "eq", 1), REL(D3, "lt", 447), REL(D4, "ge", 553))
@@ -94,7 +94,7 @@ def one():
 
 def expect(a, b, on, sets, label):
     assert bool(a.flags & BIT27) == on and a.plane_agg == on, (label, hex(a.flags), a.kernel)
-    assert not a.flags & (1 << 5) and not a.jit, (label, hex(a.flags))
+    assert not a.flags & capi.INFO_JIT and not a.jit, (label, hex(a.flags))
     if on:
         assert a.flags & ON_PLANES == ON_PLANES and not a.flags & OFF, (label, hex(a.flags))
         assert a.kernel.startswith(KERNEL), (label, a.kernel)

@@ -15,8 +15,8 @@ pytestmark = pytest.mark.gpu
 ROWS, CAP = 5000, 8192
 ID = 6                                           # C3's row-id column: in no projection
 NO_SLICED = capi.PLAN_NO_SLICED
-ON_PLANES = 1 << 4 | 1 << 11 | 1 << 13           # vh_result_info.reserved: narrowed, a predicate projection, its bit-sliced form
-SLICED = 1 << 13
+ON_PLANES = capi.INFO_ON_PLANES      # vh_result_info.reserved: narrowed, a predicate projection, its bit-sliced form
+SLICED = capi.INFO_SLICED
 OPS = [("eq", capi.OP_EQ), ("ne", capi.OP_NE), ("lt", capi.OP_LT), ("le", capi.OP_LE), ("gt", capi.OP_GT), ("ge", capi.OP_GE)]
 
 

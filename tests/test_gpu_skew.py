@@ -307,7 +307,7 @@ def test_four_byte_tuples(monkeypatch):
     for wl in ("C3", "C3z"):
         w = synth.WORKLOADS[wl](segment_rows=150_000)
         res, st = check_workload(w, nseg=8, flags=FORCE_PART | capi.PLAN_FORCE_JIT)
-        assert res.path == "dense_part" and res.retries == 0 and (res.flags & 1024), (res.path, res.retries, res.flags)
+        assert res.path == "dense_part" and res.retries == 0 and (res.flags & capi.INFO_TUPLE1), (res.path, res.retries, res.flags)
         monkeypatch.setenv("VH_NO_TUPLE4", "1")
         res8, _ = check_workload(w, nseg=8, flags=FORCE_PART | capi.PLAN_FORCE_JIT)
         monkeypatch.delenv("VH_NO_TUPLE4")

@@ -52,7 +52,7 @@ def leg(name, rows):
             steady.append((time.perf_counter() - t0) * 1e3)
         out["after_wait_per_query_ms"] = steady
         out["after_wait_flags"] = res.flags
-        ready = [i for i, f in enumerate(info_flags) if f & 32 and f & 8 and not f & capi.INFO_BUILD_PENDING]
+        ready = [i for i, f in enumerate(info_flags) if f & capi.INFO_JIT and f & capi.INFO_PACKED and not f & capi.INFO_BUILD_PENDING]
         out["first_query_on_kernel_and_layouts"] = ready[0] if ready else None
     dt.close()
     print("LEG " + json.dumps(out), flush=True)

@@ -54,7 +54,7 @@ def legs(limit):
         k, v, (info, path) = sorted(ks[label]), sorted(ws[label]), last[label]
         lines.append({"tag": tag, "leg": label, "limit": limit, "rows": nseg * w.segment_rows, "kernel_ms": round(k[len(k) // 2], 4), "kernel_ms_min": round(k[0], 4),
                       "wall_ms": round(v[len(v) // 2], 4), "queries": len(k), "nrows": info.nrows, "passed": info.passed_recs,
-                      "flags": path, "sliced": None if path is None else bool(path & (1 << 13))})
+                      "flags": path, "sliced": None if path is None else bool(path & capi.INFO_SLICED)})
         print(json.dumps(lines[-1]), flush=True)
 
 

@@ -151,19 +151,43 @@ class CommOps(C.Structure):
 COMM_ID_BYTES = 128
 
 BUILD_INLINE, BUILD_BACKGROUND = 0, 1
-INFO_PACKED = 1 << 3             # vh_result_info.reserved bit 3: group / metric values came from a payload projection
-INFO_BUILD_PENDING = 1 << 19      # vh_result_info.reserved bit 19
-INFO_GROUPED_PAYLOAD = 1 << 20    # vh_result_info.reserved bit 20
-INFO_GROUPED_PLANES = 1 << 21     # vh_result_info.reserved bit 21
-INFO_INSET = 1 << 22              # vh_result_info.reserved bit 22: the filter's set leaves were evaluated by lookup
-INFO_INSET_SEARCH = 1 << 23       # ... bit 23: at least one of them by binary search in a sorted array
-INFO_INSET_SLICED = 1 << 25       # ... bit 25: all of them from truth tables on the bit-sliced predicate planes instead (no lookup per row)
-INFO_SLICED_PREBUILT = 1 << 26    # ... bit 26: a pre-built scan read the filter off the bit-sliced predicate planes (bits 4, 11 and 13 are set too)
-INFO_PLANE_AGG = 1 << 27          # ... bit 27: the aggregate was computed on the bit-sliced planes (bits 4, 11 and 13 are set too; bits 0, 1, 5 and 26 are clear)
-INFO_SUBTRIM = 1 << 28             # ... bit 28: the clustered planes are a sub-sorted form's and every run was trimmed by the sub column's leaf (bits 20 and 21 are set too)
-INFO_GPSPAN = 1 << 29              # ... bit 29: the clustered scan's tile groups spanned segments, its queue held table-wide record indexes (bits 20 and 21 are set too)
-INFO_BATCH_FUSED = 1 << 30         # ... bit 30: the result was filled by a fused launch of a batch (vh_query_agg_batch; bit 27 and its company are set too)
-INFO_EVICTED = 1 << 24            # ... bit 24: planning this query evicted at least one derived layout (tables with a layout budget)
+# enum vh_info_bits: what ran, one name per bit of vh_result_info.reserved (include/viya_hip.h tells each bit's meaning at the field)
+INFO_FAST = 1 << 0                # the register-resident fast scan kernel ran
+INFO_LANES = 1 << 1               # ... its no-compaction "lanes" variant
+INFO_LDS_HASH = 1 << 2            # LDS front table of the hash path
+INFO_PACKED = 1 << 3              # group / metric values came from a payload projection
+INFO_NARROW = 1 << 4              # predicate columns streamed from narrow copies
+INFO_JIT = 1 << 5                 # a scan kernel compiled for this plan shape ran
+INFO_HPART = 1 << 6               # hashed partitioning of the hash path
+INFO_PACKED_COMPRESSED = 1 << 7   # the projection's records are compressed
+INFO_HP_PACKED = 1 << 8           # the hashed partitioning's tuples were packed (bit 9 is never set)
+INFO_TUPLE1 = 1 << 10             # DENSE_PART wrote one-word tuples
+INFO_PREDPACK = 1 << 11           # predicate columns streamed as byte planes of a bit-packed predicate projection (bit 4 is set too)
+INFO_STREAMED_PAYLOAD = 1 << 12   # the payload was streamed beside the predicate columns, not gathered (bits 3 and 7 are set too)
+INFO_SLICED = 1 << 13             # ... of the predicate projection's bit-sliced form
+INFO_TUPLE4 = 1 << 14             # DENSE_PART's one-word tuples were four bytes (bit 10 is set too)
+INFO_PACK_BITS = 1 << 15          # the projection's records are bit fields (bits 3 and 7 are set too)
+INFO_REC_SHIFT = 16               # bits 16-18: log2 of the projection's record bytes, less one (info_rec_bytes)
+INFO_REC_MASK = 7 << 16
+INFO_BUILD_PENDING = 1 << 19      # a kernel compile or a layout build for this query's shape is queued or running (BUILD_BACKGROUND tables)
+INFO_GROUPED_PAYLOAD = 1 << 20    # the payload records were gathered from the projection's grouped form
+INFO_GROUPED_PLANES = 1 << 21     # ... and the predicate bits read from the planes clustered in the same order (bit 20 is set too)
+INFO_INSET = 1 << 22              # the filter's set leaves were evaluated by lookup
+INFO_INSET_SEARCH = 1 << 23       # ... at least one of them by binary search in a sorted array
+INFO_EVICTED = 1 << 24            # planning this query evicted at least one derived layout (tables with a layout budget)
+INFO_INSET_SLICED = 1 << 25       # ... all of the set leaves from truth tables on the bit-sliced predicate planes instead (no lookup per row)
+INFO_SLICED_PREBUILT = 1 << 26    # a pre-built scan read the filter off the bit-sliced predicate planes (bits 4, 11 and 13 are set too)
+INFO_PLANE_AGG = 1 << 27          # the aggregate was computed on the bit-sliced planes (bits 4, 11 and 13 are set too; bits 0, 1, 5 and 26 are clear)
+INFO_SUBTRIM = 1 << 28            # the clustered planes are a sub-sorted form's and every run was trimmed by the sub column's leaf (bits 20 and 21 are set too)
+INFO_GPSPAN = 1 << 29             # the clustered scan's tile groups spanned segments, its queue held table-wide record indexes (bits 20 and 21 are set too)
+INFO_BATCH_FUSED = 1 << 30        # the result was filled by a fused launch of a batch (vh_query_agg_batch; bit 27 and its company are set too)
+INFO_ON_PLANES = INFO_NARROW | INFO_PREDPACK | INFO_SLICED      # the filter was read off the bit-sliced predicate planes
+INFO_PROJECTION = INFO_PACKED | INFO_PACKED_COMPRESSED | INFO_PACK_BITS | INFO_REC_MASK      # everything that describes a payload projection
+
+
+def info_rec_bytes(flags: int) -> int:
+    """Bytes of one projection record (0: no projection was read)."""
+    return 2 << ((flags & INFO_REC_MASK) >> INFO_REC_SHIFT) if flags & INFO_PACKED else 0
 
 
 BATCH_MAX = 8                     # VH_BATCH_MAX: members of one vh_query_agg_batch call

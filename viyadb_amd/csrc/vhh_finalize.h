@@ -29,7 +29,7 @@ static int heavy_pass_enqueue(vh_result* r, VhHeavyRun& H) {
   o.rp.cap_override = H.cap; o.rp.force_hash = true; o.rp.no_hpart = true;
   const int rc = query_launch_locked(t, H.x2, &H.p2, &H.r2, o);
   g_heavy = VhHeavyCtx{};
-  if (g_plan_carry) { r->info.reserved |= 1u << 24; g_plan_carry = false; }      // (what the pass evicted is the query's to report)
+  if (g_plan_carry) { r->info.reserved |= VH_INFO_EVICTED; g_plan_carry = false; }      // (what the pass evicted is the query's to report)
   if (rc) H.r2 = nullptr; else H.r2->exec = H.x2;
   return rc;
 }
@@ -593,7 +593,7 @@ static int batch_launch_scans(VhBatchFuse& F, uint32_t n, VhBatchGroups* G, uint
       *failed = m[k];
       if (s.x->stream() != ls) HIP_TRY(hipStreamWaitEvent(s.x->stream(), lx->ev_batch[1], 0));
       s.r->kernel = nm;
-      s.r->info.reserved |= 1u << 30;
+      s.r->info.reserved |= VH_INFO_BATCH_FUSED;
       if (int rc = query_scan_tail(s.r, s.x)) return rc;
     }
   }
@@ -678,10 +678,10 @@ extern "C" int vh_query_agg_batch(vh_table* t, const vh_plan* const* plans, uint
     (void)hipEventElapsedTime(&ms, fuse->scan[G.lead[g]].x->ev_batch[0], fuse->scan[G.lead[g]].x->ev_batch[1]);
     bi.fused_kernel_ms += ms;
     for (uint32_t i = 0; i < n; ++i)
-      if (G.of[i] == (int32_t)g && (out[i]->info.reserved & (1u << 30))) { out[i]->info.scan_kernel_ms = ms; ++bi.fused_members; }      // (a member that was planned again is a single query's result)
+      if (G.of[i] == (int32_t)g && (out[i]->info.reserved & VH_INFO_BATCH_FUSED)) { out[i]->info.scan_kernel_ms = ms; ++bi.fused_members; }      // (a member that was planned again is a single query's result)
   }
   bi.singles = n - bi.fused_members;
-  if (evicted) for (uint32_t i = 0; i < n; ++i) out[i]->info.reserved |= 1u << 24;
+  if (evicted) for (uint32_t i = 0; i < n; ++i) out[i]->info.reserved |= VH_INFO_EVICTED;
   if (info) *info = bi;
   return VH_OK;
 }
@@ -809,12 +809,12 @@ static int table_prepare(vh_table* t, const vh_plan* plan, vh_result_info* info_
   for (int round = 0; round < 3; ++round) {
     vh_result* r = nullptr;
     if (int rc = vh_query_agg(t, plan, &r)) return rc;
-    const uint32_t now = r->info.reserved & ~(1u << 24);      // (whether the round evicted something is no property of the plan)
+    const uint32_t now = r->info.reserved & ~(uint32_t)VH_INFO_EVICTED;      // (whether the round evicted something is no property of the plan)
     if (info_out) *info_out = r->info;
     vh_result_free(r);
     if (now == last) break;
     last = now;
   }
-  return last & (8u | 2048u) ? place_layouts(t, plan, info_out, 1000.0) : VH_OK;
+  return last & (VH_INFO_PACKED | VH_INFO_PREDPACK) ? place_layouts(t, plan, info_out, 1000.0) : VH_OK;
 }
 

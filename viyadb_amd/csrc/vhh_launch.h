@@ -344,7 +344,7 @@ int QueryBuild::compile_kernel() {
         ++g_build_quiet;        // (the second plan counts towards no automatic layout: this query has been counted)
         const int prc = plan_again(true, false);
         --g_build_quiet;
-        if (!prc && out && *out) (*out)->info.reserved |= 1u << 19;
+        if (!prc && out && *out) (*out)->info.reserved |= VH_INFO_BUILD_PENDING;
         return prc;
       }
       if (!jk) {
@@ -961,15 +961,15 @@ int QueryBuild::launch() {
   for (int k = 0; k < P.npred; ++k) narrowed |= P.pred_width[k] != 4;
   if (jk) { narrowed = jshape.pp_nplanes || jshape.pp_sliced; for (int k = 0; k < jshape.npred; ++k) narrowed |= jshape.pred[k].width != vh_elem_size(jshape.pred[k].type); }
   r->hpart = hpart;
-  r->info.reserved = (hpart ? 64 : 0) | (fastj || jk ? 1 : 0) | (lanes ? 2 : 0) | (P.lds_hash_slots ? 4 : 0) | (packed ? 8 : 0) | (fastj && narrowed ? 16 : 0) | (jk ? 32 : 0) | (packed && packed_compressed ? 128 : 0) | (hpart && hp_pack ? 256 : 0) | (mode == VH_MODE_DENSE_PART && P.gid_bits ? 1024 : 0) | (jk && (jshape.pp_nplanes || jshape.pp_sliced) ? 2048 : 0) | (jk && jshape.qpay ? 4096 : 0) | (jk && jshape.pp_sliced ? 8192 : 0) | (mode == VH_MODE_DENSE_PART && P.gid_bits && P.tuple4 ? 16384 : 0)
-                   | (has_set ? 1u << 22 : 0) | (has_set && set_search ? 1u << 23 : 0) | (jk && has_set && set_truth && jshape.pp_sliced ? 1u << 25 : 0) | (build_pending ? 1u << 19 : 0) | (jk && grouped ? 1u << 20 : 0) | (jk && grouped && gplanes ? 1u << 21 : 0) | (jk && grouped && gplanes && subtrim ? 1u << 28 : 0) | (jk && grouped && gplanes && gpspan ? 1u << 29 : 0) | (packed && packed_bits ? 32768 : 0) | (packed ? (uint32_t)(31 - __builtin_clz(std::max<uint32_t>(packed_rec, 2)) - 1) << 16 : 0);
-  r->fast_scan = (r->info.reserved & 1u) != 0;
-  // the pre-built scan over the bit-sliced planes: bit 26, with the bits of a predicate projection's bit-sliced form (and of the sets' truth tables);
-  // no register-resident kernel, no lanes form, no compiled kernel ran
-  if (sliced_prebuilt) r->info.reserved = (r->info.reserved & ~(1u | 2u | 32u)) | 1u << 26 | 1u << 4 | 1u << 11 | 1u << 13 | (has_set ? 1u << 22 | 1u << 25 : 0u);
-  // the aggregate computed on the planes: bit 27 with the same company, and without bit 26; it gathers no payload, so the projection's bits
-  // (3, 7, 15-18) are clear whatever choose_projection had found
-  if (plane_agg) r->info.reserved = (r->info.reserved & ~(1u | 2u | 32u | 1u << 26 | 8u | 128u | 32768u | 7u << 16)) | 1u << 27 | 1u << 4 | 1u << 11 | 1u << 13 | (has_set ? 1u << 22 | 1u << 25 : 0u);
+  VhWhatRan w;
+  w.hpart = hpart; w.fast = fastj || jk; w.fastj = fastj; w.jk = jk != nullptr; w.lanes = lanes; w.lds_hash = P.lds_hash_slots != 0;
+  w.packed = packed; w.packed_compressed = packed_compressed; w.packed_bits = packed_bits; w.packed_rec = packed_rec;
+  w.narrowed = narrowed; w.hp_pack = hp_pack; w.dense_part = mode == VH_MODE_DENSE_PART; w.gid_bits = P.gid_bits != 0; w.tuple4 = P.tuple4 != 0;
+  w.pp_planes = jshape.pp_nplanes != 0; w.pp_sliced = jshape.pp_sliced != 0; w.qpay = jshape.qpay != 0;
+  w.has_set = has_set; w.set_search = set_search; w.set_truth = set_truth; w.build_pending = build_pending;
+  w.grouped = grouped; w.gplanes = gplanes; w.subtrim = subtrim; w.gpspan = gpspan; w.sliced_prebuilt = sliced_prebuilt; w.plane_agg = plane_agg;
+  r->info.reserved = vh_info_compose(w);
+  r->fast_scan = w.fast;      // (VH_INFO_FAST as planned: a pre-built reader of the planes clears the bit in the result's word)
   if (r->hp_chunks) memset(x->h_chunk, 0, VH_HP_CHUNKS * sizeof(unsigned long long));      // (what the context's previous query left there)
   // a second pass over heavy level-A partitions of a hashed partitioning: from the first pass's tuples when this plan's table can take them as
   // they are (one key word laid out as the first pass's, narrow ids) — else from the table's rows behind the bitmap, like any heavy range
@@ -1068,7 +1068,7 @@ struct PlanTick {
     if (!t->layout_budget) return;
     derived_trim(t, true);
     if (further) g_plan_carry = g_plan_evicted;
-    else if (g_plan_evicted && out && *out) (*out)->info.reserved |= 1u << 24;
+    else if (g_plan_evicted && out && *out) (*out)->info.reserved |= VH_INFO_EVICTED;
   }
 };
 static int query_launch_locked(vh_table* t, VhExec* x, const vh_plan* p, vh_result** out, const VhLaunchOpts& o) {

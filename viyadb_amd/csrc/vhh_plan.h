@@ -1,5 +1,6 @@
 // vhh_plan.h — host side of libviya_hip, part of viya_hip.hip's translation unit (included there, in order; not a stand-alone header):
 // the planner: QueryBuild — filter program, segment snapshot + skipping, group / metric shapes, table organisation, hashed partitioning, projection choice.
+#include "vhh_info.h"      // vh_result_info.reserved: what a query's word says (vh_info_select here, vh_info_compose in vhh_launch.h)
 // ----------------------------------------------------------------- planning
 static int sop_for(int kind, int elem, int* sop, uint64_t* ident) {
   const bool sum = kind == VH_METRIC_SUM || kind == VH_METRIC_AVG || kind == VH_METRIC_COUNT || kind == VH_METRIC_HIDDEN_COUNT;
@@ -768,8 +769,7 @@ int QueryBuild::snapshot_segments() {
       }
     }
     // what ran, in vh_result_info.reserved's bits (vh_rows_flags)
-    r->info.reserved = r->sel_sliced ? (1u << 4 | 1u << 11 | 1u << 13 | (has_set ? 1u << 22 | 1u << 25 : 0u))
-                                     : (has_set ? 1u << 22 | (set_search ? 1u << 23 : 0u) : 0u);
+    r->info.reserved = vh_info_select(r->sel_sliced, has_set, set_search);
     r->info.algorithmic_bytes = rows_to_scan * bytes_per_row;
     *out = holder.release();
     done = true;

@@ -131,6 +131,22 @@ class AggResult:
         return bool(self.flags & capi.INFO_GPSPAN)
 
 
+# AggResult's flag fields and the bit of vh_result_info.reserved each one decodes (the rest of the word: AggResult's properties, `flags`)
+INFO_FIELDS = {
+    "fast": capi.INFO_FAST, "lanes": capi.INFO_LANES, "packed": capi.INFO_PACKED, "narrow": capi.INFO_NARROW, "jit": capi.INFO_JIT,
+    "hpart": capi.INFO_HPART, "packed_compressed": capi.INFO_PACKED_COMPRESSED, "hp_packed": capi.INFO_HP_PACKED,
+    "predpack": capi.INFO_PREDPACK, "sliced": capi.INFO_SLICED, "streamed_payload": capi.INFO_STREAMED_PAYLOAD,
+    "tuple4": capi.INFO_TUPLE4, "pack_bits": capi.INFO_PACK_BITS, "grouped_payload": capi.INFO_GROUPED_PAYLOAD,
+    "grouped_planes": capi.INFO_GROUPED_PLANES, "inset": capi.INFO_INSET, "inset_search": capi.INFO_INSET_SEARCH,
+    "inset_sliced": capi.INFO_INSET_SLICED, "sliced_prebuilt": capi.INFO_SLICED_PREBUILT,
+}
+
+
+def info_fields(flags: int) -> dict:
+    """AggResult's flag fields as vh_result_info.reserved tells them."""
+    return {field: bool(flags & bit) for field, bit in INFO_FIELDS.items()}
+
+
 class DeviceTable:
     """vh_table: the HBM mirror of a db::Table's segment store."""
 
@@ -443,17 +459,13 @@ class DeviceTable:
         hidden = view(C.cast(hp, C.c_void_p).value, np.uint64) if info.has_hidden_count else None
         tail = capi.TailInfo()
         capi.check(self.lib.vh_result_tail(res, C.byref(tail)))
-        out = AggResult(keys, states, hidden, int(info.ngroups), int(info.scanned_recs), int(info.scanned_segments),
-                        int(info.passed_recs), capi.PATH_NAMES[info.path], float(info.scan_kernel_ms),
-                        float(info.total_ms), int(info.algorithmic_bytes), int(info.retries), bool(info.reserved & 1),
-                        bool(info.reserved & 2), bool(info.reserved & 8), int(ng), (self.lib.vh_result_kernel(res) or b"").decode(),
-                        bool(info.reserved & 16), bool(info.reserved & 32), bool(info.reserved & 64), bool(info.reserved & 128), bool(info.reserved & 256),
-                        bool(info.reserved & 2048), bool(info.reserved & 8192), bool(info.reserved & 4096), int(info.reserved),
-                        bool(info.reserved & 16384), bool(info.reserved & 32768),
-                        (2 << ((info.reserved >> 16) & 7)) if info.reserved & 8 else 0,
-                        bool(info.reserved & capi.INFO_GROUPED_PAYLOAD), bool(info.reserved & capi.INFO_GROUPED_PLANES),
-                        bool(info.reserved & capi.INFO_INSET), bool(info.reserved & capi.INFO_INSET_SEARCH),
-                        bool(info.reserved & capi.INFO_INSET_SLICED), bool(info.reserved & capi.INFO_SLICED_PREBUILT))
+        flags = int(info.reserved)
+        out = AggResult(keys=keys, states=states, hidden_count=hidden, ngroups=int(info.ngroups), scanned_recs=int(info.scanned_recs),
+                        scanned_segments=int(info.scanned_segments), passed_recs=int(info.passed_recs), path=capi.PATH_NAMES[info.path],
+                        scan_kernel_ms=float(info.scan_kernel_ms), total_ms=float(info.total_ms),
+                        algorithmic_bytes=int(info.algorithmic_bytes), retries=int(info.retries), returned=int(ng),
+                        kernel=(self.lib.vh_result_kernel(res) or b"").decode(), flags=flags, pack_rec_bytes=capi.info_rec_bytes(flags),
+                        **info_fields(flags))
         out._tail = tail
         return out
 

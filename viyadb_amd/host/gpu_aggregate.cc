@@ -228,7 +228,7 @@ void FetchGroups(vh_result* res, AggregateQuery& query, Groups& groups, QuerySta
   stats.device_total_ms = info.total_ms;
   stats.path = info.path;
   stats.device_flags = info.reserved; stats.retries = info.retries;
-  stats.build_pending = (info.reserved & (1u << 19)) != 0;
+  stats.build_pending = (info.reserved & VH_INFO_BUILD_PENDING) != 0;
 
   groups.n = info.returned_groups;
   std::vector<void*> kp, sp;
