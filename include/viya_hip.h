@@ -564,8 +564,15 @@ VH_API int vh_query_agg(vh_table* t, const vh_plan* plan, vh_result** out);
  * projection V, the same memory scope of their table updates, the same number of snapshot segments and chunks per segment form a group, in
  * plan order, of at most VH_BATCH_MAX members whose LDS tables together take at most 48 KB; the candidate that would pass either bound opens
  * the next group. A group of two or more is answered by ONE launch of scan_agg_planes_batch_kernel: one walk over the chunks, one load of V's
- * plane words, one launch and one wait; each member keeps its own filter (or none), its own projection F, its own snapshot and skipped
- * segments, and its own LDS table. Such a result has vh_result_info.reserved bit 30 set beside bit 27's, vh_result_kernel names
+ * plane words, one launch and one wait; each member keeps its own snapshot and skipped segments, its own row counters and its own LDS
+ * table. Its pass mask — its filter over its projection F, cut at its snapshot — it evaluates itself unless an earlier member of the same
+ * launch has the same one. The sharing rule: two members of a launch share ONE evaluation of the mask per plane word when both have a
+ * filter or both have none; with a filter, both read the same projection F and their programs over its fields are equal (the same tree, the
+ * same relations, the same literals) and hold no VH_F_INSET leaf, whose table is the member's own; and their effective rows are equal in
+ * every segment (the snapshot, 0 for a segment the member skips) — one row fewer in one segment is another mask. The later member takes the
+ * earlier one's mask word; K breakdowns under one filter evaluate it once. Sharing never spans launches, and it changes neither a member's
+ * results nor its scan_kernel_ms, which stays the launch's; vh_result_batch_member says whose mask a member used. A fused result has
+ * vh_result_info.reserved bit 30 set beside bit 27's, vh_result_kernel names
  * scan_agg_planes_batch_kernel<256, S>, and its scan_kernel_ms is the FUSED launch's time, the same for every member of the group (so the
  * members' values must not be added up; vh_batch_info.fused_kernel_ms is the sum over the launches). A group of one, and every member that
  * is no candidate, runs as the single query it is: the flags and the kernel name its vh_query_agg would give, bit 30 clear. A fused member
@@ -582,6 +589,17 @@ typedef struct vh_batch_info {
   uint32_t reserved;
 } vh_batch_info;
 VH_API int vh_query_agg_batch(vh_table* t, const vh_plan* const* plans, uint32_t n, vh_result** out /* n */, vh_batch_info* info /* may be NULL */);
+/* A result's place in a fused launch of vh_query_agg_batch (test and measurement support, like vh_result_tail). All zeros for a result of
+ * vh_query_agg, for a member answered singly, and for a member that was planned again. */
+typedef struct vh_batch_member_info {
+  uint32_t fused;         /* 1: a fused launch filled this result (bit 30); 0: everything below is 0            */
+  uint32_t launch;        /* which fused launch of the call, numbered like vh_batch_info.fused_groups counts     */
+  uint32_t position;      /* the member's place in that launch's member array                                    */
+  uint32_t members;       /* members of that launch                                                              */
+  uint32_t mask_of;       /* position of the member whose pass mask this one used; == position: its own          */
+  uint32_t mask_classes;  /* masks the launch evaluated per plane word (distinct values of mask_of)              */
+} vh_batch_member_info;
+VH_API int vh_result_batch_member(vh_result* r, vh_batch_member_info* out);   /* VH_E_INVALID: a null argument */
 /* Launch only: partial aggregate stays in HBM (multi-GPU: reduce, then finalise). */
 VH_API int vh_query_launch(vh_table* t, const vh_plan* plan, vh_result** out);
 VH_API int vh_result_device_buffers(vh_result* r, vh_device_buffer* bufs,

@@ -199,6 +199,13 @@ class BatchInfo(C.Structure):
                 ("fused_kernel_ms", C.c_float), ("reserved", C.c_uint32)]
 
 
+class BatchMemberInfo(C.Structure):
+    """vh_batch_member_info: a result's place in a fused launch of a batch and whose pass mask it used (vh_result_batch_member). All zeros
+    outside a fused launch."""
+    _fields_ = [("fused", C.c_uint32), ("launch", C.c_uint32), ("position", C.c_uint32), ("members", C.c_uint32),
+                ("mask_of", C.c_uint32), ("mask_classes", C.c_uint32)]
+
+
 class BuildInfo(C.Structure):
     """vh_build_info: what the background build worker did for one table."""
     _fields_ = [("jobs_queued", C.c_uint64), ("jobs_running", C.c_uint64), ("jobs_done", C.c_uint64),
@@ -294,6 +301,7 @@ SYMBOLS = {
     "vh_table_build_info": (C.c_int, [_VP, C.POINTER(BuildInfo)]),
     "vh_result_kernel": (C.c_char_p, [_VP]),
     "vh_result_tail": (C.c_int, [_VP, C.POINTER(TailInfo)]),
+    "vh_result_batch_member": (C.c_int, [_VP, C.POINTER(BatchMemberInfo)]),
     "vh_result_state_elem": (C.c_int, [_VP, C.c_int32]),
     "vh_result_copy": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(C.c_uint64)]),
     "vh_result_view": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(C.POINTER(C.c_uint64))]),

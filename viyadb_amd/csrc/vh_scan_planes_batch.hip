@@ -1,9 +1,9 @@
 // The aggregate scan on the bit-sliced planes for a BATCH of queries (vh_query_agg_batch, include/viya_hip.h): up to VH_BATCH_MAX plans that
 // scan_agg_planes_kernel (vh_scan_planes.hip) would each answer alone share ONE walk over the chunks, ONE load of the value planes V per plane
 // word, one launch and one wait. What a member keeps to itself is what the single kernel's whole per-query state is: a pass mask — its own
-// filter program over its own projection F against its own snapshot — and an LDS table of at most a few KB. vh_batch.h holds the rule that
-// forms a group (same V, same scope, same segments, same chunks per segment); QueryBuild::choose_plane_agg (vhh_launch.h) the rule that makes a
-// plan a candidate.
+// filter program over its own projection F against its own snapshot, unless an earlier member's is the same one (step 1 below) — and an LDS
+// table of at most a few KB. vh_batch.h holds the rule that forms a group (same V, same scope, same segments, same chunks per segment) and
+// the one that lets members of a group share a mask; QueryBuild::choose_plane_agg (vhh_launch.h) the rule that makes a plan a candidate.
 #include "vh_kernels.h"
 #include "vh_launch.h"
 #include "vh_sliced.h"
@@ -19,7 +19,11 @@ static_assert(VH_BATCH_MAX <= 32, "scan_agg_planes_batch_kernel keeps a bit per 
 // that they come by scalar loads like the program and the descriptor of the single kernel (vh_sliced.h) — which is why a member holds its
 // program and its descriptor by value. The walk is the single kernel's over
 // the segments all members share. Per chunk:
-//   1. every member's pass mask of the lane's word: 0 where the chunk lies at or beyond that member's snapshot or its segment is skipped;
+//   1. every member's pass mask of the lane's word: 0 where the chunk lies at or beyond that member's snapshot or its segment is skipped.
+//      ONE evaluation per mask class: a member whose filter program, projection F and effective rows per segment equal an earlier member's
+//      (VhBatchMember::mask_of, set by the host with vh_batch_share) takes that member's word from its LDS slot instead of running the
+//      interpreter again — K breakdowns under one filter evaluate it once. Its row counter, its share of `any` and `need`, its group loop,
+//      its error flag and its flush stay its own;
 //   2. nothing more when no lane of the wave has a passing row of any member;
 //   3. the planes of V that a member with a passing row in the wave needs, loaded ONCE, into the array that is indexed by constants only — and
 //      not at all by a lane without a passing row of any member;
@@ -64,10 +68,19 @@ __global__ __launch_bounds__(BLOCK, 3) void scan_agg_planes_batch_kernel(const V
 #pragma unroll 1
     for (uint32_t k = 0; k < n; ++k) {
       const VhBatchMember& M = Q[k];
-      // (the snapshot lies behind a pointer of the plan: a vector load of a uniform address, made a scalar again so that the branch on it is one)
-      const uint32_t seg_rows = (uint32_t)__builtin_amdgcn_readfirstlane((int)M.P.seg_rows[seg]);
+      const uint32_t of = M.mask_of;      // (plan data by a scalar load: the branch is uniform)
       uint32_t m = 0u;
-      if (base < seg_rows) m = M.D.has_filter ? vh_sliced_mask(M.B, M.F, seg, base, seg_rows, lane) : vh_sliced_tail_mask(row_l, seg_rows);
+      if (of < k) {
+        // An earlier member of the same mask class (vh_batch.h): its word IS this member's, the cut at the snapshot and the 0 of a chunk at
+        // or beyond it included — equal effective rows in every segment are part of the class key, so nothing is checked a second time. The
+        // slot is this thread's own, written earlier in this loop: no barrier. (A position that is not an earlier one evaluates: no slot
+        // is ever read before it is written.)
+        m = s_mask[of][threadIdx.x];
+      } else {
+        // (the snapshot lies behind a pointer of the plan: a vector load of a uniform address, made a scalar again so that the branch on it is one)
+        const uint32_t seg_rows = (uint32_t)__builtin_amdgcn_readfirstlane((int)M.P.seg_rows[seg]);
+        if (base < seg_rows) m = M.D.has_filter ? vh_sliced_mask(M.B, M.F, seg, base, seg_rows, lane) : vh_sliced_tail_mask(row_l, seg_rows);
+      }
       s_mask[k][threadIdx.x] = m;
       vh_member_put(npassed32, k, vh_member_get(npassed32, k) + __popc(m));
       any |= m;

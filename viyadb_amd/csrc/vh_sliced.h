@@ -55,12 +55,15 @@ struct VhPlaneAggRef {
 // Program and descriptor lie IN the member, by value: read through a pointer that was itself loaded from the array, the compiler no longer
 // knows them for unclobbered — it took vector loads and turned every branch of the interpreter, which is on plan data, into a divergent one
 // (952 exec-mask branches against the single kernel's 412; measured 25 % slower than the single queries: profiles/r18/NOTES.md).
+// mask_of: the position in the array of the member whose pass mask this one uses (vh_batch.h, vh_batch_share: the same filter program over the
+// same F against the same effective rows per segment); its own position: it evaluates B over F itself. Never a later position.
 struct VhBatchMember {
   VhPlanDev P;
   VhBitsProg B;                   // (all zeros: no filter — D.has_filter says)
   VhPlaneAggDesc D;
   VhSlicedPlanes F;
-  uint32_t lds_base, pad;         // bytes, a multiple of 16
+  uint32_t lds_base;              // bytes, a multiple of 16
+  uint32_t mask_of;
 };
 
 #if defined(__HIPCC__)

@@ -540,14 +540,24 @@ extern "C" int vh_query_agg(vh_table* t, const vh_plan* plan, vh_result** out) {
 // The scans the members' plans handed over (QueryBuild::launch), enqueued: vh_batch.h forms the groups; a group's members are answered by ONE
 // launch of scan_agg_planes_batch_kernel on the stream of its first member, the lead; a candidate that stays alone gets the launch its plan
 // would have made. Behind either, each member's own tail on its own stream (query_scan_tail). t->mu is held, and so is the batch's tick.
+// Within a group, vh_batch_share (vh_batch.h) says which members take an earlier member's pass mask (VhBatchMember::mask_of); no_share: every
+// member evaluates its own (VH_TEST_NO_BATCH_SHARE).
+static_assert(VH_SHARE_KIND_REL == VH_F_REL && VH_SHARE_KIND_IN == VH_F_IN && VH_SHARE_KIND_INSET == VH_F_INSET, "vh_batch.h restates enum vh_fkind");
+static_assert(sizeof(VhBitsOp) == 8 && offsetof(VhBitsOp, w0) == 0 && offsetof(VhBitsOp, w1) == 4, "vh_batch.h reads an op as two words");
 struct VhBatchGroups { uint32_t n = 0; int32_t of[VH_BATCH_MAX]; uint32_t lead[VH_BATCH_MAX]; };
-static int batch_launch_scans(VhBatchFuse& F, uint32_t n, VhBatchGroups* G, uint32_t* failed) {
+static int batch_launch_scans(VhBatchFuse& F, uint32_t n, VhBatchGroups* G, uint32_t* failed, bool no_share) {
   VhFuseDesc d[VH_BATCH_MAX] = {};
+  VhShareDesc sh[VH_BATCH_MAX] = {};
   for (uint32_t i = 0; i < n; ++i) {
     const VhDeferredScan& s = F.scan[i];
     if (!s.r) continue;
     d[i].candidate = 1; d[i].scope = s.xcd_private ? 1u : 0u; d[i].v_serial = s.v_serial; d[i].nseg = (uint32_t)s.P.nseg; d[i].chunks_per_seg = s.chunks_per_seg;
     d[i].lds_bytes = (uint32_t)((s.lds_table + 15) / 16 * 16);
+    VhShareDesc& h = sh[i];
+    h.has_filter = s.D.has_filter; h.f_serial = s.f_serial;
+    h.f_planes = (uint64_t)(uintptr_t)s.A.F.planes; h.f_stride = s.A.F.stride; h.f_pitch = s.A.F.pitch;
+    h.nprog = s.B.nprog; h.flat = s.B.flat; h.ops = &s.B.op[0].w0; h.lits = s.B.lits; h.nlits = VH_BITS_MAX_LITS;
+    h.nseg = (uint32_t)s.P.nseg; h.seg_rows = s.segrows;
   }
   G->n = vh_batch_group(d, n, G->of);
   for (uint32_t i = 0; i < n; ++i) {      // alone after all: the single query's launch
@@ -569,11 +579,14 @@ static int batch_launch_scans(VhBatchFuse& F, uint32_t n, VhBatchGroups* G, uint
     hipStream_t ls = lx->stream();
     uint32_t lds = 0;
     int grid = 0;
+    uint32_t mask_of[VH_BATCH_MAX], classes = cnt;
+    if (no_share) for (uint32_t k = 0; k < cnt; ++k) mask_of[k] = k;
+    else classes = vh_batch_share(sh, m, cnt, mask_of);
     for (uint32_t k = 0; k < cnt; ++k) {      // the lead's stream behind every member's clears and uploads; the members' array, staged
       const VhDeferredScan& s = F.scan[m[k]];
       if (s.x->stream() != ls) HIP_TRY(hipStreamWaitEvent(ls, s.x->ev[1], 0));
       VhBatchMember& M = lx->h_batch[k];
-      M.P = s.P; M.B = s.B; M.D = s.D; M.F = s.A.F; M.lds_base = lds; M.pad = 0;
+      M.P = s.P; M.B = s.B; M.D = s.D; M.F = s.A.F; M.lds_base = lds; M.mask_of = mask_of[k];
       lds += d[m[k]].lds_bytes;
       grid = std::max(grid, s.grid);
     }
@@ -594,6 +607,7 @@ static int batch_launch_scans(VhBatchFuse& F, uint32_t n, VhBatchGroups* G, uint
       if (s.x->stream() != ls) HIP_TRY(hipStreamWaitEvent(s.x->stream(), lx->ev_batch[1], 0));
       s.r->kernel = nm;
       s.r->info.reserved |= VH_INFO_BATCH_FUSED;
+      s.r->batch_member = vh_batch_member_info{1u, g, k, cnt, mask_of[k], classes};
       if (int rc = query_scan_tail(s.r, s.x)) return rc;
     }
   }
@@ -612,6 +626,8 @@ extern "C" int vh_query_agg_batch(vh_table* t, const vh_plan* const* plans, uint
   VH_ENTER();
   const char* const nf = test_env("VH_TEST_NO_BATCH_FUSE");      // tests, probe: every member answered singly (an A/B inside one process)
   const bool no_fuse = nf && atoi(nf) != 0;
+  const char* const ns = test_env("VH_TEST_NO_BATCH_SHARE");     // tests, probe: every fused member evaluates its own pass mask (the fused launch without sharing)
+  const bool no_share = ns && atoi(ns) != 0;
   VhExec* xs[VH_BATCH_MAX] = {};          // a member's context while no result owns it
   vh_result* rs[VH_BATCH_MAX] = {};       // a member's launched attempt (it owns the context)
   bool wide[VH_BATCH_MAX] = {};           // more metrics than one pass carries: vh_query_agg's passes, behind the others
@@ -656,7 +672,7 @@ extern "C" int vh_query_agg_batch(vh_table* t, const vh_plan* const* plans, uint
         if (rc) { rs[i] = nullptr; break; }
         rs[i]->exec = xs[i];
       }
-      if (!rc) rc = batch_launch_scans(*fuse, n, &G, &failed);
+      if (!rc) rc = batch_launch_scans(*fuse, n, &G, &failed, no_share);
     }
     evicted = t->layout_budget != 0 && g_plan_evicted;
   }

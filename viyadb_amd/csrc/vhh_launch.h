@@ -1000,6 +1000,7 @@ int QueryBuild::launch() {
     // follows it are the batch's to launch, once it knows the groups. The plan goes by value: it is complete here.
     VhDeferredScan& d = o.fuse->scan[o.fuse->member];
     d.r = r; d.x = x; d.P = P; d.A = pagg_ref; d.B = pagg_filter ? planes_prog : VhBitsProg{}; d.D = pagg_desc; d.grid = grid; d.lds_table = lds_table; d.xcd_private = nxcd > 1; d.v_serial = pagg_v->serial;
+    d.f_serial = (pagg_filter ? sliced_use : pagg_v)->serial; d.segrows = x->h_segrows;
     d.chunks_per_seg = (uint32_t)std::max<uint64_t>(1, (t->padded_rows + VH_SLICED_CHUNK_ROWS - 1) / VH_SLICED_CHUNK_ROWS);
     *out = holder.release();
     done = true;

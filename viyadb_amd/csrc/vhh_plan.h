@@ -209,6 +209,8 @@ struct VhDeferredScan {
   VhPlaneAggDesc D{};         // ... and the descriptor behind A.D
   int grid = 0; size_t lds_table = 0;
   bool xcd_private = false; uint32_t chunks_per_seg = 0; uint64_t v_serial = 0;
+  uint64_t f_serial = 0;      // the projection F the program reads (V's where there is no filter): part of the mask key (vh_batch.h)
+  const uint32_t* segrows = nullptr;      // the effective rows per segment as staged (x->h_segrows[0 .. P.nseg): the context is the member's own until its result is freed)
 };
 struct VhBatchFuse { VhDeferredScan scan[VH_BATCH_MAX]; uint32_t member = 0; };      // member: the one being planned
 // ... and how query_launch_locked is asked for a plan, beyond table, context and the plan itself: every caller names the members it sets.

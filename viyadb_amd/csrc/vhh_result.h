@@ -114,6 +114,7 @@ struct vh_result {
   bool small_tail = false;             // a small dense result that goes straight into pinned host memory: merge + emission + header are ONE launch (small_tail_kernel)
   bool unmerged = false;               // ... which also adds the private copies up: until then (or until merge_copies_now, in front of a cross-GPU reduce) nobody has
   vh_tail_info tail{};                 // which kernels ended the query (vh_result_tail): filled by result_finalize, `merged` by whoever adds the copies up
+  vh_batch_member_info batch_member{}; // its place in a fused launch of a batch (vh_result_batch_member): filled by batch_launch_scans, zeros otherwise
   std::vector<int> metric_elem;        // output element type per device metric (P.m order)
   std::vector<int> group_elem;
   std::string group_sig;
@@ -170,6 +171,12 @@ extern "C" const char* vh_result_kernel(vh_result* r) { return r ? r->kernel.c_s
 extern "C" int vh_result_tail(vh_result* r, vh_tail_info* out) {
   if (!r || !out) return vh_fail(VH_E_INVALID, "null argument");
   *out = r->tail;
+  return VH_OK;
+}
+
+extern "C" int vh_result_batch_member(vh_result* r, vh_batch_member_info* out) {
+  if (!r || !out) return vh_fail(VH_E_INVALID, "null argument");
+  *out = r->batch_member;
   return VH_OK;
 }
 

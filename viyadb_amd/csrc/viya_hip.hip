@@ -69,7 +69,10 @@ static std::mutex g_mu;
 // queries of one process — and go through test_env(): one gate (VH_TEST_HOOKS, read once; tests/conftest.py sets it) in front of them, so
 // that a serving process never walks its environment on the query path. Among them: VH_TEST_PLACE_CANDIDATES / VH_TEST_PLACE_VERDICT /
 // VH_TEST_PLACE_WAIT_SYNC make vh_table_prepare's placement of the derived layouts deterministic (vhh_finalize.h, place_layouts), and
-// VH_TEST_JOURNAL_CAP replaces the 2^18 entries at which the table's journal drops its older half (vhh_table.h, table_note_change).
+// VH_TEST_JOURNAL_CAP replaces the 2^18 entries at which the table's journal drops its older half (vhh_table.h, table_note_change);
+// VH_TEST_NO_BATCH_FUSE=1 makes vh_query_agg_batch answer every member singly, and VH_TEST_NO_BATCH_SHARE=1 keeps its fused launches but
+// has every member evaluate its own pass mask (mask_of = its own position: the fused launch without sharing) — both read per call, the
+// A/B of tools/batch_probe.py inside one process (vhh_finalize.h).
 static const char* test_env(const char* name) {
   static const bool hooks = getenv("VH_TEST_HOOKS") != nullptr;
   return hooks ? getenv(name) : nullptr;

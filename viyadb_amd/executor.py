@@ -108,6 +108,13 @@ class AggResult:
         return getattr(self, "_tail", None)
 
     @property
+    def batch_member(self):
+        """capi.BatchMemberInfo: the result's place in a fused launch of a batch and whose pass mask it used (vh_result_batch_member) —
+        fused, launch, position, members, mask_of, mask_classes; all zeros outside a fused launch. Set by query_agg and query_agg_batch; no
+        field of its own (None for a record built by hand)."""
+        return getattr(self, "_batch_member", None)
+
+    @property
     def plane_agg(self) -> bool:
         """The aggregate was computed on the bit-sliced planes (PLAN2_PLANE_AGG / VH_PLANE_AGG=1): derived from `flags`, no field of its own."""
         return bool(self.flags & capi.INFO_PLANE_AGG)
@@ -467,6 +474,9 @@ class DeviceTable:
                         kernel=(self.lib.vh_result_kernel(res) or b"").decode(), flags=flags, pack_rec_bytes=capi.info_rec_bytes(flags),
                         **info_fields(flags))
         out._tail = tail
+        member = capi.BatchMemberInfo()
+        capi.check(self.lib.vh_result_batch_member(res, C.byref(member)))
+        out._batch_member = member
         return out
 
     def query_agg(self, plan: AggPlan, copy: bool = True) -> AggResult:
@@ -481,7 +491,8 @@ class DeviceTable:
     def query_agg_batch(self, plans: Sequence[AggPlan], copy: bool = True) -> Tuple[List[AggResult], capi.BatchInfo]:
         """Up to capi.BATCH_MAX aggregates in one call (vh_query_agg_batch): results in plan order, each equal to query_agg's of the same
         plan, and how the batch was answered. Members that take the aggregate on the bit-sliced planes share fused launches
-        (AggResult.batch_fused). All or nothing: a failing member fails the call."""
+        (AggResult.batch_fused), and members of a launch with the same filter and snapshot share one evaluation of its pass mask
+        (AggResult.batch_member: launch, position, mask_of, mask_classes). All or nothing: a failing member fails the call."""
         n = len(plans)
         built = [self._build_plan(p) for p in plans]
         ptrs = (C.POINTER(capi.Plan) * max(1, n))(*[C.pointer(b[0]) for b in built])
