@@ -7,12 +7,10 @@ agree bit for bit; and `grouped_planes` (vh_result_info.reserved bit 21) must be
 import numpy as np
 import pytest
 
-from oracle import viya_oracle as vo
 from tests.conftest import JIT_OFF
-from tests.parity import compare, sort_rows
+from tests.cluster_shapes import ask, four_forms, same_bits          # noqa: F401 (other modules take them from here)
 from tests.test_gpu_layout_lifecycle import C3Host, D2
 from viyadb_amd import capi
-from viyadb_amd.executor import AggPlan
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(JIT_OFF, reason="clustered planes are read by the compiled scan only")]
 PART, JIT, PACK = 64, capi.PLAN_FORCE_JIT, capi.PLAN_FORCE_PACK
@@ -36,37 +34,6 @@ def REL(col, op, name, v):
 
 D3_LT, D4_GE = REL(3, capi.OP_LT, "lt", 447), REL(4, capi.OP_GE, "ge", 553)
 C3 = [EQ(D2, 1), D3_LT, D4_GE]
-
-
-def ask(h, leaves, flags, seg_rows=None, label=""):
-    filt = [l[0] for l in leaves] + [("and", len(leaves))]
-    q = dict(h.w.query, filter={"op": "and", "filters": [l[1] for l in leaves]})
-    p = h.w.plan
-    res = h.dt.query_agg(AggPlan(filter=filt, groups=p.groups, metrics=p.metrics, flags=flags, groups_hint=p.groups_hint, seg_rows=seg_rows))
-    compare(res, vo.scan_aggregate(vo.parse_query(h.tab, q), seg_rows=seg_rows), f"{label} flags={flags:#x} snapshot={seg_rows}")
-    return res
-
-
-def same_bits(a, b, label):
-    pa, pb = sort_rows(a.keys, a.states), sort_rows(b.keys, b.states)
-    assert a.passed_recs == b.passed_recs, label
-    for x, y in zip(a.keys + a.states, b.keys + b.states):
-        assert x.dtype == y.dtype and x.dtype.kind in "iu" and np.array_equal(x[pa], y[pb]), label
-
-
-def four_forms(h, leaves, seg_rows=None, label="", planes=True, grouped=True):
-    c = ask(h, leaves, HOT, seg_rows, label + " clustered")
-    assert c.jit and c.sliced and c.packed and c.pack_bits and c.pack_rec_bytes == 4, (label, hex(c.flags), c.kernel)
-    assert c.grouped_payload == grouped and c.grouped_planes == (planes and grouped), (label, hex(c.flags))
-    g = ask(h, leaves, HOT | capi.PLAN_NO_GPLANES, seg_rows, label + " row-order planes")
-    assert g.grouped_payload == grouped and not g.grouped_planes, (label, hex(g.flags))
-    r = ask(h, leaves, HOT | capi.PLAN_NO_GROUPED, seg_rows, label + " row-order records")
-    assert r.packed and r.sliced and not r.grouped_payload and not r.grouped_planes, (label, hex(r.flags))
-    a = ask(h, leaves, PART | JIT | capi.PLAN_NO_PACK, seg_rows, label + " arenas")
-    assert not a.packed and not a.grouped_payload and not a.grouped_planes, (label, hex(a.flags))
-    for other, name in ((g, "row-order planes"), (r, "row-order records"), (a, "the arenas")):
-        same_bits(c, other, f"{label}: clustered planes against {name}")
-    return c
 
 
 @pytest.fixture

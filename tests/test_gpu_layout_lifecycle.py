@@ -48,6 +48,7 @@ class C3Host:
 
     def __init__(self, nseg, rows, cap, reserve=None, seed=42):
         self.w = synth.c3(segment_rows=cap)
+        self.query, self.base = self.w.query, self.w.plan          # (what tests/cluster_shapes.py's comparisons take from a host)
         self.cap, self.seed = cap, seed
         self.tab = build_oracle_table(self.w, nseg, cap, seed=seed)
         for seg in self.tab.segments:

@@ -7,13 +7,11 @@ the planner's rule says."""
 import numpy as np
 import pytest
 
-from oracle import viya_oracle as vo
 from tests.conftest import JIT_OFF
-from tests.parity import compare
+from tests.cluster_shapes import ask, twins
 from tests.test_gpu_gplanes import C3, D3_LT, D4_GE, EQ, HOT, REL, ROWS, CAP, TILE, same_bits
 from tests.test_gpu_layout_lifecycle import C3Host, D2, D3
 from viyadb_amd import capi
-from viyadb_amd.executor import AggPlan
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(JIT_OFF, reason="a sub-sorted form is read by the compiled scan only")]
 FIELD_MAX = 1023          # d3 holds 0 .. 999: a field of 10 bits
@@ -32,27 +30,6 @@ def host(monkeypatch):
     h = C3Host(3, ROWS, CAP)
     yield h
     h.close()
-
-
-def ask(h, leaves, flags, seg_rows=None, label="", node="and"):
-    filt = [l[0] for l in leaves] + [(node, len(leaves))]
-    q = dict(h.w.query, filter={"op": node, "filters": [l[1] for l in leaves]})
-    p = h.w.plan
-    res = h.dt.query_agg(AggPlan(filter=filt, groups=p.groups, metrics=p.metrics, flags=flags, groups_hint=p.groups_hint, seg_rows=seg_rows))
-    compare(res, vo.scan_aggregate(vo.parse_query(h.tab, q), seg_rows=seg_rows), f"{label} flags={flags:#x} snapshot={seg_rows}")
-    return res
-
-
-def twins(h, leaves, seg_rows=None, label="", trim=True, grouped=True, node="and"):
-    """The query on the sub-sorted form and its VH_PLAN_NO_GROUPED twin: both against the oracle, bit for bit against each other, bit 28."""
-    c = ask(h, leaves, HOT, seg_rows, label + " sub-sorted", node)
-    assert c.jit and c.packed and c.pack_bits and c.pack_rec_bytes == 4, (label, hex(c.flags), c.kernel)
-    assert c.grouped_payload == grouped and c.grouped_planes == grouped and c.sub_trimmed == (grouped and trim), (label, hex(c.flags))
-    assert bool(c.flags & capi.INFO_SUBTRIM) == c.sub_trimmed
-    r = ask(h, leaves, HOT | capi.PLAN_NO_GROUPED, seg_rows, label + " row order", node)
-    assert not r.grouped_payload and not r.grouped_planes and not r.sub_trimmed, (label, hex(r.flags))
-    same_bits(c, r, label)
-    return c
 
 
 def warm(h, trim=True):

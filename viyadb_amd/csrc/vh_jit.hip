@@ -887,6 +887,18 @@ static bool vj_canonical(int which, VhJitShape* s) {
     S.gp_span = 1;
     return true;
   }
+  if (which >= 35 && which <= 37) {      // ... at other geometries than C3's (tests/cluster_shapes.py): the fields of the == leaf's, the < leaf's (sub) and the >= leaf's column
+    if (!vj_canonical(34, s)) return false;
+    struct Geo { int type[3], off[3], bits[3], G; };
+    static const Geo geo[3] = {
+        {{VH_U8, VH_U16, VH_U32}, {7, 10, 0}, {3, 11, 7}, 20},        // 35 "middle": a 3-bit grouping field between 7 and 11 bits, 18 planes in 20 dwords
+        {{VH_U64, VH_U32, VH_U16}, {28, 0, 16}, {4, 16, 12}, 28},     // 36 "top": a 4-bit grouping field at the top of 32 planes, a 16-bit sub field, whole 16-byte loads
+        {{VH_U8, VH_U32, VH_U16}, {0, 16, 1}, {1, 16, 15}, 32}};      // 37 "wide": a 1-bit grouping field below 31 planes in 32 dwords, the sub field at 15
+    const Geo& g = geo[which - 35];
+    for (int k = 0; k < 3; ++k) { S.pred[k].type = g.type[k]; S.prog[(size_t)k].set_type((uint8_t)g.type[k]); S.pp_off[k] = g.off[k]; S.pp_bits[k] = g.bits[k]; }
+    S.gp_G = g.G; S.gp_goff = g.off[0];
+    return true;
+  }
   switch (which) { case 25: which = 22; depth = 1; break; case 26: which = 22; depth = 2; break; case 27: which = 21; depth = -2; break; case 28: which = 7; depth = -2; break; case 29: which = 1; depth = -2; break; default: break; }
   if (depth != -1) {
     if (!vj_canonical(which, s)) return false;
