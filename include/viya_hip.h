@@ -236,10 +236,15 @@ enum vh_plan_flags {
 };
 /* vh_plan.flags2: all 32 bits of `flags` are taken. */
 enum vh_plan_flags2 {
-  VH_PLAN2_PLANE_AGG = 1u << 0    /* opt-in: an aggregate of few groups that no compiled kernel answers is computed ON the bit-sliced planes —
+  VH_PLAN2_PLANE_AGG = 1u << 0,   /* opt-in: an aggregate of few groups that no compiled kernel answers is computed ON the bit-sliced planes —
                                      sums and min / max by popcount, no row materialised (scan_agg_planes_kernel; the rule: "Aggregates on
                                      the bit-sliced planes" below; VH_PLANE_AGG=1 in the environment sets it for every aggregate of the
                                      process that is not a vh_query_agg_sharded call) */
+  VH_PLAN2_PLANE_ROWS = 1u << 1   /* opt-in: asks for the aggregate on the planes exactly as VH_PLAN2_PLANE_AGG does and lifts its bound of 64
+                                     group ids — a plan of more ids that meets every other condition of the rule takes the path with the ROW
+                                     SINK: every surviving row's record is rebuilt from the plane words in registers and updates the LDS
+                                     table once per metric (scan_agg_planes_rows_kernel). Up to 64 ids the loop over ids runs as without
+                                     it. No environment variable sets it; sharded calls ignore it. vh_result_plane_sink tells */
 };
 typedef struct vh_plan {
   const vh_filter_node* filter; int32_t nfilter;   /* postfix program        */
@@ -574,7 +579,10 @@ VH_API int vh_query_agg(vh_table* t, const vh_plan* plan, vh_result** out);
  * results nor its scan_kernel_ms, which stays the launch's; vh_result_batch_member says whose mask a member used. A fused result has
  * vh_result_info.reserved bit 30 set beside bit 27's, vh_result_kernel names
  * scan_agg_planes_batch_kernel<256, S>, and its scan_kernel_ms is the FUSED launch's time, the same for every member of the group (so the
- * members' values must not be added up; vh_batch_info.fused_kernel_ms is the sum over the launches). A group of one, and every member that
+ * members' values must not be added up; vh_batch_info.fused_kernel_ms is the sum over the launches). A member that takes the row sink
+ * (VH_PLAN2_PLANE_ROWS and more than 64 ids) is a candidate like any other, shares or lends a mask like any other, and the 48 KB bound
+ * on the tables is what limits it; a launch with such a member is named scan_agg_planes_batch_kernel<256, S, rows> and runs the row sink
+ * for it and the loop for the others. A group of one, and every member that
  * is no candidate, runs as the single query it is: the flags and the kernel name its vh_query_agg would give, bit 30 clear. A fused member
  * that has to be planned again (a value synced in beyond the planned range) is answered alone by vh_query_agg's re-plan loop; the others stand.
  *
@@ -749,7 +757,10 @@ VH_API int vh_query_agg_sharded(vh_table* t, const vh_plan* plan, vh_comm* comm,
  *    vh_query_agg_sharded call (sharded queries ignore the switch);
  *  - no compiled kernel runs the query (the cases listed for VH_PLAN_SLICED_PREBUILT above);
  *  - the organisation is the dense LDS table (VH_PATH_DENSE_LDS, VH_PATH_SCALAR) with at most 64 group ids: the loop over the ids is paid
- *    per plane word, so this bounds the design, it is not a tuned figure;
+ *    per plane word, so this bounds the design, it is not a tuned figure. VH_PLAN2_PLANE_ROWS lifts that bound for the plan that carries it
+ *    (VH_PLANE_AGG=1 alone keeps it): any number of ids the dense LDS table holds. From 65 ids on the ROW SINK stands in for the loop — the
+ *    wave compacts its surviving rows, rebuilds each one's record from the plane words already in registers (no queue of row numbers, no
+ *    gather from memory) and updates the table once per row and metric, as the scans over rows do; up to 64 ids the loop runs as before;
  *  - the filter is empty, or satisfies the select's conditions above on ONE usable bit-sliced projection F (every leaf's column a field, the
  *    inline budget, set leaves on fields of at most 10 bits); none of VH_PLAN_NO_SLICED / VH_PLAN_NO_PREDPACK / VH_PLAN_NO_NARROW is set;
  *  - ONE usable, current bit-sliced projection V holds every group column and every metric's source column, the hidden count included
@@ -760,7 +771,9 @@ VH_API int vh_query_agg_sharded(vh_table* t, const vh_plan* plan, vh_comm* comm,
  * Whether the plan had settled on the no-compaction (lanes) form plays no part. When both this and VH_PLAN_SLICED_PREBUILT apply, this wins.
  * It changes which kernel fills the same LDS table and nothing else: organisation, states (a u32 sum wraps as before), HAVING, top-N and
  * delivery are those of the same plan without the switch. The query stamps F and V (vh_layout_info.uses) and holds them against eviction
- * while it runs; it builds and queues no layout. vh_result_info.reserved bit 27 tells. */
+ * while it runs; it builds and queues no layout. vh_result_info.reserved bit 27 tells, whichever sink ran; vh_result_plane_sink tells
+ * the sink: 0 the result is no aggregate on the planes, 1 the loop over ids, 2 the row sink. */
+VH_API int vh_result_plane_sink(vh_result* r, uint32_t* sink);   /* VH_E_INVALID: a null argument */
 #define VH_COL_ROWID (-2)
 typedef struct vh_rows vh_rows;
 typedef struct vh_select_plan {

@@ -39,6 +39,7 @@ PLAN_NO_GPLANES = 1 << 29
 PLAN_SET_SEARCH = 1 << 30         # testing: every set of an F_INSET leaf takes the sorted-array form
 PLAN_SLICED_PREBUILT = 1 << 31    # opt-in: an aggregate no compiled kernel answers reads its filter off the bit-sliced planes (scan_agg_sliced_kernel)
 PLAN2_PLANE_AGG = 1 << 0          # vh_plan.flags2 (enum vh_plan_flags2). Opt-in: an aggregate of few groups is computed on the bit-sliced planes (scan_agg_planes_kernel)
+PLAN2_PLANE_ROWS = 1 << 1         # ... the same, without the bound of 64 group ids: beyond it the row sink fills the table (scan_agg_planes_rows_kernel; vh_result_plane_sink)
 # paths
 PATH_SCALAR, PATH_DENSE_LDS, PATH_DENSE_GLOBAL, PATH_HASH, PATH_DENSE_PART = range(5)
 PATH_NAMES = ["scalar", "dense_lds", "dense_global", "hash", "dense_part"]
@@ -302,6 +303,7 @@ SYMBOLS = {
     "vh_result_kernel": (C.c_char_p, [_VP]),
     "vh_result_tail": (C.c_int, [_VP, C.POINTER(TailInfo)]),
     "vh_result_batch_member": (C.c_int, [_VP, C.POINTER(BatchMemberInfo)]),
+    "vh_result_plane_sink": (C.c_int, [_VP, C.POINTER(C.c_uint32)]),
     "vh_result_state_elem": (C.c_int, [_VP, C.c_int32]),
     "vh_result_copy": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(C.c_uint64)]),
     "vh_result_view": (C.c_int, [_VP, C.POINTER(_VP), C.POINTER(_VP), C.POINTER(C.POINTER(C.c_uint64))]),

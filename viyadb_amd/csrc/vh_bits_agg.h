@@ -1,5 +1,6 @@
 // vh_bits_agg.h — aggregates computed ON the bit-sliced predicate planes (VhPredPack::sliced), 32 rows per call: the sum, the smallest and the
-// largest value of a field over the rows of a mask, and the rows that belong to one group. Plain C++ for host and device, like
+// largest value of a field over the rows of a mask, the rows that belong to one group, and — the other way round, for the row sink — one
+// row's record and group id out of the plane words. Plain C++ for host and device, like
 // vh_bits_eval.h, whose layout of the planes it shares: the aggregate scan on the planes includes it (vh_scan_planes.hip), and a
 // host-compiled check holds it against a per-row evaluation (tests/bits_agg_host.cc). No row is materialised and nothing here is floating point.
 //
@@ -76,4 +77,40 @@ VH_BITS_FN uint32_t vh_bits_match(const uint32_t (&v)[VH_BITS_MAX_FIELD], uint32
     eq &= ((pat >> p) & 1u) ? v[p] : ~v[p];
   }
   return eq;
+}
+
+// ---- one row back out of the planes: what the row sink of the aggregate on the planes (vh_plane_agg.h: vh_plane_agg_rows) computes per
+// surviving row, where the loop over group ids computes per id.
+// Bit p of a row's RECORD is the row's bit of plane p: the record is the row word the planes were sliced from, over the planes of `need`.
+// vh_bits_row_bit is one plane's share of it — the kernel fetches the word from the row's source lane plane by plane and ORs the shares —,
+// vh_bits_row the whole record of row r out of one lane's own plane words.
+VH_BITS_FN uint32_t vh_bits_row_bit(uint32_t word, uint32_t r, uint32_t p) { return ((word >> (r & 31u)) & 1u) << p; }
+VH_BITS_FN uint32_t vh_bits_row(const uint32_t (&v)[VH_BITS_MAX_FIELD], uint32_t need, uint32_t r) {
+  uint32_t rec = 0u;
+  VH_BITS_UNROLL
+  for (int p = 0; p < VH_BITS_MAX_FIELD; ++p) {
+    if (!((need >> p) & 1u)) continue;
+    rec |= vh_bits_row_bit(v[p], r, (uint32_t)p);
+  }
+  return rec;
+}
+// A field's value out of a record: nb <= 32 planes from plane off on.
+VH_BITS_FN uint32_t vh_bits_row_field(uint32_t rec, uint32_t off, uint32_t nb) {
+  return nb == 0u ? 0u : (rec >> off) & (nb >= 32u ? ~0u : (1u << nb) - 1u);
+}
+// The dense group id of a record: per group column i, digit_i = field_i - g[i].lo, and gid = Σ digit_i * g[i].stride (VhGroupDev: any type
+// with lo, extent and stride serves; goff / gbits: the columns' fields, VhPlaneAggDesc). false: a field below lo, or a digit at or beyond
+// extent — the row belongs to no id (a value outside the planned range), *gid is not to be used.
+template <class GROUP>
+VH_BITS_FN bool vh_bits_row_gid(uint32_t rec, int ngroup, const GROUP* g, const uint32_t* goff, const uint32_t* gbits, uint64_t* gid) {
+  uint64_t id = 0;
+  bool ok = true;
+  for (int i = 0; i < ngroup; ++i) {
+    const uint64_t field = vh_bits_row_field(rec, goff[i], gbits[i]);
+    const uint64_t digit = field - g[i].lo;
+    ok = ok && field >= g[i].lo && digit < g[i].extent;
+    id += digit * g[i].stride;
+  }
+  *gid = id;
+  return ok;
 }

@@ -43,12 +43,14 @@ struct VhSlicedRef;
 // the pre-built scan over the bit-sliced predicate planes (vh_sliced.h), whatever the organisation: `mode` picks the sink
 void vh_launch_scan_sliced(int mode, const VhPlanDev& P, const VhSlicedRef& A, uint32_t chunks_per_seg, const VhScanLaunch& L, bool xcd_private);
 struct VhPlaneAggRef;
-// the aggregate scan ON the bit-sliced planes (vh_sliced.h): DENSE_LDS plans of at most VH_PLANE_AGG_MAX_GROUPS ids, sums and min / max by popcount
+// the aggregate scan ON the bit-sliced planes (vh_sliced.h): DENSE_LDS plans of at most VH_PLANE_AGG_MAX_GROUPS ids, sums and min / max by popcount;
+// A.rows: the row sink's instantiation, for plans of more ids (one LDS update per surviving row and metric, from the plane words in registers)
 void vh_launch_scan_planes(const VhPlanDev& P, const VhPlaneAggRef& A, uint32_t chunks_per_seg, const VhScanLaunch& L, bool xcd_private);
 struct VhBatchMember;
 struct VhSlicedPlanes;
-// ... for the `n` members of a fused batch at once (vh_sliced.h, vh_batch.h): one walk, one load of V; L.lds = the members' LDS tables together
-void vh_launch_scan_planes_batch(const VhBatchMember* d_members, uint32_t n, const VhSlicedPlanes& V, uint32_t chunks_per_seg, const VhScanLaunch& L, bool xcd_private);
+// ... for the `n` members of a fused batch at once (vh_sliced.h, vh_batch.h): one walk, one load of V; L.lds = the members' LDS tables together;
+// rows: some member is a row member (VhPlaneAggDesc::rows) — the instantiation that carries the row sink beside the loop
+void vh_launch_scan_planes_batch(const VhBatchMember* d_members, uint32_t n, const VhSlicedPlanes& V, uint32_t chunks_per_seg, const VhScanLaunch& L, bool xcd_private, bool rows);
 
 // The tails of DENSE_PART behind the scan, and beside each launcher the symbol of the kernel it runs (for vh_result_kernel).
 void vh_launch_part_agg(const VhPlanDev& P, int blocks_per_part, size_t lds, hipStream_t s);

@@ -1,6 +1,8 @@
 // vh_plane_agg.h — what the two aggregate scans ON the bit-sliced planes share on the device: scan_agg_planes_kernel (vh_scan_planes.hip, one
 // query) and scan_agg_planes_batch_kernel (vh_scan_planes_batch.hip, the members of a fused batch). One plane word of V, already in registers,
-// and one query's pass mask in; that query's updates of its block's LDS table out.
+// and one query's pass mask in; that query's updates of its block's LDS table out. Two sinks with that contract: the loop over group ids
+// (vh_plane_agg_groups: one LDS update per chunk, id and metric; at most VH_PLANE_AGG_MAX_GROUPS ids) and the row sink (vh_plane_agg_rows: one
+// per surviving row and metric; any number of ids the table holds).
 #pragma once
 #include "vh_kernels.h"
 #include "vh_sliced.h"
@@ -42,5 +44,66 @@ __device__ __forceinline__ bool vh_plane_agg_groups(const VhPlanDev& P, const Vh
     if (lane == 63) reinterpret_cast<uint8_t*>(lds + P.lds_present_off)[g] = 1;
   }
   return (mask & ~seen) != 0u;
+}
+
+// The ROW SINK: the same contract as vh_plane_agg_groups — a lane's plane words of V and its pass mask in, the plan's updates of its LDS table
+// out, whether a passing row of the lane belonged to no id returned — for plans of more ids than a loop over them can pay for. It turns
+// every surviving row back into its record, from the plane words in registers: no queue of row numbers, no gather from memory.
+//   COMPACT. The mask is taken in VH_PLANE_ROWS_SLICES slices of VH_PLANE_ROWS_SLICE_BITS bits per lane. Per slice a lane has popc survivors;
+//   an exclusive wave prefix of those (the DPP scans of vh_wave_scan.h) is where it writes one entry `lane << 5 | bit` per set bit into the
+//   wave's queue q (VH_PLANE_ROWS_QUEUE entries of 16 bits in static LDS): the queue holds the slice's survivors by lane, then by bit.
+//   DRAIN, in groups of 64: lane l takes survivor i = 64 b + l, entry (s, r), and fetches lane s's word of every plane of `need` with
+//   ds_bpermute; bit r of that word is bit p of the record (vh_bits_agg.h: vh_bits_row_bit). The loop over p is unrolled, under the uniform
+//   `need` bit, so v[] is indexed by constants only. ALL 64 lanes execute every bpermute — the trip count is the wave's, a lane with
+//   i >= total fetches from itself and updates nothing —: a source lane that exec switches off supplies no defined data.
+//   Per record: the group id (vh_bits_row_gid; a field outside [lo, lo + extent) skips the row and sets the return value), per metric one
+//   vh_state_update with its field's value — wrapping is vh_state_update's, as in the loop — and the presence byte, as vh_consume does.
+// Like the loop, the caller must be in uniform control flow: the scans and the bpermutes need all 64 lanes.
+#define VH_PLANE_ROWS_SLICE_BITS 8
+#define VH_PLANE_ROWS_SLICES (32 / VH_PLANE_ROWS_SLICE_BITS)
+#define VH_PLANE_ROWS_QUEUE (64 * VH_PLANE_ROWS_SLICE_BITS)      // 512 entries of 2 bytes: 1 KB per wave
+__device__ __forceinline__ bool vh_plane_agg_rows(const VhPlanDev& P, const VhPlaneAggDesc* __restrict__ D, char* lds, const uint32_t (&v)[VH_BITS_MAX_FIELD],
+                                                  uint32_t mask, int lane, uint16_t* q) {
+  const uint32_t need = D->need;
+  bool range_err = false;
+#pragma unroll 1
+  for (int k = 0; k < VH_PLANE_ROWS_SLICES; ++k) {
+    uint32_t mk = (mask >> (VH_PLANE_ROWS_SLICE_BITS * k)) & ((1u << VH_PLANE_ROWS_SLICE_BITS) - 1u);
+    const uint32_t mine = (uint32_t)__popc(mk);
+    const uint32_t incl = vh_wave_incl_add(mine);
+    const uint32_t total = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);      // (<= VH_PLANE_ROWS_QUEUE: SLICE_BITS survivors a lane)
+    if (total == 0u) continue;
+    uint32_t at = incl - mine;
+    while (mk) {
+      const uint32_t bit = (uint32_t)__builtin_ctz(mk);
+      mk &= mk - 1u;
+      q[at++] = (uint16_t)((uint32_t)lane << 5 | (uint32_t)(VH_PLANE_ROWS_SLICE_BITS * k) + bit);
+    }
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+    for (uint32_t i0 = 0; i0 < total; i0 += 64u) {
+      const bool act = i0 + (uint32_t)lane < total;
+      const uint32_t e = act ? (uint32_t)q[i0 + (uint32_t)lane] : (uint32_t)lane << 5;
+      const uint32_t s = e >> 5, r = e & 31u;
+      uint32_t rec = 0u;
+#pragma unroll
+      for (int p = 0; p < VH_BITS_MAX_FIELD; ++p)
+        if ((need >> p) & 1u) rec |= vh_bits_row_bit((uint32_t)__builtin_amdgcn_ds_bpermute((int)(s << 2), (int)v[p]), r, (uint32_t)p);
+      uint64_t gid = 0;
+      const bool in = vh_bits_row_gid(rec, P.ngroup, P.g, D->goff, D->gbits, &gid);
+      range_err |= act && !in;
+      if (act && in) {
+#pragma unroll 1
+        for (int j = 0; j < P.nmetric; ++j) {
+          const VhMetricDev& m = P.m[j];
+          vh_state_update<__HIP_MEMORY_SCOPE_WORKGROUP>(lds + m.lds_off, gid, (int)m.sop(), (uint64_t)vh_bits_row_field(rec, D->moff[j], D->mbits[j]));
+        }
+        reinterpret_cast<uint8_t*>(lds + P.lds_present_off)[gid] = 1;
+      }
+    }
+    __builtin_amdgcn_wave_barrier();      // (the next slice writes the queue this one read)
+  }
+  // the lane that drained a row is not the lane that owns it: every lane of the wave answers for the wave's rows
+  return __ballot(range_err) != 0ull;
 }
 #endif

@@ -25,7 +25,10 @@ static_assert(VH_PLANE_AGG_MAX_GROUPS <= 64, "VhPlaneAggDesc::valid has a bit pe
 // the block's LDS table by ONE lane: one LDS update per (chunk, group, metric) in place of one per row and metric.
 // A passing row that belongs to no id (a value outside the planned range, synced in since) raises VH_ERR_RANGE as vh_consume does: the
 // host plans again.
-template <int BLOCK, int SCOPE>
+// ROWS = 1: the ROW SINK stands in for the loop over ids (vh_plane_agg.h: vh_plane_agg_rows) — plans of more than VH_PLANE_AGG_MAX_GROUPS ids,
+// which the loop cannot pay for. Walk, mask, loads and the end of the block are the same text; the sink's per-wave queue is static LDS of
+// that instantiation alone.
+template <int BLOCK, int SCOPE, int ROWS>
 __global__ __launch_bounds__(BLOCK) void scan_agg_planes_kernel(const VhPlanDev P, const VhBitsProg* __restrict__ B, const VhPlaneAggDesc* __restrict__ D,
                                                                 const VhSlicedPlanes F, const VhSlicedPlanes V, uint32_t chunks_per_seg) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -35,7 +38,12 @@ __global__ __launch_bounds__(BLOCK) void scan_agg_planes_kernel(const VhPlanDev 
 
   const uint32_t need = D->need, care = D->care, has_filter = D->has_filter;
   const uint64_t valid = D->valid;
-  const uint32_t G = (uint32_t)P.G;                    // <= VH_PLANE_AGG_MAX_GROUPS
+  const uint32_t G = (uint32_t)P.G;                    // <= VH_PLANE_AGG_MAX_GROUPS (ROWS = 0)
+  uint16_t* q = nullptr;
+  if constexpr (ROWS) {
+    __shared__ uint16_t s_rowq[BLOCK / 64][VH_PLANE_ROWS_QUEUE];
+    q = s_rowq[wave];
+  }
   uint32_t npassed32 = 0;                              // per lane: 32 rows of every chunk this wave takes
   bool range_err = false;
 
@@ -60,7 +68,8 @@ __global__ __launch_bounds__(BLOCK) void scan_agg_planes_kernel(const VhPlanDev 
         if ((need >> p) & 1u) v[p] = VH_BITS_LOAD(planes + (uint64_t)p * V.pitch + woff);
     }
 
-    range_err |= vh_plane_agg_groups(P, D, care, valid, G, lds, v, mask, lane);      // (vh_plane_agg.h: the loop over the group ids, shared with the batch kernel)
+    if constexpr (ROWS) range_err |= vh_plane_agg_rows(P, D, lds, v, mask, lane, q);      // (vh_plane_agg.h: one LDS update per surviving row and metric)
+    else range_err |= vh_plane_agg_groups(P, D, care, valid, G, lds, v, mask, lane);      // (vh_plane_agg.h: the loop over the group ids, shared with the batch kernel)
   }
 
   if (__ballot(range_err) != 0ull && lane == 0) atomicOr(P.counters + 2, VH_ERR_RANGE);
@@ -74,7 +83,12 @@ void vh_launch_scan_planes(const VhPlanDev& P, const VhPlaneAggRef& A, uint32_t 
   constexpr int BLOCK = 256;       // (at 1024 threads a lane may hold 128 registers, a few fewer than the filter interpreter and the 32 plane words take: QueryBuild::decompose_work)
   vh_with_scope(xcd_private, [&](auto scope) {
     constexpr int SCOPE = decltype(scope)::value;
-    L.named("scan_agg_planes_kernel<%d, %d>", BLOCK, SCOPE);
-    vh_launch_or_ask(L, scan_agg_planes_kernel<BLOCK, SCOPE>, BLOCK, true, P, A.B, A.D, A.F, A.V, chunks_per_seg);
+    if (A.rows) {
+      L.named("scan_agg_planes_rows_kernel<%d, %d>", BLOCK, SCOPE);
+      vh_launch_or_ask(L, scan_agg_planes_kernel<BLOCK, SCOPE, 1>, BLOCK, true, P, A.B, A.D, A.F, A.V, chunks_per_seg);
+    } else {
+      L.named("scan_agg_planes_kernel<%d, %d>", BLOCK, SCOPE);
+      vh_launch_or_ask(L, scan_agg_planes_kernel<BLOCK, SCOPE, 0>, BLOCK, true, P, A.B, A.D, A.F, A.V, chunks_per_seg);
+    }
   });
 }

@@ -27,7 +27,8 @@ static_assert(VH_BATCH_MAX <= 32, "scan_agg_planes_batch_kernel keeps a bit per 
 //   2. nothing more when no lane of the wave has a passing row of any member;
 //   3. the planes of V that a member with a passing row in the wave needs, loaded ONCE, into the array that is indexed by constants only — and
 //      not at all by a lane without a passing row of any member;
-//   4. per member with a passing row in the wave, the loop over its group ids (vh_plane_agg_groups) into ITS table at lds + lds_base. Every
+//   4. per member with a passing row in the wave, the loop over its group ids (vh_plane_agg_groups) — or, for a row member of a launch
+//      with ROWS = 1, the row sink (vh_plane_agg_rows) — into ITS table at lds + lds_base. Every
 //      branch around it is uniform over the wave: all 64 lanes are active in it.
 // A lane's masks wait for step 4 in lane-private slots of static LDS (8 KB; a write and a read per member and chunk, no conflicts), its row
 // counters in registers that only constant indices reach (vh_member_put / _get: a chain of selects on the uniform member index, eight moves
@@ -45,11 +46,21 @@ __device__ __forceinline__ uint32_t vh_member_get(const uint32_t (&a)[VH_BATCH_M
   return x;
 }
 
-template <int BLOCK, int SCOPE>
+// ROWS = 1, launched when any member of the group is a row member (VhPlaneAggDesc::rows: more ids than the loop can pay for): step 4 takes
+// such a member's surviving rows through the row sink (vh_plane_agg.h: vh_plane_agg_rows) — the branch is on plan data read by a scalar
+// load, uniform like every other one around it — and every other member through the loop, as ROWS = 0 does for all. Steps 1 to 3 are the
+// same text: a row member shares or lends a mask through mask_of like any other. The sink's per-wave queue is 4 KB of static LDS of that
+// instantiation alone: with s_mask and 48 KB of tables two blocks fit a CU's 160 KB.
+template <int BLOCK, int SCOPE, int ROWS>
 __global__ __launch_bounds__(BLOCK, 3) void scan_agg_planes_batch_kernel(const VhBatchMember* __restrict__ Q, uint32_t n, const VhSlicedPlanes V, uint32_t chunks_per_seg) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int lane = threadIdx.x & 63;
   const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  uint16_t* q = nullptr;
+  if constexpr (ROWS) {
+    __shared__ uint16_t s_rowq[BLOCK / 64][VH_PLANE_ROWS_QUEUE];
+    q = s_rowq[wave];
+  }
 #pragma unroll 1
   for (uint32_t k = 0; k < n; ++k) vh_scan_table_init<VH_MODE_DENSE_LDS, BLOCK>(Q[k].P, lds + Q[k].lds_base);
 
@@ -104,7 +115,10 @@ __global__ __launch_bounds__(BLOCK, 3) void scan_agg_planes_batch_kernel(const V
       const uint32_t m = s_mask[k][threadIdx.x];
       if (__ballot(m != 0u) == 0ull) continue;
       const VhBatchMember& M = Q[k];
-      if (vh_plane_agg_groups(M.P, &M.D, M.D.care, M.D.valid, (uint32_t)M.P.G, lds + M.lds_base, v, m, lane)) range_err |= 1u << k;
+      bool err;
+      if (ROWS && M.D.rows) err = vh_plane_agg_rows(M.P, &M.D, lds + M.lds_base, v, m, lane, q);
+      else err = vh_plane_agg_groups(M.P, &M.D, M.D.care, M.D.valid, (uint32_t)M.P.G, lds + M.lds_base, v, m, lane);
+      if (err) range_err |= 1u << k;
     }
   }
 
@@ -123,11 +137,16 @@ __global__ __launch_bounds__(BLOCK, 3) void scan_agg_planes_batch_kernel(const V
   for (uint32_t k = 0; k < n; ++k) vh_scan_table_flush<VH_MODE_DENSE_LDS, BLOCK, SCOPE>(Q[k].P, lds + Q[k].lds_base);
 }
 
-void vh_launch_scan_planes_batch(const VhBatchMember* d_members, uint32_t n, const VhSlicedPlanes& V, uint32_t chunks_per_seg, const VhScanLaunch& L, bool xcd_private) {
+void vh_launch_scan_planes_batch(const VhBatchMember* d_members, uint32_t n, const VhSlicedPlanes& V, uint32_t chunks_per_seg, const VhScanLaunch& L, bool xcd_private, bool rows) {
   constexpr int BLOCK = 256;       // (as scan_agg_planes_kernel: vh_scan_planes.hip)
   vh_with_scope(xcd_private, [&](auto scope) {
     constexpr int SCOPE = decltype(scope)::value;
-    L.named("scan_agg_planes_batch_kernel<%d, %d>", BLOCK, SCOPE);
-    vh_launch_or_ask(L, scan_agg_planes_batch_kernel<BLOCK, SCOPE>, BLOCK, true, d_members, n, V, chunks_per_seg);
+    if (rows) {      // (any member of the group is a row member)
+      L.named("scan_agg_planes_batch_kernel<%d, %d, rows>", BLOCK, SCOPE);
+      vh_launch_or_ask(L, scan_agg_planes_batch_kernel<BLOCK, SCOPE, 1>, BLOCK, true, d_members, n, V, chunks_per_seg);
+    } else {
+      L.named("scan_agg_planes_batch_kernel<%d, %d>", BLOCK, SCOPE);
+      vh_launch_or_ask(L, scan_agg_planes_batch_kernel<BLOCK, SCOPE, 0>, BLOCK, true, d_members, n, V, chunks_per_seg);
+    }
   });
 }

@@ -33,13 +33,13 @@ struct VhSlicedRef {
 // The aggregate scan ON the planes (vh_scan_planes.hip: scan_agg_planes_kernel) reads two projections: F, whose fields the filter program
 // compares, and V, which holds every group column and every metric's source column (V may be F). Where their fields lie in V is this
 // descriptor's; it follows the program in the plan block and is passed as a restrict pointer of its own, for the reason given above.
-#define VH_PLANE_AGG_MAX_GROUPS 64      // group ids of a plan that takes the path: the loop over ids is paid per plane word
+#define VH_PLANE_AGG_MAX_GROUPS 64      // group ids of a plan that takes the loop over ids, which is paid per plane word; beyond: the row sink, where asked for
 struct VhPlaneAggDesc {
   uint32_t has_filter;            // 0: no program, every row of the snapshot passes
   uint32_t need;                  // bit p: plane p of V belongs to a group column's or a metric's field (the others are not read)
   uint32_t care;                  // bit p: ... to a group column's
-  uint32_t pad;
-  uint64_t valid;                 // bit g: every group column's value of id g lies within its field (else no row can belong to g)
+  uint32_t rows;                  // 1: the row sink (vh_plane_agg.h: vh_plane_agg_rows) — more than VH_PLANE_AGG_MAX_GROUPS ids; valid and pat are unused then
+  uint64_t valid;                // bit g: every group column's value of id g lies within its field (else no row can belong to g)
   uint32_t pat[VH_PLANE_AGG_MAX_GROUPS];      // id g: the group columns' values (VhGroupDev::lo + digit) at their fields' places (vh_bits_match)
   uint32_t goff[VH_MAX_GROUP], gbits[VH_MAX_GROUP];       // group column i: first plane and planes of its field in V (what pat and care were made of)
   uint32_t moff[VH_MAX_METRIC], mbits[VH_MAX_METRIC];     // metric j (VhPlanDev::m[j], the hidden count included): ... of its source column's field
@@ -48,6 +48,7 @@ struct VhPlaneAggRef {
   const VhBitsProg* B;            // nullptr: no filter
   const VhPlaneAggDesc* D;
   VhSlicedPlanes F, V;
+  uint32_t rows;                  // D->rows, for the host: which instantiation the launcher takes (not a kernel argument)
 };
 // One member of a fused batch (vh_scan_planes_batch.hip: scan_agg_planes_batch_kernel): what scan_agg_planes_kernel takes as arguments for one
 // query, without V — the members of a group share it — and with the place of the member's LDS table in the launch's dynamic LDS. An array of

@@ -579,6 +579,7 @@ static int batch_launch_scans(VhBatchFuse& F, uint32_t n, VhBatchGroups* G, uint
     hipStream_t ls = lx->stream();
     uint32_t lds = 0;
     int grid = 0;
+    bool rows = false;      // any row member: the instantiation that carries the row sink
     uint32_t mask_of[VH_BATCH_MAX], classes = cnt;
     if (no_share) for (uint32_t k = 0; k < cnt; ++k) mask_of[k] = k;
     else classes = vh_batch_share(sh, m, cnt, mask_of);
@@ -589,16 +590,17 @@ static int batch_launch_scans(VhBatchFuse& F, uint32_t n, VhBatchGroups* G, uint
       M.P = s.P; M.B = s.B; M.D = s.D; M.F = s.A.F; M.lds_base = lds; M.mask_of = mask_of[k];
       lds += d[m[k]].lds_bytes;
       grid = std::max(grid, s.grid);
+      rows = rows || s.D.rows != 0;
     }
     HIP_TRY(hipMemcpyAsync(lx->d_batch, lx->h_batch, cnt * sizeof(VhBatchMember), hipMemcpyHostToDevice, ls));
     HIP_TRY(hipEventRecord(lx->ev_batch[0], ls));
     char nm[160] = "";
     VhScanLaunch L;
     L.name = nm; L.name_cap = sizeof(nm);
-    vh_launch_scan_planes_batch(lx->d_batch, cnt, lead.A.V, lead.chunks_per_seg, L, lead.xcd_private);      // (its name)
+    vh_launch_scan_planes_batch(lx->d_batch, cnt, lead.A.V, lead.chunks_per_seg, L, lead.xcd_private, rows);      // (its name)
     L = VhScanLaunch{};
     L.grid = grid; L.lds = lds; L.stream = ls;
-    vh_launch_scan_planes_batch(lx->d_batch, cnt, lead.A.V, lead.chunks_per_seg, L, lead.xcd_private);
+    vh_launch_scan_planes_batch(lx->d_batch, cnt, lead.A.V, lead.chunks_per_seg, L, lead.xcd_private, rows);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(lx->ev_batch[1], ls));
     for (uint32_t k = 0; k < cnt; ++k) {      // every member's stream behind the launch, then its own tail there

@@ -391,12 +391,18 @@ void QueryBuild::choose_sliced_prebuilt() {
 
 // The aggregate is computed ON the bit-sliced planes (scan_agg_planes_kernel; include/viya_hip.h states the rule, "Aggregates on the bit-sliced
 // planes"): asked for and not a sharded query (pagg_want), no compiled kernel after all, the dense LDS table with at most VH_PLANE_AGG_MAX_GROUPS
-// ids, no filter or the select's rule on one current projection F (planes_ready), plain group columns, integer SUM / COUNT / AVG / MIN / MAX states
+// ids — any number the table holds when VH_PLAN2_PLANE_ROWS asked (pagg_rows): beyond the bound the row sink stands in for the loop over
+// ids (D.rows; vh_plane_agg.h) —, no filter or the select's rule on one current projection F (planes_ready), plain group columns, integer SUM / COUNT / AVG / MIN / MAX states
 // only, and ONE usable, current bit-sliced projection V with every group column and every metric's source column, the hidden count included
 // (F itself when it has them). Whether the plan settled on the lanes form plays no part. It only changes which kernel fills the block's LDS
 // table. F and V are stamped and held; nothing is built or queued.
 void QueryBuild::choose_plane_agg() {
-  if (!pagg_want || jk || mode != VH_MODE_DENSE_LDS || P.G > VH_PLANE_AGG_MAX_GROUPS || P.nbitset) return;
+  if (!pagg_want || jk || mode != VH_MODE_DENSE_LDS || (P.G > VH_PLANE_AGG_MAX_GROUPS && !pagg_rows) || P.nbitset) return;
+  // The row sink takes a plan that asked for it (VH_PLAN2_PLANE_ROWS) from one id beyond the loop's bound on; the test hook moves that threshold
+  // down, so that one process runs the same small plan through both sinks.
+  uint64_t rows_min = VH_PLANE_AGG_MAX_GROUPS + 1;
+  if (const char* e = test_env("VH_TEST_PLANE_ROWS_MIN")) rows_min = std::min<uint64_t>(rows_min, strtoull(e, nullptr, 10));
+  const bool rows = pagg_rows && P.G >= rows_min;
   VhPredPack* f = nullptr;
   if (pagg_filter) {
     if (!planes_ready || !sliced_use || sliced_use->applied_epoch != t->sync_epoch) return;
@@ -430,7 +436,8 @@ void QueryBuild::choose_plane_agg() {
   for (int i = 0; i < P.ngroup; ++i) D.care |= field(p->groups[i].col, &D.goff[i], &D.gbits[i]);
   D.need = D.care;
   for (int j = 0; j < P.nmetric; ++j) D.need |= field(metric_col[j], &D.moff[j], &D.mbits[j]);
-  for (uint64_t g = 0; g < P.G; ++g) {      // id g's digits -> the values its rows hold, at their fields' places
+  D.rows = rows ? 1u : 0u;
+  for (uint64_t g = 0; g < P.G && !rows; ++g) {      // id g's digits -> the values its rows hold, at their fields' places (the row sink goes the other way: a row's values -> its id)
     uint32_t pat = 0;
     bool fits = true;
     for (int i = 0; i < P.ngroup; ++i) {
@@ -442,6 +449,7 @@ void QueryBuild::choose_plane_agg() {
     if (fits) D.valid |= 1ull << g;
   }
   plane_agg = true;
+  pagg_ref.rows = D.rows;      // (here, not with the rest of pagg_ref in layout_scratch: decompose_work asks the launcher for the kernel's name and occupancy first)
   pagg_v = v;
   if (f) layout_use(t, f);
   layout_use(t, v);
@@ -492,7 +500,7 @@ int QueryBuild::decompose_work() {
   const int env_lanes_block = knobs().lanes_block, env_bpc = knobs().blocks_per_cu, env_unit = knobs().unit_rows;
   choose_plane_agg();           // (first: when both apply, the aggregate on the planes wins)
   choose_sliced_prebuilt();
-  BLOCK = jk ? jit_block : mode == VH_MODE_DENSE_LDS && !plane_agg ? 1024 : 256;      // (the aggregate on the planes: 151 registers a lane, three 256-thread blocks per CU; its table has at most 64 groups to flush)
+  BLOCK = jk ? jit_block : mode == VH_MODE_DENSE_LDS && !plane_agg ? 1024 : 256;      // (the aggregate on the planes: 151 registers a lane, three 256-thread blocks per CU; its table has at most 64 groups to flush — with the row sink 105 registers and whatever table the organisation allows)
   if (mode == VH_MODE_DENSE_LDS && lanes && !plane_agg) {
     if (env_lanes_block == 256 || env_lanes_block == 512 || env_lanes_block == 1024) BLOCK = env_lanes_block;
     else if ((uint64_t)g_ctx.num_cu * 5 * G * std::max(1, P.nmetric) <= rows_to_scan / 32) BLOCK = 256;
@@ -780,8 +788,7 @@ int QueryBuild::layout_scratch() {
       pagg_ref.B = pagg_filter ? reinterpret_cast<const VhBitsProg*>(S + o_segrows + planes_word * 4) : nullptr;
       pagg_ref.D = reinterpret_cast<const VhPlaneAggDesc*>(S + o_segrows + pagg_word * 4);
       pagg_ref.F.planes = f->plane[0].ptr; pagg_ref.F.stride = f->plane[0].stride; pagg_ref.F.pitch = f->pitch;
-      pagg_ref.V.planes = pagg_v->plane[0].ptr; pagg_ref.V.stride = pagg_v->plane[0].stride; pagg_ref.V.pitch = pagg_v->pitch;
-    }
+      pagg_ref.V.planes = pagg_v->plane[0].ptr; pagg_ref.V.stride = pagg_v->plane[0].stride; pagg_ref.V.pitch = pagg_v->pitch;    }
   }
   if (mode == VH_MODE_HASH) {
     P.hkeys = reinterpret_cast<uint64_t*>(S + o_hkeys);
@@ -969,6 +976,7 @@ int QueryBuild::launch() {
   w.has_set = has_set; w.set_search = set_search; w.set_truth = set_truth; w.build_pending = build_pending;
   w.grouped = grouped; w.gplanes = gplanes; w.subtrim = subtrim; w.gpspan = gpspan; w.sliced_prebuilt = sliced_prebuilt; w.plane_agg = plane_agg;
   r->info.reserved = vh_info_compose(w);
+  r->plane_sink = !plane_agg ? 0u : pagg_desc.rows ? 2u : 1u;      // (vh_result_plane_sink: `reserved` has no bit left for it)
   r->fast_scan = w.fast;      // (VH_INFO_FAST as planned: a pre-built reader of the planes clears the bit in the result's word)
   if (r->hp_chunks) memset(x->h_chunk, 0, VH_HP_CHUNKS * sizeof(unsigned long long));      // (what the context's previous query left there)
   // a second pass over heavy level-A partitions of a hashed partitioning: from the first pass's tuples when this plan's table can take them as

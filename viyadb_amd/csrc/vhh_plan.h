@@ -325,7 +325,8 @@ struct QueryBuild {
   // The aggregate ON the bit-sliced planes (scan_agg_planes_kernel; opt-in: VH_PLAN2_PLANE_AGG, or VH_PLANE_AGG=1 for the process). Its filter is the
   // program above (planes_prog over sliced_use = F), or none.
   bool pagg_want = false;                        // shape_filter: asked for, not a sharded query, none of the flags that keep a plan off the planes
-  bool pagg_filter = false;                      // ... and the filter has a leaf (nodes that are always true alone: no program, as with no filter)
+  bool pagg_rows = false;                        // ... with VH_PLAN2_PLANE_ROWS: more than VH_PLANE_AGG_MAX_GROUPS ids take the row sink
+  bool pagg_filter = false;                     // ... and the filter has a leaf (nodes that are always true alone: no program, as with no filter)
   size_t pagg_word = 0;                          // snapshot_segments: the descriptor's u32 word in the plan block (behind the program)
   VhPredPack* pagg_v = nullptr;                  // decompose_work: the projection that holds group and metric columns (V) ...
   bool plane_agg = false;                        // ... and the rule holds: the kernel runs
@@ -576,7 +577,9 @@ int QueryBuild::shape_filter() {
   sliced_asked = planes_allowed && p->nfilter > 0 && ((p->flags & VH_PLAN_SLICED_PREBUILT) || knobs().sliced_prebuilt);
   // ... and so does one that asks to be computed on the planes (VH_PLAN2_PLANE_AGG), unless it has no filter: then it needs no program.
   // Sharded queries (an agreed plan, a summary call, rows kept on the device for the exchange) ignore that switch.
-  pagg_want = planes_allowed && ((p->flags2 & VH_PLAN2_PLANE_AGG) || knobs().plane_agg) && !o.ag && !o.summary_out && !o.device_rows;
+  // VH_PLAN2_PLANE_ROWS asks for the same, and lifts the bound on the group ids: beyond it the row sink answers (choose_plane_agg).
+  pagg_want = planes_allowed && ((p->flags2 & (VH_PLAN2_PLANE_AGG | VH_PLAN2_PLANE_ROWS)) || knobs().plane_agg) && !o.ag && !o.summary_out && !o.device_rows;
+  pagg_rows = pagg_want && (p->flags2 & VH_PLAN2_PLANE_ROWS) != 0;
   for (const VhProgOp& o : prog) pagg_filter |= o.kind() == VH_F_REL || o.kind() == VH_F_IN || o.kind() == VH_F_INSET;
   planes_want = sliced_asked || (pagg_want && pagg_filter);
   bool shaped = (jit_allowed || o.plan_only || planes_want) && prog.size() <= VH_INLINE_PROG && r->h_lits.size() <= VH_INLINE_LITS;

@@ -115,6 +115,7 @@ struct vh_result {
   bool unmerged = false;               // ... which also adds the private copies up: until then (or until merge_copies_now, in front of a cross-GPU reduce) nobody has
   vh_tail_info tail{};                 // which kernels ended the query (vh_result_tail): filled by result_finalize, `merged` by whoever adds the copies up
   vh_batch_member_info batch_member{}; // its place in a fused launch of a batch (vh_result_batch_member): filled by batch_launch_scans, zeros otherwise
+  uint32_t plane_sink = 0;             // the aggregate on the planes' sink (vh_result_plane_sink): 0 not on the planes, 1 the loop over ids, 2 the row sink
   std::vector<int> metric_elem;        // output element type per device metric (P.m order)
   std::vector<int> group_elem;
   std::string group_sig;
@@ -177,6 +178,12 @@ extern "C" int vh_result_tail(vh_result* r, vh_tail_info* out) {
 extern "C" int vh_result_batch_member(vh_result* r, vh_batch_member_info* out) {
   if (!r || !out) return vh_fail(VH_E_INVALID, "null argument");
   *out = r->batch_member;
+  return VH_OK;
+}
+
+extern "C" int vh_result_plane_sink(vh_result* r, uint32_t* sink) {
+  if (!r || !sink) return vh_fail(VH_E_INVALID, "null argument");
+  *sink = r->plane_sink;
   return VH_OK;
 }
 

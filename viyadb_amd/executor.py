@@ -120,6 +120,13 @@ class AggResult:
         return bool(self.flags & capi.INFO_PLANE_AGG)
 
     @property
+    def plane_sink(self) -> int:
+        """Which sink of the aggregate on the planes filled the table (vh_result_plane_sink): 0 the result is no plane aggregate, 1 the loop
+        over group ids, 2 the row sink (PLAN2_PLANE_ROWS and more than 64 ids). Set by _collect; no field of its own (0 for a record built
+        by hand)."""
+        return getattr(self, "_plane_sink", 0)
+
+    @property
     def batch_fused(self) -> bool:
         """The result was filled by a fused launch of a batch (query_agg_batch; bit 30, bit 27 and its company are set too): derived from
         `flags`, like plane_agg."""
@@ -477,6 +484,9 @@ class DeviceTable:
         member = capi.BatchMemberInfo()
         capi.check(self.lib.vh_result_batch_member(res, C.byref(member)))
         out._batch_member = member
+        sink = C.c_uint32(0)
+        capi.check(self.lib.vh_result_plane_sink(res, C.byref(sink)))
+        out._plane_sink = int(sink.value)
         return out
 
     def query_agg(self, plan: AggPlan, copy: bool = True) -> AggResult:
