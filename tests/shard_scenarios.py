@@ -1,7 +1,9 @@
 """Sharded-query scenarios (tests/test_gpu_distributed.py): per-rank data that makes the ranks' LOCAL views differ — disjoint
 value ranges of the group columns, different selectivities, one shard with far more groups than the other, an empty shard —
 so that only a plan agreed between the ranks gives identically indexed tables and matching collectives.
-`build(name, ranks)` -> (oracle Table holding the segments of those ranks, query JSON, plan flags, groups_hint)."""
+`build(name, ranks)` -> (oracle Table holding the segments of those ranks, query JSON, plan flags, groups_hint).
+tests/test_gpu_thread_ranks.py runs the same scenarios at 3, 4 and 8 ranks with smaller segments (`rows`), `empty_shard` with any set of
+empty ranks, and `typed`: signed keys of two widths with a count-distinct metric (build_typed)."""
 import numpy as np
 
 from oracle import viya_oracle as vo
@@ -17,7 +19,12 @@ def _rng(name, rank, seg):
     return np.random.default_rng(abs(hash((name, rank, seg))) % (2 ** 32)) if False else np.random.default_rng([sum(map(ord, name)), rank, seg])
 
 
-def build(name, ranks, world=2, grown=False):
+def build(name, ranks, world=2, grown=False, rows=None, empty=(1,), spread=1000):
+    """rows: rows of a full segment (less 17 per rank number, as ever), SEG when None; empty: the ranks that hold no rows in `empty_shard`;
+    spread: what lies between two ranks' ranges of `a` in `disjoint_ranges`.
+    Every rank's segments depend on (name, rank, segment) alone, so any `world` works; world = 2 with the defaults is what it always was."""
+    if name == "typed":
+        return build_typed(ranks, rows)
     U = [{"name": "a", "type": "uint"}, {"name": "b", "type": "uint"}, {"name": "f", "type": "uint"}]
     M = [{"name": "v", "type": "long_sum"}, {"name": "count", "type": "count"}, {"name": "umin", "type": "uint_min"},
          {"name": "lmax", "type": "ulong_max"}, {"name": "d", "type": "double_sum"}]
@@ -29,12 +36,12 @@ def build(name, ranks, world=2, grown=False):
     for rank in ranks:
         for s in range(segs_per_rank + (1 if grown and rank == 1 else 0)):
             r = _rng(name, rank, s)
-            n = SEG - 17 * (rank + 1)
+            n = (SEG if rows is None else rows) - 17 * (rank + 1)
             a = r.integers(0, 60, n)
             b = r.integers(0, 50, n)
             f = r.integers(0, 100, n)
             if name == "disjoint_ranges":            # rank r only holds a in [1000 r, 1000 r + 60), b in [7 r, 7 r + 50)
-                a = a + 1000 * rank
+                a = a + spread * rank
                 b = b + 7 * rank
                 if s >= segs_per_rank:               # the segment that appears between two queries: outside every range agreed so far
                     a = a + 700
@@ -50,7 +57,7 @@ def build(name, ranks, world=2, grown=False):
                 else:
                     a = r.integers(0, 900, n)     # 45 000 groups against the 4096 slots a hint of 4 groups buys
             elif name == "empty_shard":
-                if rank == 1:
+                if rank in empty:
                     n = 0
                     a, b, f = a[:0], b[:0], f[:0]
             elif name == "sparse_keys":              # float / wide keys: hash organisation
@@ -71,3 +78,25 @@ def build(name, ranks, world=2, grown=False):
         q = dict(q, dimensions=["a", "lmaxkey"]) if False else q
         flags = 1
     return t, q, flags, hint
+
+
+def build_typed(ranks, rows=None):
+    """Keys (short, int) with negatives, metrics count, double_sum, int_min, ulong_max and a bitset: every rank holds the same key space
+    (so every group is merged from several ranks' partials) and ids that overlap between ranks (so the merged count-distinct is no sum)."""
+    rows = 5000 if rows is None else rows
+    t = vo.Table({"name": "t", "segment_size": rows,
+                  "dimensions": [{"name": "ks", "type": "short"}, {"name": "ki", "type": "int"}, {"name": "f", "type": "uint"}],
+                  "metrics": [{"name": "count", "type": "count"}, {"name": "d", "type": "double_sum"}, {"name": "imin", "type": "int_min"},
+                              {"name": "lmax", "type": "ulong_max"}, {"name": "users", "type": "bitset", "max": 2 ** 31}]})
+    for rank in ranks:
+        for s in range(2):
+            r = _rng("typed", rank, s)
+            n = rows - 17 * (rank + 1)
+            sets = [set(int(v) for v in r.integers(0, 400, k)) for k in r.integers(0, 4, n)]
+            t.add_segment_arrays([r.integers(-30, 30, n).astype(np.int16), r.integers(-2 ** 31, -2 ** 31 + 20, n).astype(np.int32) if s else r.integers(-10, 10, n).astype(np.int32),
+                                  r.integers(0, 100, n).astype(np.uint32)],
+                                 [r.integers(1, 4, n).astype(np.uint32), r.integers(-1000, 1000, n) / 8.0, r.integers(-2 ** 31, 2 ** 31, n).astype(np.int32),
+                                  r.integers(0, 2 ** 64, n, dtype=np.uint64), sets], None, n)
+    q = {"type": "aggregate", "table": "t", "dimensions": ["ks", "ki"], "metrics": ["count", "d", "imin", "lmax", "users"],
+         "filter": {"op": "lt", "column": "f", "value": "60"}}
+    return t, q, 1, 0

@@ -637,6 +637,14 @@ class DeviceTable:
         self.lib.vh_result_free(res)
 
 
+def device_read(ptr, count: int, dtype) -> np.ndarray:
+    """Host copy of `count` elements at a device address (vh_device_read): a buffer of partition / partition_pairs, say."""
+    out = np.empty(int(count), dtype=dtype)
+    if out.nbytes:
+        capi.check(capi.load().vh_device_read(out.ctypes.data, C.c_void_p(ptr), out.nbytes))
+    return out
+
+
 def measure_read_bandwidth(nbytes: int = 4 << 30, iters: int = 5) -> float:
     out = C.c_double()
     capi.check(capi.load().vh_measure_read_bandwidth(int(nbytes), int(iters), C.byref(out)))
