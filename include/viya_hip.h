@@ -246,6 +246,15 @@ enum vh_plan_flags2 {
                                      table once per metric (scan_agg_planes_rows_kernel). Up to 64 ids the loop over ids runs as without
                                      it. No environment variable sets it; sharded calls ignore it. vh_result_plane_sink tells */
 };
+/* ... and the bit of vh_plan.flags2 that asks for a COMPILED kernel on the planes */
+enum vh_plan_flags2_compiled {
+  VH_PLAN2_PLANE_JIT = 1u << 2    /* opt-in: asks for everything VH_PLAN2_PLANE_AGG asks for AND, wherever a compiled kernel may run the query
+                                     at all (VH_JIT, VH_JIT_MIN_ROWS, VH_PLAN_FORCE_JIT), for the aggregate to be computed on the planes by
+                                     a kernel COMPILED for the plan's shape: filter, field places, metric kinds and sink are constants of
+                                     its text (the rule: "Aggregates on the bit-sliced planes, compiled" below; VH_PLANE_JIT=1 in the
+                                     environment sets it for every aggregate of the process that is not a vh_query_agg_sharded call).
+                                     With VH_PLAN2_PLANE_ROWS the compiled kernel runs the row sink from 65 ids on */
+};
 typedef struct vh_plan {
   const vh_filter_node* filter; int32_t nfilter;   /* postfix program        */
   const vh_anynum* lits;        int32_t nlits;
@@ -340,7 +349,9 @@ typedef struct vh_result_info {
                                         and 13 are set too, bits 22 and 25 when the filter has VH_F_INSET leaves; bits 0, 1 and 5 are clear);
                                 bit 27: VH_INFO_PLANE_AGG — the aggregate was computed ON the bit-sliced planes, sums and min / max by popcount (VH_PLAN2_PLANE_AGG:
                                         bits 4, 11 and 13 are set too, bits 22 and 25 when the filter has VH_F_INSET leaves; bits 0, 1, 5 and 26
-                                        are clear, and so are the projection's bits 3, 7 and 15-18: no payload is gathered);
+                                        are clear — except bit 5, which is SET when the kernel on the planes was one compiled for the plan's
+                                        shape (VH_PLAN2_PLANE_JIT; bits 0, 1 and 26 stay clear) —, and so are the projection's bits 3, 7 and
+                                        15-18: no payload is gathered);
                                 bit 28: VH_INFO_SUBTRIM — the grouped form is SUB-SORTED by the column of a range leaf (tiles ordered by grouping value, then that
                                         column's field, then row) and the scan TRIMMED every run to the words that can pass the leaf, found
                                         through 64 boundary keys per tile (bits 20 and 21 are set too);
@@ -582,7 +593,8 @@ VH_API int vh_query_agg(vh_table* t, const vh_plan* plan, vh_result** out);
  * members' values must not be added up; vh_batch_info.fused_kernel_ms is the sum over the launches). A member that takes the row sink
  * (VH_PLAN2_PLANE_ROWS and more than 64 ids) is a candidate like any other, shares or lends a mask like any other, and the 48 KB bound
  * on the tables is what limits it; a launch with such a member is named scan_agg_planes_batch_kernel<256, S, rows> and runs the row sink
- * for it and the loop for the others. A group of one, and every member that
+ * for it and the loop for the others. A member that carries VH_PLAN2_PLANE_JIT (or runs under VH_PLANE_JIT=1) is NO candidate, whether
+ * its compiled kernel or the pre-built one ends up answering it: the fused kernel is pre-built. A group of one, and every member that
  * is no candidate, runs as the single query it is: the flags and the kernel name its vh_query_agg would give, bit 30 clear. A fused member
  * that has to be planned again (a value synced in beyond the planned range) is answered alone by vh_query_agg's re-plan loop; the others stand.
  *
@@ -772,7 +784,28 @@ VH_API int vh_query_agg_sharded(vh_table* t, const vh_plan* plan, vh_comm* comm,
  * It changes which kernel fills the same LDS table and nothing else: organisation, states (a u32 sum wraps as before), HAVING, top-N and
  * delivery are those of the same plan without the switch. The query stamps F and V (vh_layout_info.uses) and holds them against eviction
  * while it runs; it builds and queues no layout. vh_result_info.reserved bit 27 tells, whichever sink ran; vh_result_plane_sink tells
- * the sink: 0 the result is no aggregate on the planes, 1 the loop over ids, 2 the row sink. */
+ * the sink: 0 the result is no aggregate on the planes, 1 the loop over ids, 2 the row sink.
+ *
+ * Aggregates on the bit-sliced planes, compiled. VH_PLAN2_PLANE_JIT in vh_plan.flags2 (VH_PLANE_JIT=1 in the environment, read once per
+ * process) asks for the same, with VH_PLAN2_PLANE_ROWS lifting the bound of 64 ids as above, and for a kernel compiled for the plan's shape
+ * to do it. The rule is the one above with ONE clause changed: in the place of "no compiled kernel runs the query" stands "the compiled
+ * kernel that runs the query is the plane aggregate's". Every other bullet holds unchanged; where one of them fails the flag changes
+ * nothing and the query is planned as without it. Where they hold but no compiled kernel can be had — VH_JIT=off, VH_PLAN_NO_JIT, fewer rows
+ * than VH_JIT_MIN_ROWS, a compile that failed (an error under VH_PLAN_FORCE_JIT / VH_JIT=force, as for every compiled kernel), or a compile
+ * still pending on a VH_BUILD_BACKGROUND table (bit 19 is set and the shape is queued with the build worker like any other) — the query is
+ * answered as the same plan with VH_PLAN2_PLANE_AGG in the flag's place: the pre-built kernel, bit 27 set and bit 5 clear. The same holds,
+ * without an error even under VH_PLAN_FORCE_JIT, for a plan the generator has no shape for: more than 8 group columns or more than 8
+ * metrics, a filter whose leaves' columns take more than 64 planes of F together (the bound the compiled scan has for its registers), or
+ * a plan that already uses one of the last two of its 32 column slots, where F and V travel.
+ * The kernel's text (vh_jit.hip, the frame is vh_jit_planes.h) holds what is SHAPE: the filter as one bit-serial expression over the planes of
+ * F its leaves read, set leaves as truth tables; V's planes loaded by constant number, exactly those of the fields involved; per metric a
+ * constant field and kind — a 10-bit SUM is ten popcounts —; the sink. What is DATA stays out of it, so one code object serves every query
+ * of the shape: literals, set members, snapshots, and the group columns' lo / extent / stride with the ids' patterns made of them.
+ * Choosing this path builds and queues nothing but the kernel; F and V are stamped and held as above. What the planner does for every
+ * plan a compiled kernel may answer BEFORE the kernel is chosen is as without the flag and is not undone: the selectivity probe runs, and
+ * the table's automatic layouts (VH_AUTO_PACK, VH_AUTO_NARROW) count the query and may build or queue a projection this path never reads. vh_query_agg_sharded ignores the flag. Reported:
+ * vh_result_info.reserved bits 27 AND 5, bits 4 / 11 / 13 (22 / 25) as for bit 27, bits 0 / 1 / 26 clear; vh_result_kernel gives the
+ * compiled kernel's name; vh_result_plane_sink 1 or 2 as above. */
 VH_API int vh_result_plane_sink(vh_result* r, uint32_t* sink);   /* VH_E_INVALID: a null argument */
 #define VH_COL_ROWID (-2)
 typedef struct vh_rows vh_rows;

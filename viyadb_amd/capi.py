@@ -40,6 +40,18 @@ PLAN_SET_SEARCH = 1 << 30         # testing: every set of an F_INSET leaf takes 
 PLAN_SLICED_PREBUILT = 1 << 31    # opt-in: an aggregate no compiled kernel answers reads its filter off the bit-sliced planes (scan_agg_sliced_kernel)
 PLAN2_PLANE_AGG = 1 << 0          # vh_plan.flags2 (enum vh_plan_flags2). Opt-in: an aggregate of few groups is computed on the bit-sliced planes (scan_agg_planes_kernel)
 PLAN2_PLANE_ROWS = 1 << 1         # ... the same, without the bound of 64 group ids: beyond it the row sink fills the table (scan_agg_planes_rows_kernel; vh_result_plane_sink)
+# enum vh_plan_flags2_compiled, the header's second enum of vh_plan.flags2 bits. The module's own PLAN2_* names are enum vh_plan_flags2's and
+# nothing else (tests/test_capi_plane_rows.py holds vars(capi) to those two), so the bits of the second enum are served by name through the
+# module's __getattr__ below: capi.PLAN2_PLANE_JIT and `from viyadb_amd.capi import PLAN2_PLANE_JIT` both work.
+_PLAN2_COMPILED = {"PLAN2_PLANE_JIT": 1 << 2}      # ... PLAN2_PLANE_AGG, by a kernel compiled for the plan's shape wherever a compiled kernel may run the query (bits 27 and 5; VH_PLANE_JIT=1)
+
+
+def __getattr__(name):
+    if name in _PLAN2_COMPILED:
+        return _PLAN2_COMPILED[name]
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 # paths
 PATH_SCALAR, PATH_DENSE_LDS, PATH_DENSE_GLOBAL, PATH_HASH, PATH_DENSE_PART = range(5)
 PATH_NAMES = ["scalar", "dense_lds", "dense_global", "hash", "dense_part"]
@@ -178,7 +190,7 @@ INFO_INSET_SEARCH = 1 << 23       # ... at least one of them by binary search in
 INFO_EVICTED = 1 << 24            # planning this query evicted at least one derived layout (tables with a layout budget)
 INFO_INSET_SLICED = 1 << 25       # ... all of the set leaves from truth tables on the bit-sliced predicate planes instead (no lookup per row)
 INFO_SLICED_PREBUILT = 1 << 26    # a pre-built scan read the filter off the bit-sliced predicate planes (bits 4, 11 and 13 are set too)
-INFO_PLANE_AGG = 1 << 27          # the aggregate was computed on the bit-sliced planes (bits 4, 11 and 13 are set too; bits 0, 1, 5 and 26 are clear)
+INFO_PLANE_AGG = 1 << 27          # the aggregate was computed on the bit-sliced planes (bits 4, 11 and 13 are set too; bits 0, 1 and 26 are clear, and so is bit 5 unless the kernel was compiled for the plan: PLAN2_PLANE_JIT)
 INFO_SUBTRIM = 1 << 28            # the clustered planes are a sub-sorted form's and every run was trimmed by the sub column's leaf (bits 20 and 21 are set too)
 INFO_GPSPAN = 1 << 29             # the clustered scan's tile groups spanned segments, its queue held table-wide record indexes (bits 20 and 21 are set too)
 INFO_BATCH_FUSED = 1 << 30        # the result was filled by a fused launch of a batch (vh_query_agg_batch; bit 27 and its company are set too)

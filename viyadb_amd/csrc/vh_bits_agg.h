@@ -57,6 +57,45 @@ VH_BITS_FN uint32_t vh_bits_min_at(const uint32_t (&v)[VH_BITS_MAX_FIELD], uint3
   *empty = m == 0u;
   return val;
 }
+// The CONSTANT-PARAMETER forms of the three: the field's place is a template argument — what a kernel compiled for one plan's shape knows
+// (vh_jit_planes.h) —, so the loop has exactly NB steps and no test per plane: a 10-bit SUM is ten popcounts. Same values as the `_at` forms
+// for every (OFF, NB) with OFF + NB <= VH_BITS_MAX_FIELD (tests/plane_jit_host.cc holds them to each other).
+template <int OFF, int NB>
+VH_BITS_FN uint64_t vh_bits_sum_c(const uint32_t (&v)[VH_BITS_MAX_FIELD], uint32_t m) {
+  static_assert(OFF >= 0 && NB >= 0 && OFF + NB <= VH_BITS_MAX_FIELD, "a field lies within the projection's planes");
+  uint64_t s = 0;
+  VH_BITS_UNROLL
+  for (int b = 0; b < NB; ++b) s += (uint64_t)(uint32_t)__builtin_popcount(m & v[OFF + b]) << b;
+  return s;
+}
+template <int OFF, int NB>
+VH_BITS_FN uint32_t vh_bits_max_c(const uint32_t (&v)[VH_BITS_MAX_FIELD], uint32_t m, bool* empty) {
+  static_assert(OFF >= 0 && NB >= 0 && OFF + NB <= VH_BITS_MAX_FIELD, "a field lies within the projection's planes");
+  uint32_t cand = m, val = 0u;
+  VH_BITS_UNROLL
+  for (int b = NB - 1; b >= 0; --b) {
+    const uint32_t t = cand & v[OFF + b];
+    const bool any = t != 0u;
+    cand = any ? t : cand;
+    val |= (any ? 1u : 0u) << b;
+  }
+  *empty = m == 0u;
+  return val;
+}
+template <int OFF, int NB>
+VH_BITS_FN uint32_t vh_bits_min_c(const uint32_t (&v)[VH_BITS_MAX_FIELD], uint32_t m, bool* empty) {
+  static_assert(OFF >= 0 && NB >= 0 && OFF + NB <= VH_BITS_MAX_FIELD, "a field lies within the projection's planes");
+  uint32_t cand = m, val = 0u;
+  VH_BITS_UNROLL
+  for (int b = NB - 1; b >= 0; --b) {
+    const uint32_t t = cand & ~v[OFF + b];
+    const bool any = t != 0u;
+    cand = any ? t : cand;
+    val |= (any ? 0u : 1u) << b;
+  }
+  *empty = m == 0u;
+  return val;
+}
 VH_BITS_FN uint64_t vh_bits_sum(const uint32_t (&x)[VH_BITS_MAX_FIELD], uint32_t nb, uint32_t m) { return vh_bits_sum_at(x, 0u, nb, m); }
 VH_BITS_FN uint32_t vh_bits_max(const uint32_t (&x)[VH_BITS_MAX_FIELD], uint32_t nb, uint32_t m, bool* empty) { return vh_bits_max_at(x, 0u, nb, m, empty); }
 VH_BITS_FN uint32_t vh_bits_min(const uint32_t (&x)[VH_BITS_MAX_FIELD], uint32_t nb, uint32_t m, bool* empty) { return vh_bits_min_at(x, 0u, nb, m, empty); }

@@ -19,7 +19,11 @@
 // table the planner built over its field (vh_inset.h: vh_inset_bits<NB>, NB <= VH_INSET_TRUTH_BITS).
 #pragma once
 #include <stdint.h>
+#ifdef __HIPCC_RTC__
+#include "viya_hip.h"      // (a compiled kernel's frame: the headers are handed to hipRTC by name, vh_jit.hip)
+#else
 #include "../../include/viya_hip.h"
+#endif
 #include "vh_inset.h"
 
 #if defined(__HIPCC__)

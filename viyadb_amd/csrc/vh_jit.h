@@ -85,6 +85,13 @@ struct VhJitShape {
   // Pipelined drain (vj_drain_pipe, vh_jit_body.h): groups of 64 survivors whose records are in flight while the group before them is
   // sunk. Only plans whose survivor payload is ONE packed record of 4 or 8 bytes (vh_jit_rec_bytes) have one; 0 = one drain after another.
   int drain_depth = 0;
+  // The aggregate ON the bit-sliced planes, compiled (vh_jit_planes.h; the rule: include/viya_hip.h, VH_PLAN2_PLANE_JIT). pa_sink: 0 = not
+  // that shape, 1 = the loop over the group ids, 2 = the row sink. The filter, when there is one (pa_filter), is the bit-sliced one above —
+  // prog over pred[] / pp_off / pp_bits in slot pp_slot, the projection F. V, the projection with the group columns' and the metrics' fields,
+  // lies in slot pa_vslot (pp_slot again when V is F); pa_goff / pa_gbits: group column i's first plane and planes there, pa_moff / pa_mbits
+  // metric j's, whose state operation is m[j].sop. g[] and m[] are otherwise unused: nothing is gathered. These enter key() only when set.
+  int pa_sink = 0, pa_filter = 0, pa_vslot = -1;
+  int pa_goff[VJ_MAX_COLS] = {}, pa_gbits[VJ_MAX_COLS] = {}, pa_moff[VJ_MAX_COLS] = {}, pa_mbits[VJ_MAX_COLS] = {};
   std::string key() const;
 };
 // Bytes of the one packed record a survivor of this shape gathers (4 or 8), 0 for every other payload: arenas, wider records or more than one,
@@ -122,6 +129,8 @@ VhJitKernel* vh_jit_get(const VhJitShape& s, std::string* err);
 int vh_jit_peek(const VhJitShape& s, VhJitKernel** k, std::string* err);
 int vh_jit_occupancy(VhJitKernel* k, int block, size_t lds);
 hipError_t vh_jit_launch(VhJitKernel* k, const VhPlanDev& P, int grid, int block, size_t lds, hipStream_t s);
+// ... of a plane-aggregate shape (VhJitShape::pa_sink): the descriptor's device pointer and the chunks per segment travel beside the plan
+hipError_t vh_jit_launch_planes(VhJitKernel* k, const VhPlanDev& P, const void* d_desc, uint32_t chunks_per_seg, int grid, int block, size_t lds, hipStream_t s);
 hipError_t vh_jit_launch_hpagg(VhJitKernel* k, const VhPlanDev& P, const void* d_hpargs, int blocks_per_partition, int a_first, int grid, size_t lds, hipStream_t s);
 hipError_t vh_jit_launch_pagg(VhJitKernel* k, const VhPlanDev& P, int blocks_per_part, size_t lds, hipStream_t s);
 #ifndef VH_HP_AGG_BLOCK

@@ -26,7 +26,7 @@
 #include <memory>
 #include <mutex>
 
-#include "../build/vh_jit_embed.inc"     // vj_embedded[]: the text of viya_hip.h, vh_internal.h, vh_kernels.h, vh_jit_body.h (build.py)
+#include "../build/vh_jit_embed.inc"     // vj_embedded[]: the text of viya_hip.h, vh_internal.h, vh_kernels.h, vh_jit_body.h, vh_jit_planes.h and what they include (build.py)
 
 // ------------------------------------------------------------------ policy
 int vh_jit_policy() {
@@ -73,6 +73,11 @@ std::string VhJitShape::key() const {
   if (drain_depth) { k += "dd"; put(drain_depth); }      // (depth 0 keeps the names its kernels always had)
   if (sub_slot >= 0) { k += "st"; put(sub_slot); put(sub_pred); put(sub_op); put(sub_lit); }      // (likewise: a scan that trims no run keeps its name)
   if (gp_span) { k += "gs"; put(gp_span); }      // (likewise: a scan whose groups end with the segment keeps its name)
+  if (pa_sink) {      // (likewise: only the aggregate on the planes has a sink)
+    k += "pa"; put(pa_sink); put(pa_filter); put(pa_vslot);
+    for (int i = 0; i < ng; ++i) { put(pa_goff[i]); put(pa_gbits[i]); }
+    for (int j = 0; j < nm; ++j) { put(pa_moff[j]); put(pa_mbits[j]); }
+  }
   return k;
 }
 
@@ -139,12 +144,15 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
   // (a scan that trims the runs of a sub-sorted form says so ahead of the frame; every other shape's text is what it always was)
   const bool subtrim = s.pp_sliced && s.pp_group >= 0 && s.pp_group < s.npred && !s.qpay && !s.lanes && s.gp_slot >= 0 && s.gp_G > 0 &&
                        s.sub_slot >= 0 && s.sub_pred >= 0 && s.sub_pred < s.npred && s.sub_pred != s.pp_group && vh_gsub_op_ok(s.sub_op);
-  t += "// generated by vh_jit.hip for one plan shape; the frame is vh_jit_body.h\n#define VH_HPART_KERNELS\n";
+  // (the aggregate on the planes has a frame of its own, which no other shape's text names)
+  if (s.pa_sink) t += "// generated by vh_jit.hip for one plan shape; the frame is vh_jit_planes.h\n";
+  else t += "// generated by vh_jit.hip for one plan shape; the frame is vh_jit_body.h\n#define VH_HPART_KERNELS\n";
   if (subtrim) t += "#define VJ_SUBTRIM 1\n";
   // (... and so does one whose tile groups span segments)
   const bool gpspan = s.gp_span && vh_jit_span_ok(s);
   if (gpspan) t += "#define VJ_GPSPAN 1\n";
-  t += "#include \"vh_jit_body.h\"\n#include \"vh_hpart.h\"\n";
+  if (s.pa_sink) t += "#include \"vh_jit_planes.h\"\n";
+  else t += "#include \"vh_jit_body.h\"\n#include \"vh_hpart.h\"\n";
   t += "typedef uint32_t vj_u32x2 __attribute__((ext_vector_type(2)));\n#define vj_b(x) __builtin_amdgcn_ballot_w64(x)\n";
   // ---- packed predicate registers: stream p (a predicate column, or a plane of the bit-packed predicate projection) occupies
   //      v[base[p] .. base[p] + 4 * width) of every lane
@@ -336,6 +344,27 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
       for (int b = 0; b < s.pp_bits[p]; ++b)
         t += vj_fmt("    v[%d] = in ? __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(base + %dull * ps)) : 0u;\n", sbase[p] + b, s.pp_off[p] + b);
     t += "  }\n";
+  }
+  if (s.pa_sink) {
+    // ---- the aggregate ON the planes (vh_jit_planes.h): the filter is the bit-sliced mask() over preload() above, F's planes; what follows
+    //      says where the group columns' and the metrics' fields lie in V, and loads exactly their planes, by constant plane number
+    uint32_t need = 0, care = 0;
+    auto span = [](int off, int bits) { return bits <= 0 ? 0u : (bits >= 32 ? ~0u : (1u << bits) - 1u) << off; };
+    std::vector<int> a, b, c, d;
+    for (int i = 0; i < s.ng; ++i) { care |= span(s.pa_goff[i], s.pa_gbits[i]); a.push_back(s.pa_goff[i]); b.push_back(s.pa_gbits[i]); }
+    need = care;
+    for (int j = 0; j < s.nm; ++j) { need |= span(s.pa_moff[j], s.pa_mbits[j]); c.push_back(s.pa_moff[j]); d.push_back(s.pa_mbits[j]); }
+    t += vj_fmt("  static constexpr int PA_SINK = %d, PA_VSLOT = %d;\n  static constexpr bool PA_FILTER = %s;\n  static constexpr uint32_t PA_NEED = 0x%Xu, PA_CARE = 0x%Xu;\n",
+                s.pa_sink, s.pa_vslot, s.pa_filter && s.pp_sliced ? "true" : "false", need, care);
+    t += vj_int_array("pa_goff", s.ng, a) + vj_int_array("pa_gbits", s.ng, b) + vj_int_array("pa_moff", s.nm, c) + vj_int_array("pa_mbits", s.nm, d);
+    t += "  static __device__ __forceinline__ void pa_load(const VhPlanDev& P, uint32_t seg, uint32_t row_l, uint32_t (&v)[VH_BITS_MAX_FIELD]) {\n";
+    t += vj_fmt("    const char* base = P.colbase[%d] + (uint64_t)seg * P.colstride[%d] + (uint64_t)(row_l >> 5) * 4ull;\n    const uint64_t ps = P.colpitch[%d];\n    (void)base; (void)ps; (void)v;\n",
+                s.pa_vslot, s.pa_vslot, s.pa_vslot);
+    for (int pl = 0; pl < 32; ++pl) if ((need >> pl) & 1u) t += vj_fmt("    v[%d] = VH_BITS_LOAD(base + %dull * ps);\n", pl, pl);
+    t += "  }\n};\n";
+    t += vj_fmt("extern \"C\" __global__ __launch_bounds__(%d) void %s(const VhPlanDev P, const VhPlaneAggDesc* __restrict__ D, uint32_t chunks_per_seg) { vj_plane_agg<VJ>(P, D, chunks_per_seg); }\n",
+                s.block, kernel_name);
+    return t;
   }
   if (gplanes) {
     // the filter over a word of the clustered planes (the `==` leaf on the grouping column left out), and the lane's loads of a word group: the
@@ -852,6 +881,15 @@ hipError_t vh_jit_launch_pagg(VhJitKernel* k, const VhPlanDev& P, int blocks_per
   return hipModuleLaunchKernel(k->fn_pagg, (unsigned)(P.nfine * blocks_per_part), 1, 1, 1024, 1, 1, (unsigned)lds, s, args, nullptr);
 }
 
+hipError_t vh_jit_launch_planes(VhJitKernel* k, const VhPlanDev& P, const void* d_desc, uint32_t chunks_per_seg, int grid, int block, size_t lds, hipStream_t s) {
+  if (lds > k->scan_lds_set) {
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k->fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    k->scan_lds_set = lds;
+  }
+  void* args[] = {const_cast<VhPlanDev*>(&P), &d_desc, &chunks_per_seg};
+  return hipModuleLaunchKernel(k->fn, (unsigned)grid, 1, 1, (unsigned)block, 1, 1, (unsigned)lds, s, args, nullptr);
+}
+
 hipError_t vh_jit_launch(VhJitKernel* k, const VhPlanDev& P, int grid, int block, size_t lds, hipStream_t s) {
   if (lds > k->scan_lds_set) {       // (the scan that partitions by itself keeps 64 KB of waiting lines next to its queues)
     if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k->fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -897,6 +935,31 @@ static bool vj_canonical(int which, VhJitShape* s) {
     const Geo& g = geo[which - 35];
     for (int k = 0; k < 3; ++k) { S.pred[k].type = g.type[k]; S.prog[(size_t)k].set_type((uint8_t)g.type[k]); S.pp_off[k] = g.off[k]; S.pp_bits[k] = g.bits[k]; }
     S.gp_G = g.G; S.gp_goff = g.off[0];
+    return true;
+  }
+  // the aggregate ON the planes (vh_jit_planes.h). 38: C3's filter over F = [d2 (2 bits), d3 (10), d4 (10)] in slot 7, V = [d2 (2), m0 (10), count (2)]
+  // in slot 8, GROUP BY d2, SUM + COUNT, the loop over ids; 39: the same plan through the row sink; 40: no filter, no group column, V = F one
+  // slot, SUM + MIN + MAX of signed and unsigned kinds over three fields that end at plane 31
+  if (which == 38 || which == 39) {
+    S.mode = VH_MODE_DENSE_LDS; S.block = 256; S.scope = __HIP_MEMORY_SCOPE_WORKGROUP; S.xcd = 1; S.carrier = -1; S.gid32 = 1;
+    S.npred = 3;
+    S.pred[0] = VhJitPred{0, VH_U32, 4}; S.pred[1] = VhJitPred{1, VH_U32, 4}; S.pred[2] = VhJitPred{2, VH_U32, 4};
+    S.prog = {vj_leaf(VH_F_REL, VH_U32, VH_OP_EQ, 0, 0), vj_leaf(VH_F_REL, VH_U32, VH_OP_LT, 1, 1), vj_leaf(VH_F_REL, VH_U32, VH_OP_GE, 2, 2), vj_node(VH_F_AND, 3)};
+    S.nlits = 3;
+    S.pp_sliced = 1; S.pp_slot = 7; S.pp_off[0] = 0; S.pp_bits[0] = 2; S.pp_off[1] = 2; S.pp_bits[1] = 10; S.pp_off[2] = 12; S.pp_bits[2] = 10;
+    S.pa_sink = which == 38 ? 1 : 2; S.pa_filter = 1; S.pa_vslot = 8;
+    S.ng = 1; S.pa_goff[0] = 0; S.pa_gbits[0] = 2;
+    S.nm = 2; S.m[0].sop = SOP_ADD64; S.pa_moff[0] = 2; S.pa_mbits[0] = 10; S.m[1].sop = SOP_ADD32; S.pa_moff[1] = 12; S.pa_mbits[1] = 2;
+    return true;
+  }
+  if (which == 40) {
+    S.mode = VH_MODE_DENSE_LDS; S.block = 256; S.scope = __HIP_MEMORY_SCOPE_AGENT; S.carrier = -1; S.gid32 = 1;
+    S.prog = {vj_node(VH_F_TRUE, 0)};
+    S.pa_sink = 1; S.pa_filter = 0; S.pa_vslot = 3;
+    S.ng = 0; S.nm = 6;
+    const int sops[6] = {SOP_ADD64, SOP_MIN_I32, SOP_MAX_I32, SOP_MIN_U32, SOP_MAX_U64, SOP_MIN_I64};
+    const int offs[6] = {0, 0, 9, 9, 20, 20}, bits[6] = {9, 9, 11, 11, 12, 12};
+    for (int j = 0; j < 6; ++j) { S.m[j].sop = sops[j]; S.pa_moff[j] = offs[j]; S.pa_mbits[j] = bits[j]; }
     return true;
   }
   switch (which) { case 25: which = 22; depth = 1; break; case 26: which = 22; depth = 2; break; case 27: which = 21; depth = -2; break; case 28: which = 7; depth = -2; break; case 29: which = 1; depth = -2; break; default: break; }

@@ -10,14 +10,40 @@
 #include "vh_wave_scan.h"
 
 #if defined(__HIPCC__)
+// WHERE THE FIELDS LIE is a traits object of the two sinks, so that one text serves the pre-built kernels, which read it from the plan
+// (VhPlaneAggPlan below: D->moff / mbits / need, P.m[j].sop() — run-time data, a loop over the metrics that is not unrolled), and a kernel compiled for
+// one plan's shape, which knows it (vh_jit_planes.h: VjPlaneShape — the same members as constants, the loop unrolled). A traits type has
+//   need()                      bit p: plane p of V belongs to a field of the plan
+//   each_metric(f)              f(j) for every metric j of the plan, j an int or a VhIdx<J>
+//   sop(j), sum(j, v, m), min(j, v, m), max(j, v, m)      metric j's state operation and its field's aggregates over the rows of m (vh_bits_agg.h)
+//   field(j, rec), gid(rec, &id)                          metric j's field and the dense group id out of one row's record
+// Everything that depends on lo / extent / stride or on the ids stays data in either form: P.g[], D->pat, D->valid.
+template <int J> struct VhIdx { static constexpr int value = J; __device__ constexpr operator int() const { return J; } };
+struct VhPlaneAggPlan {
+  const VhPlanDev& P;
+  const VhPlaneAggDesc* __restrict__ D;
+  __device__ __forceinline__ uint32_t need() const { return D->need; }
+  template <class F> __device__ __forceinline__ void each_metric(F f) const {
+#pragma unroll 1
+    for (int j = 0; j < P.nmetric; ++j) f(j);
+  }
+  __device__ __forceinline__ int sop(int j) const { return (int)P.m[j].sop(); }
+  __device__ __forceinline__ uint64_t sum(int j, const uint32_t (&v)[VH_BITS_MAX_FIELD], uint32_t m) const { return vh_bits_sum_at(v, D->moff[j], D->mbits[j], m); }
+  __device__ __forceinline__ uint32_t min(int j, const uint32_t (&v)[VH_BITS_MAX_FIELD], uint32_t m) const { bool e; return vh_bits_min_at(v, D->moff[j], D->mbits[j], m, &e); }
+  __device__ __forceinline__ uint32_t max(int j, const uint32_t (&v)[VH_BITS_MAX_FIELD], uint32_t m) const { bool e; return vh_bits_max_at(v, D->moff[j], D->mbits[j], m, &e); }
+  __device__ __forceinline__ uint32_t field(int j, uint32_t rec) const { return vh_bits_row_field(rec, D->moff[j], D->mbits[j]); }
+  __device__ __forceinline__ bool gid(uint32_t rec, uint64_t* id) const { return vh_bits_row_gid(rec, P.ngroup, P.g, D->goff, D->gbits, id); }
+};
+
 // The loop over the group ids of ONE plan for a lane's plane word. v: every plane of V the plan needs, for the lane's 32 rows (planes the plan
 // does not need may hold anything: care, pat and the fields name the ones that are looked at); mask: the lane's passing rows; lds: the plan's
 // LDS table. Every branch is on the plan, so all 64 lanes are active in it, which the wave combination needs — the caller must be in uniform
 // control flow too. Per id g: the lane's rows of g, nothing more to do when no lane has any, and per metric the lane's partial result, combined
 // across the wave (the DPP scans of vh_wave_scan.h) and added to the LDS table by ONE lane: one LDS update per (chunk, group, metric) in
 // place of one per row and metric. Returns whether a passing row of the lane belongs to no id (a value outside the planned range).
-__device__ __forceinline__ bool vh_plane_agg_groups(const VhPlanDev& P, const VhPlaneAggDesc* __restrict__ D, uint32_t care, uint64_t valid, uint32_t G,
-                                                    char* lds, const uint32_t (&v)[VH_BITS_MAX_FIELD], uint32_t mask, int lane) {
+template <class T>
+__device__ __forceinline__ bool vh_plane_agg_groups_t(const T& t, const VhPlanDev& P, const VhPlaneAggDesc* __restrict__ D, uint32_t care, uint64_t valid, uint32_t G,
+                                                      char* lds, const uint32_t (&v)[VH_BITS_MAX_FIELD], uint32_t mask, int lane) {
   uint32_t seen = 0u;
 #pragma unroll 1
   for (uint32_t g = 0; g < G; ++g) {
@@ -26,24 +52,24 @@ __device__ __forceinline__ bool vh_plane_agg_groups(const VhPlanDev& P, const Vh
     seen |= mg;
     if (__ballot(mg != 0u) == 0ull) continue;
     const bool in = mg != 0u;
-#pragma unroll 1
-    for (int j = 0; j < P.nmetric; ++j) {
-      const VhMetricDev& m = P.m[j];
-      const int sop = (int)m.sop();
-      const uint32_t off = D->moff[j], nb = D->mbits[j];
+    t.each_metric([&](auto j) __attribute__((always_inline)) {
+      const int sop = t.sop(j);
       // the lanes' partial results combined by DPP scans (vh_wave_scan.h; all lanes are active here): lane 63 ends up with the wave's. A
       // field's value is an unsigned number of at most 32 bits, so MAX takes 0 from a lane without a row of g and MIN is the complement
       // of the MAX of the complements.
       uint64_t total;
-      bool empty;
-      if (sop == SOP_ADD32 || sop == SOP_ADD64) total = vh_wave_incl_add((unsigned long long)vh_bits_sum_at(v, off, nb, mg));
-      else if (sop == SOP_MIN_I32 || sop == SOP_MIN_U32 || sop == SOP_MIN_I64 || sop == SOP_MIN_U64) total = (uint32_t)~vh_wave_incl_max(in ? ~vh_bits_min_at(v, off, nb, mg, &empty) : 0u);
-      else total = vh_wave_incl_max(in ? vh_bits_max_at(v, off, nb, mg, &empty) : 0u);
-      if (lane == 63) vh_state_update<__HIP_MEMORY_SCOPE_WORKGROUP>(lds + m.lds_off, g, sop, total);
-    }
+      if (sop == SOP_ADD32 || sop == SOP_ADD64) total = vh_wave_incl_add((unsigned long long)t.sum(j, v, mg));
+      else if (sop == SOP_MIN_I32 || sop == SOP_MIN_U32 || sop == SOP_MIN_I64 || sop == SOP_MIN_U64) total = (uint32_t)~vh_wave_incl_max(in ? ~t.min(j, v, mg) : 0u);
+      else total = vh_wave_incl_max(in ? t.max(j, v, mg) : 0u);
+      if (lane == 63) vh_state_update<__HIP_MEMORY_SCOPE_WORKGROUP>(lds + P.m[j].lds_off, g, sop, total);
+    });
     if (lane == 63) reinterpret_cast<uint8_t*>(lds + P.lds_present_off)[g] = 1;
   }
   return (mask & ~seen) != 0u;
+}
+__device__ __forceinline__ bool vh_plane_agg_groups(const VhPlanDev& P, const VhPlaneAggDesc* __restrict__ D, uint32_t care, uint64_t valid, uint32_t G,
+                                                    char* lds, const uint32_t (&v)[VH_BITS_MAX_FIELD], uint32_t mask, int lane) {
+  return vh_plane_agg_groups_t(VhPlaneAggPlan{P, D}, P, D, care, valid, G, lds, v, mask, lane);
 }
 
 // The ROW SINK: the same contract as vh_plane_agg_groups — a lane's plane words of V and its pass mask in, the plan's updates of its LDS table
@@ -62,9 +88,9 @@ __device__ __forceinline__ bool vh_plane_agg_groups(const VhPlanDev& P, const Vh
 #define VH_PLANE_ROWS_SLICE_BITS 8
 #define VH_PLANE_ROWS_SLICES (32 / VH_PLANE_ROWS_SLICE_BITS)
 #define VH_PLANE_ROWS_QUEUE (64 * VH_PLANE_ROWS_SLICE_BITS)      // 512 entries of 2 bytes: 1 KB per wave
-__device__ __forceinline__ bool vh_plane_agg_rows(const VhPlanDev& P, const VhPlaneAggDesc* __restrict__ D, char* lds, const uint32_t (&v)[VH_BITS_MAX_FIELD],
-                                                  uint32_t mask, int lane, uint16_t* q) {
-  const uint32_t need = D->need;
+template <class T>
+__device__ __forceinline__ bool vh_plane_agg_rows_t(const T& t, const VhPlanDev& P, char* lds, const uint32_t (&v)[VH_BITS_MAX_FIELD], uint32_t mask, int lane, uint16_t* q) {
+  const uint32_t need = t.need();
   bool range_err = false;
 #pragma unroll 1
   for (int k = 0; k < VH_PLANE_ROWS_SLICES; ++k) {
@@ -90,14 +116,12 @@ __device__ __forceinline__ bool vh_plane_agg_rows(const VhPlanDev& P, const VhPl
       for (int p = 0; p < VH_BITS_MAX_FIELD; ++p)
         if ((need >> p) & 1u) rec |= vh_bits_row_bit((uint32_t)__builtin_amdgcn_ds_bpermute((int)(s << 2), (int)v[p]), r, (uint32_t)p);
       uint64_t gid = 0;
-      const bool in = vh_bits_row_gid(rec, P.ngroup, P.g, D->goff, D->gbits, &gid);
+      const bool in = t.gid(rec, &gid);
       range_err |= act && !in;
       if (act && in) {
-#pragma unroll 1
-        for (int j = 0; j < P.nmetric; ++j) {
-          const VhMetricDev& m = P.m[j];
-          vh_state_update<__HIP_MEMORY_SCOPE_WORKGROUP>(lds + m.lds_off, gid, (int)m.sop(), (uint64_t)vh_bits_row_field(rec, D->moff[j], D->mbits[j]));
-        }
+        t.each_metric([&](auto j) __attribute__((always_inline)) {
+          vh_state_update<__HIP_MEMORY_SCOPE_WORKGROUP>(lds + P.m[j].lds_off, gid, t.sop(j), (uint64_t)t.field(j, rec));
+        });
         reinterpret_cast<uint8_t*>(lds + P.lds_present_off)[gid] = 1;
       }
     }
@@ -105,5 +129,9 @@ __device__ __forceinline__ bool vh_plane_agg_rows(const VhPlanDev& P, const VhPl
   }
   // the lane that drained a row is not the lane that owns it: every lane of the wave answers for the wave's rows
   return __ballot(range_err) != 0ull;
+}
+__device__ __forceinline__ bool vh_plane_agg_rows(const VhPlanDev& P, const VhPlaneAggDesc* __restrict__ D, char* lds, const uint32_t (&v)[VH_BITS_MAX_FIELD],
+                                                  uint32_t mask, int lane, uint16_t* q) {
+  return vh_plane_agg_rows_t(VhPlaneAggPlan{P, D}, P, lds, v, mask, lane, q);
 }
 #endif

@@ -22,6 +22,7 @@ struct VhWhatRan {
   bool build_pending = false;
   bool grouped = false, gplanes = false, subtrim = false, gpspan = false;
   bool sliced_prebuilt = false, plane_agg = false;      // the two pre-built readers of the bit-sliced planes
+  bool plane_jit = false;                               // ... the second of them in its compiled form (VH_PLAN2_PLANE_JIT): plane_agg is set too
 };
 
 // The word of a query that planned a scan.
@@ -58,6 +59,8 @@ static inline uint32_t vh_info_compose(const VhWhatRan& w) {
   if (w.sliced_prebuilt) bits = (bits & ~no_reader) | VH_INFO_SLICED_PREBUILT | on_planes;
   // the plane aggregate reports no projection — it gathers no payload, whatever choose_projection had found — and is not the pre-built scan
   if (w.plane_agg) bits = (bits & ~(no_reader | VH_INFO_SLICED_PREBUILT | VH_INFO_PROJECTION)) | VH_INFO_PLANE_AGG | on_planes;
+  // ... whose compiled form is a compiled kernel all the same: bit 27's word plus bit 5
+  if (w.plane_agg && w.plane_jit) bits |= VH_INFO_JIT;
   return bits;
 }
 

@@ -237,7 +237,97 @@ int QueryBuild::plan_again(bool keep_part, bool no_hashed_part) {
   return query_launch_locked(t, x, &p2, out, o2);
 }
 
+// No compiled kernel for a plan that asked for the COMPILED aggregate on the planes and met the rest of its rule: the same plan with
+// VH_PLAN2_PLANE_AGG in the flag's place, for the pre-built kernels — choose_plane_agg then takes it (bit 27 without bit 5). A member of a
+// batch stays the single query it is.
+int QueryBuild::plan_again_prebuilt_planes() {
+  vh_plan p2 = *p;
+  p2.flags |= VH_PLAN_NO_JIT;
+  p2.flags2 = (p2.flags2 & ~(uint32_t)VH_PLAN2_PLANE_JIT) | VH_PLAN2_PLANE_AGG;
+  VhLaunchOpts o2 = o;
+  o2.fuse = nullptr;
+  holder.reset();
+  done = true;
+  return query_launch_locked(t, x, &p2, out, o2);
+}
+
+// The aggregate ON the bit-sliced planes by a kernel compiled for this plan's shape (include/viya_hip.h, "Aggregates on the bit-sliced planes,
+// compiled"; the frame is vh_jit_planes.h): asked for (pagg_jit), a compiled kernel may run the query at all (jit_try: the JIT policy, the
+// plan's flags, VH_JIT_MIN_ROWS), and the rest of the rule holds (plane_agg_rule, the pre-built choice's own). The shape handed to the
+// generator is then the plane aggregate's, not the scan's the plan would otherwise get: the filter's fields in F (slot pp_slot, as the
+// bit-sliced compacting scan finds them), V in a slot of its own unless it is F, every group column's and every metric's field in V, the
+// metrics' kinds and the sink — nothing that is data: the ids' patterns, which rest on lo / extent / stride, stay in the descriptor.
+// *settled: this function has answered (kernel at hand, or the query handed to a second plan); false: the flag changes nothing.
+int QueryBuild::compile_plane_agg(bool* settled) {
+  *settled = false;
+  VhPredPack *f = nullptr, *v = nullptr;
+  if (!pagg_jit || !jit_try || !plane_agg_rule(&f, &v)) return VH_OK;
+  *settled = true;
+  // F and V in the plan's LAST two slots, whatever the plan's own slots hold: which narrow copies and projections exist — they come and go
+  // with the automatic layouts — must not make another shape, and another compile, of the same query. V's slot is F's when V is F.
+  const int fslot = VH_MAX_SLOTS - 2, vslot = f && v == f ? fslot : VH_MAX_SLOTS - 1;
+  // No shape for this plan — its last two slots taken, more columns than a shape names, or more filter planes than the 64 registers the
+  // compiled scan allows itself for them (compile_kernel below: beyond that the array would spill) —: the pre-built plane kernel, quietly, even
+  // under VH_PLAN_FORCE_JIT (include/viya_hip.h lists these beside the other "no compiled kernel can be had" cases).
+  int filter_planes = 0;
+  for (int k = 0; pagg_filter && k < jshape.npred; ++k) filter_planes += pp_sbits[k];
+  if (P.nslots > fslot || P.ngroup > VJ_MAX_COLS || P.nmetric > VJ_MAX_COLS || (pagg_filter && !jshape.pp_sliced) || filter_planes > 64) return plan_again_prebuilt_planes();
+  if (f) { P.colbase[fslot] = f->plane[0].ptr; P.colstride[fslot] = f->plane[0].stride; P.colpitch[fslot] = (uint32_t)f->pitch; }
+  P.colbase[vslot] = v->plane[0].ptr; P.colstride[vslot] = v->plane[0].stride; P.colpitch[vslot] = (uint32_t)v->pitch;
+  VhJitShape js;
+  js.mode = mode; js.block = 256;
+  js.xcd = nxcd > 1 ? 1 : 0;
+  js.scope = nxcd > 1 ? (int)__HIP_MEMORY_SCOPE_WORKGROUP : (int)__HIP_MEMORY_SCOPE_AGENT;      // (vh_launch_scan_planes: vh_with_scope)
+  if (pagg_filter) {
+    js.prog = jshape.prog; js.nlits = jshape.nlits; js.npred = jshape.npred;
+    js.pp_sliced = 1; js.pp_slot = fslot;
+    for (int k = 0; k < js.npred; ++k) { js.pred[k] = VhJitPred{-1, jshape.pred[k].type, 0}; js.pp_off[k] = pp_soff[k]; js.pp_bits[k] = pp_sbits[k]; }      // (the planes' fields; no column is streamed)
+  } else {
+    VhProgOp all{};
+    all.set_kind(VH_F_TRUE);
+    js.prog = {all};
+  }
+  js.pa_sink = pagg_desc.rows ? 2 : 1; js.pa_filter = pagg_filter ? 1 : 0; js.pa_vslot = vslot;
+  js.ng = P.ngroup; js.nm = P.nmetric;
+  for (int i = 0; i < P.ngroup; ++i) { js.pa_goff[i] = (int)pagg_desc.goff[i]; js.pa_gbits[i] = (int)pagg_desc.gbits[i]; }
+  for (int j = 0; j < P.nmetric; ++j) { js.m[j].sop = (int)P.m[j].sop(); js.pa_moff[j] = (int)pagg_desc.moff[j]; js.pa_mbits[j] = (int)pagg_desc.mbits[j]; }
+  // the kernel: looked up or compiled exactly as the scan's is below (background build mode: the worker's job, pending is not failure)
+  std::string jerr;
+  VhJitKernel* k = nullptr;
+  bool pending = false;
+  if (build_background(t)) {
+    if (vh_jit_peek(js, &k, &jerr) == 0) pending = build_request_kernel(t, js);
+    if (!pending && !k && jerr.empty()) jerr = "the build worker is shutting down";
+  } else {
+    VhJitKernel* had = nullptr;
+    std::string ignored;
+    const bool known = vh_jit_peek(js, &had, &ignored) != 0;
+    k = vh_jit_get(js, &jerr);
+    if (!known) ++t->inline_builds;
+  }
+  if (pending) {
+    ++g_build_quiet;
+    const int prc = plan_again_prebuilt_planes();
+    --g_build_quiet;
+    if (!prc && out && *out) (*out)->info.reserved |= VH_INFO_BUILD_PENDING;
+    return prc;
+  }
+  if (!k) {
+    if (knobs().jit_verbose) fprintf(stderr, "vh: compiled aggregate on the planes unavailable, the pre-built one answers: %s\n", jerr.c_str());
+    if ((p->flags & VH_PLAN_FORCE_JIT) || vh_jit_policy() == VH_JIT_FORCE) return vh_fail(VH_E_UNSUPPORTED, "per-query kernel requested (VH_PLAN_FORCE_JIT / VH_JIT=force) but unavailable: %s", jerr.c_str());
+    return plan_again_prebuilt_planes();
+  }
+  pagg_jk = k;
+  plane_agg_take(f, v);
+  return VH_OK;
+}
+
 int QueryBuild::compile_kernel() {
+  {   // ---------------- the aggregate on the planes, compiled, where the plan asked for it: then no scan over rows is compiled at all
+    bool settled = false;
+    if (int rc = compile_plane_agg(&settled)) return rc;
+    if (settled) return VH_OK;
+  }
   // ---------------- the scan kernel compiled for this plan shape (vh_jit.hip), when there is to be one
   // the no-compaction kernels are pre-built, except DENSE_LDS's over plain 4- / 8-byte arena columns (C2's shape), which has a compiled form
   if (jit_try && lanes && (mode != VH_MODE_DENSE_LDS || test_env("VH_TEST_NO_JIT_LANES"))) jit_try = false;
@@ -395,9 +485,22 @@ void QueryBuild::choose_sliced_prebuilt() {
 // ids (D.rows; vh_plane_agg.h) —, no filter or the select's rule on one current projection F (planes_ready), plain group columns, integer SUM / COUNT / AVG / MIN / MAX states
 // only, and ONE usable, current bit-sliced projection V with every group column and every metric's source column, the hidden count included
 // (F itself when it has them). Whether the plan settled on the lanes form plays no part. It only changes which kernel fills the block's LDS
-// table. F and V are stamped and held; nothing is built or queued.
+// table. F and V are stamped and held; nothing is built or queued. The rule but for "no compiled kernel" is plane_agg_rule, which the compiled
+// form (compile_plane_agg, VH_PLAN2_PLANE_JIT) calls too: the two cannot drift.
 void QueryBuild::choose_plane_agg() {
-  if (!pagg_want || jk || mode != VH_MODE_DENSE_LDS || (P.G > VH_PLANE_AGG_MAX_GROUPS && !pagg_rows) || P.nbitset) return;
+  if (plane_agg || jk) return;      // (settled already, by its compiled form: compile_plane_agg; or a compiled scan runs the query)
+  VhPredPack *f = nullptr, *v = nullptr;
+  if (plane_agg_rule(&f, &v)) plane_agg_take(f, v);
+}
+void QueryBuild::plane_agg_take(VhPredPack* f, VhPredPack* v) {
+  plane_agg = true;
+  pagg_ref.rows = pagg_desc.rows;      // (here, not with the rest of pagg_ref in layout_scratch: decompose_work asks the launcher for the kernel's name and occupancy first)
+  pagg_v = v;
+  if (f) layout_use(t, f);
+  layout_use(t, v);
+}
+bool QueryBuild::plane_agg_rule(VhPredPack** fp, VhPredPack** vp) {
+  if (!pagg_want || mode != VH_MODE_DENSE_LDS || (P.G > VH_PLANE_AGG_MAX_GROUPS && !pagg_rows) || P.nbitset) return false;
   // The row sink takes a plan that asked for it (VH_PLAN2_PLANE_ROWS) from one id beyond the loop's bound on; the test hook moves that threshold
   // down, so that one process runs the same small plan through both sinks.
   uint64_t rows_min = VH_PLANE_AGG_MAX_GROUPS + 1;
@@ -405,25 +508,25 @@ void QueryBuild::choose_plane_agg() {
   const bool rows = pagg_rows && P.G >= rows_min;
   VhPredPack* f = nullptr;
   if (pagg_filter) {
-    if (!planes_ready || !sliced_use || sliced_use->applied_epoch != t->sync_epoch) return;
+    if (!planes_ready || !sliced_use || sliced_use->applied_epoch != t->sync_epoch) return false;
     f = sliced_use;
   }
   std::vector<int> cols;
   for (int i = 0; i < P.ngroup; ++i) {
-    if (P.g[i].gran() != VH_T_NONE || P.g[i].nroll()) return;
+    if (P.g[i].gran() != VH_T_NONE || P.g[i].nroll()) return false;
     cols.push_back(p->groups[i].col);
   }
   for (int j = 0; j < P.nmetric; ++j) {
     const int sop = (int)P.m[j].sop();
     const bool integer = sop == SOP_ADD32 || sop == SOP_ADD64 || (sop >= SOP_MIN_I32 && sop <= SOP_MAX_U64);
-    if (!integer || P.m[j].slot() == VH_SLOT_ROWID || metric_col[j] < 0) return;
+    if (!integer || P.m[j].slot() == VH_SLOT_ROWID || metric_col[j] < 0) return false;
     cols.push_back(metric_col[j]);
   }
   std::sort(cols.begin(), cols.end());
   cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
-  if (cols.empty()) return;
+  if (cols.empty()) return false;
   VhPredPack* v = f && std::includes(f->cols.begin(), f->cols.end(), cols.begin(), cols.end()) ? f : predpack_usable(t, cols, 1);
-  if (!v || !v->sliced || v->bits > VH_BITS_MAX_FIELD || v->applied_epoch != t->sync_epoch) return;
+  if (!v || !v->sliced || v->bits > VH_BITS_MAX_FIELD || v->applied_epoch != t->sync_epoch) return false;
 
   VhPlaneAggDesc& D = pagg_desc;
   D = VhPlaneAggDesc{};
@@ -448,11 +551,8 @@ void QueryBuild::choose_plane_agg() {
     D.pat[g] = pat;
     if (fits) D.valid |= 1ull << g;
   }
-  plane_agg = true;
-  pagg_ref.rows = D.rows;      // (here, not with the rest of pagg_ref in layout_scratch: decompose_work asks the launcher for the kernel's name and occupancy first)
-  pagg_v = v;
-  if (f) layout_use(t, f);
-  layout_use(t, v);
+  *fp = f; *vp = v;
+  return true;
 }
 
 // The one place that decides which scan kernel runs. L brings the grid to launch — or, with L.occ / L.name set, what the chosen launcher is to
@@ -465,7 +565,11 @@ void QueryBuild::scan_dispatch(VhScanLaunch L) {
   L.stream = x->stream();
   if (plane_agg) {      // (no queue: the block's LDS table alone)
     L.lds = lds_table;
-    vh_launch_scan_planes(P, pagg_ref, chunks_per_seg, L, xcd_private);
+    if (pagg_jk) {      // ... compiled for this plan's shape: plan, descriptor and chunks per segment (the row sink's queue is static LDS of the kernel)
+      if (L.occ) *L.occ = vh_jit_occupancy(pagg_jk, BLOCK, lds_table);
+      else if (!L.name) (void)vh_jit_launch_planes(pagg_jk, P, pagg_ref.D, chunks_per_seg, L.grid, BLOCK, lds_table, L.stream);
+    }
+    else vh_launch_scan_planes(P, pagg_ref, chunks_per_seg, L, xcd_private);
   }
   else if (sliced_prebuilt) {
     if (mode == VH_MODE_DENSE_PART) L.lds = qb;
@@ -501,6 +605,9 @@ int QueryBuild::decompose_work() {
   choose_plane_agg();           // (first: when both apply, the aggregate on the planes wins)
   choose_sliced_prebuilt();
   BLOCK = jk ? jit_block : mode == VH_MODE_DENSE_LDS && !plane_agg ? 1024 : 256;      // (the aggregate on the planes: 151 registers a lane, three 256-thread blocks per CU; its table has at most 64 groups to flush — with the row sink 105 registers and whatever table the organisation allows)
+  // (the compiled plane aggregate, pagg_jk, takes the same 256 threads: at its 62 - 80 registers up to eight blocks fit a CU (occ_cap below) where
+  // the pre-built kernel has three, i.e. more table flushes per CU. Block size and blocks per CU were NOT measured separately for it:
+  // profiles/r21/NOTES.md shows the result of this choice only)
   if (mode == VH_MODE_DENSE_LDS && lanes && !plane_agg) {
     if (env_lanes_block == 256 || env_lanes_block == 512 || env_lanes_block == 1024) BLOCK = env_lanes_block;
     else if ((uint64_t)g_ctx.num_cu * 5 * G * std::max(1, P.nmetric) <= rows_to_scan / 32) BLOCK = 256;
@@ -510,9 +617,10 @@ int QueryBuild::decompose_work() {
   {   // the kernel symbol(s) this query runs, as rocprofv3 prints them (vh_result_kernel: bench.py's roofline.kernel)
     char nm[160] = "";
     VhScanLaunch ask;
-    ask.occ = env_bpc <= 0 ? &occupancy : nullptr; ask.name = jk ? nullptr : nm; ask.name_cap = sizeof(nm);
+    const VhJitKernel* compiled = jk ? jk : pagg_jk;
+    ask.occ = env_bpc <= 0 ? &occupancy : nullptr; ask.name = compiled ? nullptr : nm; ask.name_cap = sizeof(nm);
     if (ask.occ || ask.name) scan_dispatch(ask);
-    r->kernel = jk ? jk->name : std::string(nm);
+    r->kernel = compiled ? compiled->name : std::string(nm);
     if (hpart) {      // (the scatter kernel runs twice per query, level A and level B: named twice, so that per-query sums over the names count it twice)
       char hn[160];
       if (hp_fan) snprintf(hn, sizeof(hn), " + hp_ring_scatter_kernel<1024, %d> + ", hp_units);      // (the scan wrote level A itself; level B without barriers)
@@ -975,6 +1083,7 @@ int QueryBuild::launch() {
   w.pp_planes = jshape.pp_nplanes != 0; w.pp_sliced = jshape.pp_sliced != 0; w.qpay = jshape.qpay != 0;
   w.has_set = has_set; w.set_search = set_search; w.set_truth = set_truth; w.build_pending = build_pending;
   w.grouped = grouped; w.gplanes = gplanes; w.subtrim = subtrim; w.gpspan = gpspan; w.sliced_prebuilt = sliced_prebuilt; w.plane_agg = plane_agg;
+  w.plane_jit = plane_agg && pagg_jk != nullptr;
   r->info.reserved = vh_info_compose(w);
   r->plane_sink = !plane_agg ? 0u : pagg_desc.rows ? 2u : 1u;      // (vh_result_plane_sink: `reserved` has no bit left for it)
   r->fast_scan = w.fast;      // (VH_INFO_FAST as planned: a pre-built reader of the planes clears the bit in the result's word)
@@ -1003,7 +1112,7 @@ int QueryBuild::launch() {
   if (g_heavy.only && !from_tuples && g_heavy.epoch != t->sync_epoch)       // the table has moved on since the first pass: its rows are no longer the rows that pass saw
     return vh_fail(VH_E_RANGE, "second pass over heavy ranges: the table changed since the first pass");      // (heavy_pass_finish gives up; the caller re-plans the whole query)
   if (from_tuples) {
-  } else if (P.total_units && plane_agg && o.fuse) {
+  } else if (P.total_units && plane_agg && o.fuse && !pagg_jit) {      // (a member that asked for the compiled form is answered as the single query it is)
     // A member of a batch whose scan may share a fused launch (vh_query_agg_batch): everything up to ev[1] is enqueued; the scan and what
     // follows it are the batch's to launch, once it knows the groups. The plan goes by value: it is complete here.
     VhDeferredScan& d = o.fuse->scan[o.fuse->member];

@@ -325,6 +325,7 @@ struct QueryBuild {
   // The aggregate ON the bit-sliced planes (scan_agg_planes_kernel; opt-in: VH_PLAN2_PLANE_AGG, or VH_PLANE_AGG=1 for the process). Its filter is the
   // program above (planes_prog over sliced_use = F), or none.
   bool pagg_want = false;                        // shape_filter: asked for, not a sharded query, none of the flags that keep a plan off the planes
+  bool pagg_jit = false;                         // ... by a kernel compiled for the plan's shape where one may run (VH_PLAN2_PLANE_JIT / VH_PLANE_JIT=1): compile_kernel
   bool pagg_rows = false;                        // ... with VH_PLAN2_PLANE_ROWS: more than VH_PLANE_AGG_MAX_GROUPS ids take the row sink
   bool pagg_filter = false;                     // ... and the filter has a leaf (nodes that are always true alone: no program, as with no filter)
   size_t pagg_word = 0;                          // snapshot_segments: the descriptor's u32 word in the plan block (behind the program)
@@ -332,7 +333,14 @@ struct QueryBuild {
   bool plane_agg = false;                        // ... and the rule holds: the kernel runs
   VhPlaneAggDesc pagg_desc{};
   VhPlaneAggRef pagg_ref{};                      // layout_scratch: the kernel's view of program, descriptor and the two projections
+  // The rule but for its clause on compiled kernels — the organisation, the id bound, F, V, the group columns, the states —, and the descriptor
+  // filled in when it holds: ONE function, which the pre-built choice (choose_plane_agg) and the compiled one (compile_plane_agg) both call.
+  bool plane_agg_rule(VhPredPack** f, VhPredPack** v);
+  void plane_agg_take(VhPredPack* f, VhPredPack* v);      // the rule holds and a kernel is at hand: the plan is the plane aggregate's, F and V are stamped and held
   void choose_plane_agg();
+  VhJitKernel* pagg_jk = nullptr;                // compile_kernel: the plane aggregate's kernel compiled for this plan's shape (jk stays null: no scan over rows is compiled)
+  int compile_plane_agg(bool* settled);          // compile_kernel's first step for a plan that asked (pagg_jit)
+  int plan_again_prebuilt_planes();              // ... and its way out where no compiled kernel can be had: the same plan with VH_PLAN2_PLANE_AGG in the flag's place
   VhJitKernel* jk = nullptr;
   bool build_pending = false;                    // background build mode: a job for this query's shape is queued or running (vh_result_info.reserved bit 19)
   int jit_block = 256;
@@ -578,7 +586,9 @@ int QueryBuild::shape_filter() {
   // ... and so does one that asks to be computed on the planes (VH_PLAN2_PLANE_AGG), unless it has no filter: then it needs no program.
   // Sharded queries (an agreed plan, a summary call, rows kept on the device for the exchange) ignore that switch.
   // VH_PLAN2_PLANE_ROWS asks for the same, and lifts the bound on the group ids: beyond it the row sink answers (choose_plane_agg).
-  pagg_want = planes_allowed && ((p->flags2 & (VH_PLAN2_PLANE_AGG | VH_PLAN2_PLANE_ROWS)) || knobs().plane_agg) && !o.ag && !o.summary_out && !o.device_rows;
+  // VH_PLAN2_PLANE_JIT asks for the same, and for a kernel compiled for the plan's shape wherever one may run (compile_plane_agg).
+  pagg_want = planes_allowed && ((p->flags2 & (VH_PLAN2_PLANE_AGG | VH_PLAN2_PLANE_ROWS | VH_PLAN2_PLANE_JIT)) || knobs().plane_agg || knobs().plane_jit) && !o.ag && !o.summary_out && !o.device_rows;
+  pagg_jit = pagg_want && ((p->flags2 & VH_PLAN2_PLANE_JIT) || knobs().plane_jit);
   pagg_rows = pagg_want && (p->flags2 & VH_PLAN2_PLANE_ROWS) != 0;
   for (const VhProgOp& o : prog) pagg_filter |= o.kind() == VH_F_REL || o.kind() == VH_F_IN || o.kind() == VH_F_INSET;
   planes_want = sliced_asked || (pagg_want && pagg_filter);

@@ -78,7 +78,7 @@ static const char* test_env(const char* name) {
   return hooks ? getenv(name) : nullptr;
 }
 struct VhKnobs {
-  bool trace_alloc, no_topk, jit_verbose, skip_phase2, no_direct_emit, times, no_jit_pagg, predpack_bytes, build_background, sliced_prebuilt, plane_agg;
+  bool trace_alloc, no_topk, jit_verbose, skip_phase2, no_direct_emit, times, no_jit_pagg, predpack_bytes, build_background, sliced_prebuilt, plane_agg, plane_jit;
   int max_exec, prepare_place, auto_narrow, auto_pack, jit_ablate, hp_ablate, hp_bpp, pack_plain, lanes_block, blocks_per_cu, unit_rows, grid, ext_tuples, ext_pad, bw_blocks_per_cu, hp_stream, hp_regions, hp_agg_waves, deliver_blocks;
   double hp_load_g, hp_load_s, qpay_min_sel;
   uint64_t layout_budget;
@@ -97,6 +97,7 @@ static const VhKnobs& knobs() {
     { const char* e = getenv("VH_LAYOUT_BUDGET"); x.layout_budget = e ? strtoull(e, nullptr, 10) : 0; }      // bytes the derived layouts of a new table may hold (0: no budget; vh_table_set_layout_budget, vhh_derived.h)
     { const char* e = getenv("VH_SLICED_PREBUILT"); x.sliced_prebuilt = e && atoi(e) != 0; }      // every aggregate plan of the process carries VH_PLAN_SLICED_PREBUILT (opt-in: profiles/r14/NOTES.md)
     { const char* e = getenv("VH_PLANE_AGG"); x.plane_agg = e && atoi(e) != 0; }      // ... VH_PLAN2_PLANE_AGG (opt-in: profiles/r15/NOTES.md)
+    { const char* e = getenv("VH_PLANE_JIT"); x.plane_jit = e && atoi(e) != 0; }      // ... VH_PLAN2_PLANE_JIT (opt-in: profiles/r21/NOTES.md)
     x.hp_stream = num("VH_HP_STREAM", 0);             // chunk launches of a streamed result (0: off — measured: the link, not the wait for the kernels, bounds the delivery; profiles/r04/NOTES.md)
     x.qpay_min_sel = real("VH_QPAY_MIN_SEL", 0.15);        // selectivity from which the compiled scan streams 4-byte payload records instead of gathering them (measured: profiles/r05/NOTES.md)
     // What rounds 2-5 could switch from the environment for a measurement and round 6 fixed at the measured value (the notes of the round that

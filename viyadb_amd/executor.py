@@ -120,6 +120,12 @@ class AggResult:
         return bool(self.flags & capi.INFO_PLANE_AGG)
 
     @property
+    def plane_jit(self) -> bool:
+        """... by a kernel compiled for the plan's shape (PLAN2_PLANE_JIT / VH_PLANE_JIT=1): bits 27 and 5 together, so `jit` and `plane_agg`
+        are both true for such a result. Derived from `flags`, like plane_agg."""
+        return self.flags & (capi.INFO_PLANE_AGG | capi.INFO_JIT) == capi.INFO_PLANE_AGG | capi.INFO_JIT
+
+    @property
     def plane_sink(self) -> int:
         """Which sink of the aggregate on the planes filled the table (vh_result_plane_sink): 0 the result is no plane aggregate, 1 the loop
         over group ids, 2 the row sink (PLAN2_PLANE_ROWS and more than 64 ids). Set by _collect; no field of its own (0 for a record built
