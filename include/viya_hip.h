@@ -593,8 +593,15 @@ VH_API int vh_query_agg(vh_table* t, const vh_plan* plan, vh_result** out);
  * members' values must not be added up; vh_batch_info.fused_kernel_ms is the sum over the launches). A member that takes the row sink
  * (VH_PLAN2_PLANE_ROWS and more than 64 ids) is a candidate like any other, shares or lends a mask like any other, and the 48 KB bound
  * on the tables is what limits it; a launch with such a member is named scan_agg_planes_batch_kernel<256, S, rows> and runs the row sink
- * for it and the loop for the others. A member that carries VH_PLAN2_PLANE_JIT (or runs under VH_PLANE_JIT=1) is NO candidate, whether
- * its compiled kernel or the pre-built one ends up answering it: the fused kernel is pre-built. A group of one, and every member that
+ * for it and the loop for the others. A member that carries VH_PLAN2_PLANE_JIT (or runs under VH_PLANE_JIT=1) and has the kernel compiled
+ * for its own shape at hand is a COMPILED candidate: compiled candidates group with compiled candidates only, pre-built ones with pre-built
+ * ones, under the same key and the same two bounds. A compiled group is answered by ONE launch of a kernel compiled for its BATCH SHAPE —
+ * the ordered list of its members' shapes, which member takes whose mask, and the memory scope ("Aggregates on the bit-sliced planes,
+ * compiled" below) —: the same walk, the same single load of V and the same sharing, with one more condition for sharing: the two
+ * members' filter texts are equal. Such a member has bits 30, 27 and 5, vh_result_kernel names the batch kernel (viya_jit_scan_...,
+ * the same for every member of the launch and not the name of any member's own kernel), and everything else is as for a pre-built
+ * launch. A member that carries the flag and has NO compiled kernel of its own (VH_JIT=off, VH_PLAN_NO_JIT, a pending or failed compile, no
+ * shape) is no candidate and is answered as the single query it is, by the pre-built plane kernel. A group of one, and every member that
  * is no candidate, runs as the single query it is: the flags and the kernel name its vh_query_agg would give, bit 30 clear. A fused member
  * that has to be planned again (a value synced in beyond the planned range) is answered alone by vh_query_agg's re-plan loop; the others stand.
  *
@@ -606,7 +613,7 @@ VH_API int vh_query_agg(vh_table* t, const vh_plan* plan, vh_result** out);
 typedef struct vh_batch_info {
   uint32_t nplans, fused_groups, fused_members, singles;   /* members in all / fused launches / members they answered / members answered singly */
   float fused_kernel_ms;     /* HIP-event time of the fused launches, summed */
-  uint32_t reserved;
+  uint32_t reserved;         /* how many of fused_groups were COMPILED fused launches (VH_PLAN2_PLANE_JIT members: one kernel per batch shape) */
 } vh_batch_info;
 VH_API int vh_query_agg_batch(vh_table* t, const vh_plan* const* plans, uint32_t n, vh_result** out /* n */, vh_batch_info* info /* may be NULL */);
 /* A result's place in a fused launch of vh_query_agg_batch (test and measurement support, like vh_result_tail). All zeros for a result of
@@ -805,7 +812,17 @@ VH_API int vh_query_agg_sharded(vh_table* t, const vh_plan* plan, vh_comm* comm,
  * plan a compiled kernel may answer BEFORE the kernel is chosen is as without the flag and is not undone: the selectivity probe runs, and
  * the table's automatic layouts (VH_AUTO_PACK, VH_AUTO_NARROW) count the query and may build or queue a projection this path never reads. vh_query_agg_sharded ignores the flag. Reported:
  * vh_result_info.reserved bits 27 AND 5, bits 4 / 11 / 13 (22 / 25) as for bit 27, bits 0 / 1 / 26 clear; vh_result_kernel gives the
- * compiled kernel's name; vh_result_plane_sink 1 or 2 as above. */
+ * compiled kernel's name; vh_result_plane_sink 1 or 2 as above.
+ * In a batch (vh_query_agg_batch) two or more such members of one fuse key are answered by ONE kernel compiled for their BATCH SHAPE (the
+ * frame is vh_jit_planes_batch.h): each member's traits exactly as its own kernel has them, in launch order; per mask class one evaluation
+ * of the filter text, later members of the class taking the word out of a register; V's planes loaded once, the union of what the members
+ * with a passing row in the wave need; each member's own sink into its own table. Literals, truth tables, snapshots, lo / extent / stride,
+ * the ids' patterns and the tables' places stay data: one code object serves every batch of the shape, whatever its literals. The batch
+ * kernel is had the way a single shape's is — compiled inline and counted in vh_build_info.inline_builds, or queued with the build worker
+ * of a VH_BUILD_BACKGROUND table. While it is pending (bit 19 on those members), where its compile failed, and for a group the generator
+ * has no shape for (its mask classes' filter planes come to more than 64 together), every member of the group is launched by its own
+ * compiled kernel, the single compiled query it would have been: never an error, VH_PLAN_FORCE_JIT or not; VH_JIT_VERBOSE prints the
+ * reason. VH_TEST_NO_BATCH_SHARE=1 gives every member a mask of its own: another batch shape. */
 VH_API int vh_result_plane_sink(vh_result* r, uint32_t* sink);   /* VH_E_INVALID: a null argument */
 #define VH_COL_ROWID (-2)
 typedef struct vh_rows vh_rows;
@@ -944,6 +961,9 @@ VH_API int vh_jit_selftest(int32_t which, const char* hsaco_path, char* text, ui
 /* The name a query's kernel of canonical shape `which` would carry ("viya_jit_scan_" + eight hex digits of the shape's key): shapes that
  * differ in a member that enters the key have different names. VH_E_INVALID: no such shape. */
 VH_API int vh_jit_selftest_name(int32_t which, char* name, uint64_t name_bytes);
+/* ... and the key itself, the text the name is a hash of (what a process keeps its kernels by). VH_E_INVALID: no such shape, or a key of
+ * key_bytes characters and more (nothing is cut off). */
+VH_API int vh_jit_selftest_key(int32_t which, char* key, uint64_t key_bytes);
 
 #ifdef __cplusplus
 }

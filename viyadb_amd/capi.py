@@ -211,6 +211,12 @@ class BatchInfo(C.Structure):
     _fields_ = [("nplans", C.c_uint32), ("fused_groups", C.c_uint32), ("fused_members", C.c_uint32), ("singles", C.c_uint32),
                 ("fused_kernel_ms", C.c_float), ("reserved", C.c_uint32)]
 
+    @property
+    def compiled_groups(self) -> int:
+        """How many of fused_groups were compiled fused launches: PLAN2_PLANE_JIT members answered by one kernel compiled for their batch
+        shape (the C field keeps its name, `reserved`)."""
+        return int(self.reserved)
+
 
 class BatchMemberInfo(C.Structure):
     """vh_batch_member_info: a result's place in a fused launch of a batch and whose pass mask it used (vh_result_batch_member). All zeros
@@ -323,6 +329,7 @@ SYMBOLS = {
     "vh_measure_read_bandwidth": (C.c_int, [C.c_uint64, C.c_int32, C.POINTER(C.c_double)]),
     "vh_jit_selftest": (C.c_int, [C.c_int32, C.c_char_p, C.c_char_p, C.c_uint64]),
     "vh_jit_selftest_name": (C.c_int, [C.c_int32, C.c_char_p, C.c_uint64]),
+    "vh_jit_selftest_key": (C.c_int, [C.c_int32, C.c_char_p, C.c_uint64]),
 }
 
 _lib = None

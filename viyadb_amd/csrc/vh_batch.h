@@ -7,6 +7,9 @@
 // table updates (a private copy per XCD or not), the segments of the snapshot and the chunks per segment. Members are taken in plan order; a
 // group holds at most VH_BATCH_MAX members and VH_BATCH_LDS_CAP bytes of LDS tables, and the candidate that would pass either opens the
 // next group of its key. A group that ends up with one member is no group: that member runs as the single query it is.
+// A COMPILED candidate — a member that asked for the compiled plane aggregate and has its own kernel at hand (VH_PLAN2_PLANE_JIT: vhh_launch.h,
+// compile_plane_agg) — groups with compiled candidates only, and a pre-built one with pre-built ones: `compiled` is part of the key. A
+// compiled group is answered by ONE kernel compiled for its BATCH SHAPE, the ordered list of its members' shapes (vh_jit_planes_batch.h).
 //
 // Within ONE group, members whose pass masks are equal by construction share ONE evaluation of the mask per plane word (vh_batch_share below:
 // the MASK KEY): the dashboard's shape, K breakdowns under one filter.
@@ -24,9 +27,10 @@ struct VhFuseDesc {
   uint64_t v_serial;           // VhLayout::serial of the projection V
   uint32_t nseg, chunks_per_seg;
   uint32_t lds_bytes;          // the member's LDS table
+  uint32_t compiled;           // 1: a compiled candidate (its own compiled kernel is at hand)
 };
 static inline bool vh_fuse_same_key(const VhFuseDesc& a, const VhFuseDesc& b) {
-  return a.v_serial == b.v_serial && a.scope == b.scope && a.nseg == b.nseg && a.chunks_per_seg == b.chunks_per_seg;
+  return a.v_serial == b.v_serial && a.scope == b.scope && a.nseg == b.nseg && a.chunks_per_seg == b.chunks_per_seg && (a.compiled != 0) == (b.compiled != 0);
 }
 // group_of[i]: the group of member i, numbered from 0 in the order of the groups' first members, or -1 — the member is answered singly.
 // Returns the number of groups.
@@ -56,7 +60,9 @@ static inline uint32_t vh_batch_group(const VhFuseDesc* d, uint32_t n, int32_t* 
 //     (nprog, flat, the nprog ops, and every literal an op refers to — a REL leaf one, an IN leaf `count` of them); no set leaf in either: a
 //     set leaf's truth table lies behind a pointer into the member's own plan block, so such a program is always a class of its own;
 //   - the same effective rows in every segment (the snapshot, 0 for a skipped segment: what the planner uploads as VhPlanDev::seg_rows). One
-//     row fewer in one segment is another class: the kernel takes the leader's word as it is, the cut at the snapshot included.
+//     row fewer in one segment is another class: the kernel takes the leader's word as it is, the cut at the snapshot included;
+//   - in a COMPILED group, the same filter member-shape (filter_shape: a number the host gives equal filter texts — the program, the fields'
+//     places in F and the leaves' types as the generator sees them): the leader's evaluation is then the text this member would have had.
 // The op's words are those of VhBitsOp (vh_bits_eval.h), restated here because this file includes nothing: kind = w0 & 0xFF, count = w0 >> 24,
 // first literal = w1 & 0xFFFF; the kinds are enum vh_fkind's (include/viya_hip.h). vhh_finalize.h asserts that both still agree.
 #define VH_SHARE_KIND_REL 1u
@@ -72,6 +78,7 @@ struct VhShareDesc {
   uint32_t nlits;              // ... and how many there are room for (an op that points beyond them never shares)
   uint32_t nseg;
   const uint32_t* seg_rows;    // nseg words: the effective rows per segment
+  uint32_t filter_shape;       // compiled groups: equal numbers for equal filter member-shapes (0 throughout a pre-built group)
 };
 static inline uint32_t vh_share_op_lits(uint32_t w0) {      // literals the op refers to, from `w1 & 0xFFFF` on
   const uint32_t kind = w0 & 0xFFu;
@@ -89,6 +96,7 @@ static inline bool vh_share_prog_plain(const VhShareDesc& a) {
 }
 static inline bool vh_share_same_key(const VhShareDesc& a, const VhShareDesc& b) {
   if ((a.has_filter != 0) != (b.has_filter != 0)) return false;
+  if (a.filter_shape != b.filter_shape) return false;
   if (a.nseg != b.nseg) return false;
   for (uint32_t s = 0; s < a.nseg; ++s) if (a.seg_rows[s] != b.seg_rows[s]) return false;
   if (!a.has_filter) return true;

@@ -4,6 +4,7 @@
 #pragma once
 #include "vh_internal.h"
 #include "vh_grouped.h"
+#include "vh_batch.h"
 #include <string>
 static_assert(VH_GSUB_EQ == VH_OP_EQ && VH_GSUB_LT == VH_OP_LT && VH_GSUB_LE == VH_OP_LE && VH_GSUB_GT == VH_OP_GT && VH_GSUB_GE == VH_OP_GE, "vh_grouped.h names the relations by vh_relop's values");
 #include <vector>
@@ -92,6 +93,12 @@ struct VhJitShape {
   // metric j's, whose state operation is m[j].sop. g[] and m[] are otherwise unused: nothing is gathered. These enter key() only when set.
   int pa_sink = 0, pa_filter = 0, pa_vslot = -1;
   int pa_goff[VJ_MAX_COLS] = {}, pa_gbits[VJ_MAX_COLS] = {}, pa_moff[VJ_MAX_COLS] = {}, pa_mbits[VJ_MAX_COLS] = {};
+  // A BATCH shape (vh_jit_planes_batch.h): the ordered member shapes of one fused group of vh_query_agg_batch, 2 to VH_BATCH_MAX of them, each
+  // the plane-aggregate shape above exactly as the single query builds it, and mask_of — the position of the member whose pass mask member k
+  // takes (vh_batch.h: vh_batch_share), its own where it evaluates one. Of the batch shape's own members only block and scope count (the
+  // memory scope of every member's table flush: part of the fuse key). Empty: no batch; these enter key() only when set.
+  std::vector<VhJitShape> members;
+  std::vector<int> mask_of;
   std::string key() const;
 };
 // Bytes of the one packed record a survivor of this shape gathers (4 or 8), 0 for every other payload: arenas, wider records or more than one,
@@ -131,6 +138,15 @@ int vh_jit_occupancy(VhJitKernel* k, int block, size_t lds);
 hipError_t vh_jit_launch(VhJitKernel* k, const VhPlanDev& P, int grid, int block, size_t lds, hipStream_t s);
 // ... of a plane-aggregate shape (VhJitShape::pa_sink): the descriptor's device pointer and the chunks per segment travel beside the plan
 hipError_t vh_jit_launch_planes(VhJitKernel* k, const VhPlanDev& P, const void* d_desc, uint32_t chunks_per_seg, int grid, int block, size_t lds, hipStream_t s);
+// ... of a batch shape (VhJitShape::members): the members' array in device memory (VhBatchMember, vh_sliced.h)
+// Whether the generator has a text for a batch shape: 2 to VH_BATCH_MAX plane-aggregate members of the batch's block size, a mask_of vector of
+// vh_batch_share's form that joins members of equal filter texts only, and at most 64 filter planes over all mask classes together.
+bool vh_jit_batch_ok(const VhJitShape& s);
+// What the generator's FILTER text of a plane-aggregate shape depends on, as a string (the program, the fields' places in F, the leaves'
+// types, F's slot): equal strings, equal mask() / preload() / Lits. Members of a batch shape may share a pass mask only under equal ones —
+// the host numbers them for vh_batch_share (VhShareDesc::filter_shape), and vh_jit_batch_ok refuses a mask_of that joins unequal ones.
+std::string vh_jit_filter_key(const VhJitShape& s);
+hipError_t vh_jit_launch_planes_batch(VhJitKernel* k, const void* d_members, uint32_t chunks_per_seg, int grid, int block, size_t lds, hipStream_t s);
 hipError_t vh_jit_launch_hpagg(VhJitKernel* k, const VhPlanDev& P, const void* d_hpargs, int blocks_per_partition, int a_first, int grid, size_t lds, hipStream_t s);
 hipError_t vh_jit_launch_pagg(VhJitKernel* k, const VhPlanDev& P, int blocks_per_part, size_t lds, hipStream_t s);
 #ifndef VH_HP_AGG_BLOCK

@@ -26,7 +26,7 @@
 #include <memory>
 #include <mutex>
 
-#include "../build/vh_jit_embed.inc"     // vj_embedded[]: the text of viya_hip.h, vh_internal.h, vh_kernels.h, vh_jit_body.h, vh_jit_planes.h and what they include (build.py)
+#include "../build/vh_jit_embed.inc"     // vj_embedded[]: the text of viya_hip.h, vh_internal.h, vh_kernels.h, vh_jit_body.h, vh_jit_planes.h, vh_jit_planes_batch.h and what they include (build.py)
 
 // ------------------------------------------------------------------ policy
 int vh_jit_policy() {
@@ -77,6 +77,10 @@ std::string VhJitShape::key() const {
     k += "pa"; put(pa_sink); put(pa_filter); put(pa_vslot);
     for (int i = 0; i < ng; ++i) { put(pa_goff[i]); put(pa_gbits[i]); }
     for (int j = 0; j < nm; ++j) { put(pa_moff[j]); put(pa_mbits[j]); }
+  }
+  if (!members.empty()) {      // (likewise: only a batch shape has members — each with the key it has as a single query, in order, and whose mask it takes)
+    k += "bt"; put((long long)members.size());
+    for (size_t i = 0; i < members.size(); ++i) { k += '['; k += members[i].key(); k += ']'; put(i < mask_of.size() ? mask_of[i] : -1); }
   }
   return k;
 }
@@ -139,21 +143,25 @@ static std::string vj_int_array(const char* name, int n, const std::vector<int>&
   return s + "};\n";
 }
 
-std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
+// One shape's text. `whole`: the text of a kernel — what is said ahead of the frame, the frame's include, the traits struct `sname` and the
+// entry points; false: the traits struct of a plane-aggregate shape alone, under the name a batch shape gives its member (vj_batch_source).
+static std::string vj_source(const VhJitShape& s, const char* kernel_name, const char* sname, bool whole) {
   std::string t;
   // (a scan that trims the runs of a sub-sorted form says so ahead of the frame; every other shape's text is what it always was)
   const bool subtrim = s.pp_sliced && s.pp_group >= 0 && s.pp_group < s.npred && !s.qpay && !s.lanes && s.gp_slot >= 0 && s.gp_G > 0 &&
                        s.sub_slot >= 0 && s.sub_pred >= 0 && s.sub_pred < s.npred && s.sub_pred != s.pp_group && vh_gsub_op_ok(s.sub_op);
   // (the aggregate on the planes has a frame of its own, which no other shape's text names)
-  if (s.pa_sink) t += "// generated by vh_jit.hip for one plan shape; the frame is vh_jit_planes.h\n";
+  if (!whole) {}
+  else if (s.pa_sink) t += "// generated by vh_jit.hip for one plan shape; the frame is vh_jit_planes.h\n";
   else t += "// generated by vh_jit.hip for one plan shape; the frame is vh_jit_body.h\n#define VH_HPART_KERNELS\n";
-  if (subtrim) t += "#define VJ_SUBTRIM 1\n";
+  if (subtrim && whole) t += "#define VJ_SUBTRIM 1\n";
   // (... and so does one whose tile groups span segments)
   const bool gpspan = s.gp_span && vh_jit_span_ok(s);
-  if (gpspan) t += "#define VJ_GPSPAN 1\n";
-  if (s.pa_sink) t += "#include \"vh_jit_planes.h\"\n";
+  if (gpspan && whole) t += "#define VJ_GPSPAN 1\n";
+  if (!whole) {}
+  else if (s.pa_sink) t += "#include \"vh_jit_planes.h\"\n";
   else t += "#include \"vh_jit_body.h\"\n#include \"vh_hpart.h\"\n";
-  t += "typedef uint32_t vj_u32x2 __attribute__((ext_vector_type(2)));\n#define vj_b(x) __builtin_amdgcn_ballot_w64(x)\n";
+  if (whole) t += "typedef uint32_t vj_u32x2 __attribute__((ext_vector_type(2)));\n#define vj_b(x) __builtin_amdgcn_ballot_w64(x)\n";
   // ---- packed predicate registers: stream p (a predicate column, or a plane of the bit-packed predicate projection) occupies
   //      v[base[p] .. base[p] + 4 * width) of every lane
   struct Stream { int slot, width; };
@@ -168,7 +176,7 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
   for (size_t p = 0; p < streams.size(); ++p) { base[p] = nv; nv += VH_SUBSTEPS * streams[p].width; }
   if (s.pp_sliced) nv = snv;
   const int nva = nv ? nv : 1;
-  t += "struct VJ {\n";
+  t += vj_fmt("struct %s {\n", sname);
   t += vj_fmt("  static constexpr int MODE = %d, BLOCK = %d, SCOPE = %d, NV = %d, NG = %d, NM = %d, TW = %d, KEY_WORDS = %d, CARRIER = %d;\n",
               s.mode, s.block, s.scope, nv, s.ng, s.nm, s.tw > 0 ? s.tw : 1, s.key_words, s.carrier);
   t += vj_fmt("  static constexpr int ABLATE = %d, BITSET_J = %d;\n  static constexpr bool HPART = %s;\n", s.ablate, s.bitset_j, s.hpart ? "true" : "false");
@@ -362,6 +370,7 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
                 s.pa_vslot, s.pa_vslot, s.pa_vslot);
     for (int pl = 0; pl < 32; ++pl) if ((need >> pl) & 1u) t += vj_fmt("    v[%d] = VH_BITS_LOAD(base + %dull * ps);\n", pl, pl);
     t += "  }\n};\n";
+    if (!whole) return t;
     t += vj_fmt("extern \"C\" __global__ __launch_bounds__(%d) void %s(const VhPlanDev P, const VhPlaneAggDesc* __restrict__ D, uint32_t chunks_per_seg) { vj_plane_agg<VJ>(P, D, chunks_per_seg); }\n",
                 s.block, kernel_name);
     return t;
@@ -602,6 +611,82 @@ std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
                 bound.c_str(), kernel_name, VH_HP_AGG_BLOCK);
   }
   return t;
+}
+
+// A BATCH shape's text (VhJitShape::members; the frame is vh_jit_planes_batch.h): member k's traits struct VJ<k> — the struct its shape gets as a
+// single query, by the same code — and VJB, the list: which member evaluates a pass mask and which takes an earlier one's (mask_of as
+// constants: the masks are registers), the loads of V's planes over the union of the members' need, and the members in order for the frame's
+// unrolled loops. Nothing that is data: literals, truth tables, snapshots, patterns and lds_base are read from the members' array.
+std::string vh_jit_filter_key(const VhJitShape& s) {
+  VhJitShape f;
+  f.pa_sink = 1; f.pa_filter = s.pa_filter;
+  if (s.pa_filter) {
+    f.prog = s.prog; f.nlits = s.nlits; f.npred = s.npred; f.pp_sliced = s.pp_sliced; f.pp_slot = s.pp_slot;
+    for (int k = 0; k < s.npred; ++k) { f.pred[k] = s.pred[k]; f.pp_off[k] = s.pp_off[k]; f.pp_bits[k] = s.pp_bits[k]; }
+  }
+  return f.key();
+}
+bool vh_jit_batch_ok(const VhJitShape& s) {
+  const size_t n = s.members.size();
+  if (n < 2 || n > VH_BATCH_MAX || s.mask_of.size() != n) return false;
+  int filter_planes = 0;
+  for (size_t k = 0; k < n; ++k) {
+    const VhJitShape& m = s.members[k];
+    const int of = s.mask_of[k];
+    if (!m.pa_sink || !m.members.empty() || m.block != s.block || of < 0 || of > (int)k || s.mask_of[(size_t)of] != of) return false;
+    if (of != (int)k && vh_jit_filter_key(m) != vh_jit_filter_key(s.members[(size_t)of])) return false;      // (the leader's word must be the text this member would have had)
+    if (of == (int)k && m.pa_filter) for (int p = 0; p < m.npred; ++p) filter_planes += m.pp_bits[p];
+  }
+  return filter_planes <= 64;      // (the filter planes of all mask classes together: what one compiled scan allows itself)
+}
+static std::string vj_batch_source(const VhJitShape& s, const char* kernel_name) {
+  const int n = (int)s.members.size();
+  std::string t = "// generated by vh_jit.hip for one batch shape; the frame is vh_jit_planes_batch.h\n#include \"vh_jit_planes_batch.h\"\n";
+  t += "typedef uint32_t vj_u32x2 __attribute__((ext_vector_type(2)));\n#define vj_b(x) __builtin_amdgcn_ballot_w64(x)\n";
+  uint32_t all = 0u, every = ~0u;
+  bool rows = false;
+  auto span = [](int off, int bits) { return bits <= 0 ? 0u : (bits >= 32 ? ~0u : (1u << bits) - 1u) << off; };
+  for (int k = 0; k < n; ++k) {
+    const VhJitShape& m = s.members[(size_t)k];
+    t += vj_source(m, nullptr, vj_fmt("VJ%d", k).c_str(), false);
+    uint32_t need = 0u;
+    for (int i = 0; i < m.ng; ++i) need |= span(m.pa_goff[i], m.pa_gbits[i]);
+    for (int j = 0; j < m.nm; ++j) need |= span(m.pa_moff[j], m.pa_mbits[j]);
+    all |= need; every &= need;
+    rows = rows || m.pa_sink == 2;
+  }
+  t += "struct VJB {\n";
+  t += vj_fmt("  static constexpr int N = %d, BLOCK = %d, SCOPE = %d, V_SLOT = %d;\n  static constexpr bool ROWS = %s;\n  static constexpr uint32_t NEED_ALL = 0x%Xu;\n",
+              n, s.block, s.scope, s.members[0].pa_vslot, rows ? "true" : "false", all);
+  // step 1: one evaluation per mask class, in member order; a member of an earlier member's class takes its word
+  t += vj_fmt("  static __device__ __forceinline__ void masks(const VhBatchMember* __restrict__ Q, uint32_t seg, uint64_t base, uint64_t row_l, uint32_t (&m)[%d]) {\n", n);
+  for (int k = 0; k < n; ++k) {
+    if (s.mask_of[(size_t)k] == k) t += vj_fmt("    m[%d] = vj_member_mask<VJ%d>(Q[%d].P, seg, base, row_l);\n", k, k, k);
+    else t += vj_fmt("    m[%d] = m[%d];\n", k, s.mask_of[(size_t)k]);
+  }
+  t += "  }\n";
+  // step 3: V's planes by constant number — member 0's plan names V (the fuse key: one V for all) —, those of `need`, the union over the
+  // members with a passing row in the wave (uniform); a plane every member needs is in every such union
+  t += "  static __device__ __forceinline__ void v_load(const VhPlanDev& P, uint32_t seg, uint32_t row_l, uint32_t need, uint32_t (&v)[VH_BITS_MAX_FIELD]) {\n";
+  t += "    const char* base = P.colbase[V_SLOT] + (uint64_t)seg * P.colstride[V_SLOT] + (uint64_t)(row_l >> 5) * 4ull;\n    const uint64_t ps = P.colpitch[V_SLOT];\n    (void)base; (void)ps; (void)need; (void)v;\n";
+  for (int pl = 0; pl < 32; ++pl) {
+    if (!((all >> pl) & 1u)) continue;
+    if ((every >> pl) & 1u) t += vj_fmt("    v[%d] = VH_BITS_LOAD(base + %dull * ps);\n", pl, pl);
+    else t += vj_fmt("    if ((need >> %d) & 1u) v[%d] = VH_BITS_LOAD(base + %dull * ps);\n", pl, pl, pl);
+  }
+  t += "  }\n";
+  // the members in order, for the frame's loops: f(position, traits)
+  t += "  template <class F> static __device__ __forceinline__ void each(F&& f) {\n";
+  for (int k = 0; k < n; ++k) t += vj_fmt("    f(VhIdx<%d>{}, VJ%d{});\n", k, k);
+  t += "  }\n};\n";
+  t += vj_fmt("extern \"C\" __global__ __launch_bounds__(%d) void %s(const VhBatchMember* __restrict__ Q, uint32_t chunks_per_seg) { vj_plane_agg_batch<VJB>(Q, chunks_per_seg); }\n",
+              s.block, kernel_name);
+  return t;
+}
+
+std::string vh_jit_source(const VhJitShape& s, const char* kernel_name) {
+  if (!s.members.empty()) return vh_jit_batch_ok(s) ? vj_batch_source(s, kernel_name) : std::string("#error \"no batch shape\"\n");
+  return vj_source(s, kernel_name, "VJ", true);
 }
 
 // ------------------------------------------------------------------ hipRTC (resolved at first use: the library loads where it is absent)
@@ -890,6 +975,15 @@ hipError_t vh_jit_launch_planes(VhJitKernel* k, const VhPlanDev& P, const void* 
   return hipModuleLaunchKernel(k->fn, (unsigned)grid, 1, 1, (unsigned)block, 1, 1, (unsigned)lds, s, args, nullptr);
 }
 
+hipError_t vh_jit_launch_planes_batch(VhJitKernel* k, const void* d_members, uint32_t chunks_per_seg, int grid, int block, size_t lds, hipStream_t s) {
+  if (lds > k->scan_lds_set) {
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k->fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    k->scan_lds_set = lds;
+  }
+  void* args[] = {&d_members, &chunks_per_seg};
+  return hipModuleLaunchKernel(k->fn, (unsigned)grid, 1, 1, (unsigned)block, 1, 1, (unsigned)lds, s, args, nullptr);
+}
+
 hipError_t vh_jit_launch(VhJitKernel* k, const VhPlanDev& P, int grid, int block, size_t lds, hipStream_t s) {
   if (lds > k->scan_lds_set) {       // (the scan that partitions by itself keeps 64 KB of waiting lines next to its queues)
     if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k->fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -960,6 +1054,55 @@ static bool vj_canonical(int which, VhJitShape* s) {
     const int sops[6] = {SOP_ADD64, SOP_MIN_I32, SOP_MAX_I32, SOP_MIN_U32, SOP_MAX_U64, SOP_MIN_I64};
     const int offs[6] = {0, 0, 9, 9, 20, 20}, bits[6] = {9, 9, 11, 11, 12, 12};
     for (int j = 0; j < 6; ++j) { S.m[j].sop = sops[j]; S.pa_moff[j] = offs[j]; S.pa_mbits[j] = bits[j]; }
+    return true;
+  }
+  // BATCH shapes (vh_jit_planes_batch.h). 41: two members over 38's plan under its filter — GROUP BY d2, and the totals — sharing one mask;
+  // 43: the same with a mask each (the A/B's shape), 44: 41's members in the other order. 42: eight members over a V of 32 planes in three
+  // filter classes and a set leaf — A = 38's filter (members 0, 1, 5; 5 through the row sink), B = d3 < x alone (2, 6), none (3: 40's six
+  // metrics over all 32 planes; 7), and 38's filter with its d3 leaf as a set (4: a set leaf never shares)
+  // 45 / 46: four and five members, every one a mask class of its own with literals of its own: the shapes between 41 and 42 in scalar
+  // registers (with its members' plan data hoisted out of the chunk loop 45 spilled 14 of them: vh_jit_planes_batch.h reloads per chunk).
+  // 45: 38's filter (GROUP BY d2), the same with `<=` for its d3 leaf (totals), B = d3 < x alone (totals) and d3 >= x alone (GROUP BY d2); 46: those and 40's member without a filter.
+  // 47: 41 with member 1 under B but mask_of [0, 0] — a vector that joins unequal filter texts: no shape (vh_jit_batch_ok)
+  if (which >= 45 && which <= 47) {
+    VhJitShape a, b;
+    if (!vj_canonical(38, &a)) return false;
+    S.mode = VH_MODE_DENSE_LDS; S.block = 256; S.scope = a.scope; S.xcd = a.xcd;
+    b = a; b.npred = 1; b.pred[0] = a.pred[1]; b.pp_off[0] = a.pp_off[1]; b.pp_bits[0] = a.pp_bits[1];
+    b.prog = {vj_leaf(VH_F_REL, VH_U32, VH_OP_LT, 0, 0)}; b.nlits = 1; b.ng = 0;
+    if (which == 47) { S.members = {a, b}; S.mask_of = {0, 0}; return true; }
+    VhJitShape le = a, ge = b, none;
+    le.prog[1].set_op(VH_OP_LE); le.ng = 0;
+    ge.prog[0].set_op(VH_OP_GE); ge.ng = 1;
+    S.members = {a, le, b, ge};      // 22 + 22 + 10 + 10 filter planes: the 64 a batch shape may read
+    S.mask_of = {0, 1, 2, 3};
+    if (which == 46) {
+      if (!vj_canonical(40, &none)) return false;
+      none.scope = a.scope; none.xcd = a.xcd; none.pa_vslot = a.pa_vslot;
+      S.members.push_back(none); S.mask_of.push_back(4);
+    }
+    return true;
+  }
+  if (which >= 41 && which <= 44) {
+    VhJitShape a, tot;
+    if (!vj_canonical(38, &a)) return false;
+    tot = a; tot.ng = 0;
+    S.mode = VH_MODE_DENSE_LDS; S.block = 256; S.scope = a.scope; S.xcd = a.xcd;
+    if (which != 42) {
+      S.members = which == 44 ? std::vector<VhJitShape>{tot, a} : std::vector<VhJitShape>{a, tot};
+      S.mask_of = which == 43 ? std::vector<int>{0, 1} : std::vector<int>{0, 0};
+      return true;
+    }
+    VhJitShape rows, b, btot, none, ntot, set;
+    if (!vj_canonical(39, &rows) || !vj_canonical(40, &none)) return false;
+    b = a; b.npred = 1; b.pred[0] = a.pred[1]; b.pp_off[0] = a.pp_off[1]; b.pp_bits[0] = a.pp_bits[1];
+    b.prog = {vj_leaf(VH_F_REL, VH_U32, VH_OP_LT, 0, 0)}; b.nlits = 1;
+    btot = b; btot.ng = 0;
+    none.scope = a.scope; none.xcd = a.xcd; none.pa_vslot = a.pa_vslot;
+    ntot = none; ntot.nm = 1; ntot.m[0].sop = SOP_ADD64; ntot.pa_moff[0] = 2; ntot.pa_mbits[0] = 10;
+    set = a; set.prog[1] = vj_leaf(VH_F_INSET, VH_U32, 1, 1, 0, 0); set.prog[2].set_lit(1); set.nlits = 2;
+    S.members = {a, tot, b, none, set, rows, btot, ntot};
+    S.mask_of = {0, 0, 2, 3, 4, 0, 2, 3};
     return true;
   }
   switch (which) { case 25: which = 22; depth = 1; break; case 26: which = 22; depth = 2; break; case 27: which = 21; depth = -2; break; case 28: which = 7; depth = -2; break; case 29: which = 1; depth = -2; break; default: break; }
@@ -1122,6 +1265,15 @@ extern "C" VH_API int vh_jit_selftest_name(int32_t which, char* name, uint64_t n
   VhJitShape S;
   if (!vj_canonical(which, &S) || !name || !name_bytes) return VH_E_INVALID;
   snprintf(name, (size_t)name_bytes, "%s", kernel_name_of(S.key()).c_str());
+  return VH_OK;
+}
+
+extern "C" VH_API int vh_jit_selftest_key(int32_t which, char* key, uint64_t key_bytes) {
+  VhJitShape S;
+  if (!vj_canonical(which, &S) || !key || !key_bytes) return VH_E_INVALID;
+  const std::string k = S.key();
+  if (k.size() >= key_bytes) return VH_E_INVALID;
+  snprintf(key, (size_t)key_bytes, "%s", k.c_str());
   return VH_OK;
 }
 

@@ -542,31 +542,101 @@ extern "C" int vh_query_agg(vh_table* t, const vh_plan* plan, vh_result** out) {
 // would have made. Behind either, each member's own tail on its own stream (query_scan_tail). t->mu is held, and so is the batch's tick.
 // Within a group, vh_batch_share (vh_batch.h) says which members take an earlier member's pass mask (VhBatchMember::mask_of); no_share: every
 // member evaluates its own (VH_TEST_NO_BATCH_SHARE).
+// COMPILED candidates (vh_batch.h; members that asked for the compiled plane aggregate and have their own kernel) form groups of their own. Such
+// a group is answered by the kernel compiled for its BATCH SHAPE (batch_kernel below): the members' shapes in launch order, the mask_of
+// vector — vh_batch_share's with one more condition, equal filter member-shapes — and the scope. While that kernel is pending, and where it
+// failed or the generator has no shape for the group, the group is dissolved before anything is launched: each member is launched by its own
+// compiled kernel, the single compiled query it would have been (never an error, VH_PLAN_FORCE_JIT or not).
 static_assert(VH_SHARE_KIND_REL == VH_F_REL && VH_SHARE_KIND_IN == VH_F_IN && VH_SHARE_KIND_INSET == VH_F_INSET, "vh_batch.h restates enum vh_fkind");
 static_assert(sizeof(VhBitsOp) == 8 && offsetof(VhBitsOp, w0) == 0 && offsetof(VhBitsOp, w1) == 4, "vh_batch.h reads an op as two words");
-struct VhBatchGroups { uint32_t n = 0; int32_t of[VH_BATCH_MAX]; uint32_t lead[VH_BATCH_MAX]; };
-static int batch_launch_scans(VhBatchFuse& F, uint32_t n, VhBatchGroups* G, uint32_t* failed, bool no_share) {
+struct VhBatchGroups { uint32_t n = 0, compiled = 0; int32_t of[VH_BATCH_MAX]; uint32_t lead[VH_BATCH_MAX]; };
+// The kernel of a compiled group's batch shape, by the single shape's paths (compile_plane_agg): inline mode compiles here and counts it in
+// inline_builds, background mode asks the worker. nullptr: *pending says whether the worker has it; else `why` holds the reason.
+static VhJitKernel* batch_kernel(vh_table* t, const VhJitShape& js, bool* pending, std::string* why) {
+  *pending = false;
+  if (!vh_jit_batch_ok(js)) { *why = "the generator has no shape for this group"; return nullptr; }
+  VhJitKernel* k = nullptr;
+  if (build_background(t)) {
+    if (vh_jit_peek(js, &k, why) == 0) *pending = build_request_kernel(t, js);
+    if (!*pending && !k && why->empty()) *why = "the build worker is shutting down";
+    if (*pending) *why = "the batch kernel is being compiled";
+  } else {
+    VhJitKernel* had = nullptr;
+    std::string ignored;
+    const bool known = vh_jit_peek(js, &had, &ignored) != 0;
+    k = vh_jit_get(js, why);
+    if (!known) ++t->inline_builds;
+  }
+  return k;
+}
+static int batch_launch_scans(vh_table* t, VhBatchFuse& F, uint32_t n, VhBatchGroups* G, uint32_t* failed, bool no_share) {
   VhFuseDesc d[VH_BATCH_MAX] = {};
   VhShareDesc sh[VH_BATCH_MAX] = {};
+  std::string fshape[VH_BATCH_MAX];
   for (uint32_t i = 0; i < n; ++i) {
     const VhDeferredScan& s = F.scan[i];
     if (!s.r) continue;
     d[i].candidate = 1; d[i].scope = s.xcd_private ? 1u : 0u; d[i].v_serial = s.v_serial; d[i].nseg = (uint32_t)s.P.nseg; d[i].chunks_per_seg = s.chunks_per_seg;
     d[i].lds_bytes = (uint32_t)((s.lds_table + 15) / 16 * 16);
+    d[i].compiled = s.pagg_jk ? 1u : 0u;
     VhShareDesc& h = sh[i];
     h.has_filter = s.D.has_filter; h.f_serial = s.f_serial;
     h.f_planes = (uint64_t)(uintptr_t)s.A.F.planes; h.f_stride = s.A.F.stride; h.f_pitch = s.A.F.pitch;
     h.nprog = s.B.nprog; h.flat = s.B.flat; h.ops = &s.B.op[0].w0; h.lits = s.B.lits; h.nlits = VH_BITS_MAX_LITS;
     h.nseg = (uint32_t)s.P.nseg; h.seg_rows = s.segrows;
+    if (s.pagg_jk) {      // (equal filter member-shapes, equal numbers: the first such member's position + 1)
+      fshape[i] = vh_jit_filter_key(s.js);
+      h.filter_shape = i + 1;
+      for (uint32_t j = 0; j < i; ++j) if (F.scan[j].r && F.scan[j].pagg_jk && fshape[j] == fshape[i]) { h.filter_shape = j + 1; break; }
+    }
   }
   G->n = vh_batch_group(d, n, G->of);
+  // the compiled groups' kernels first: a group whose batch kernel is not at hand is no group (its members: their own compiled kernels)
+  VhJitKernel* bk[VH_BATCH_MAX] = {};
+  uint32_t share_of[VH_BATCH_MAX][VH_BATCH_MAX], share_classes[VH_BATCH_MAX] = {};
+  {
+    uint32_t kept = 0;
+    bool pend[VH_BATCH_MAX] = {};
+    for (uint32_t g = 0; g < G->n; ++g) {
+      uint32_t m[VH_BATCH_MAX], cnt = 0;
+      for (uint32_t i = 0; i < n; ++i) if (G->of[i] == (int32_t)g) m[cnt++] = i;
+      uint32_t mask_of[VH_BATCH_MAX], classes = cnt;
+      if (no_share) for (uint32_t k = 0; k < cnt; ++k) mask_of[k] = k;
+      else classes = vh_batch_share(sh, m, cnt, mask_of);
+      VhJitKernel* k = nullptr;
+      bool dissolve = false;
+      if (d[m[0]].compiled) {
+        VhJitShape js;
+        js.mode = VH_MODE_DENSE_LDS; js.block = 256;
+        js.scope = F.scan[m[0]].js.scope; js.xcd = F.scan[m[0]].js.xcd;      // (part of the fuse key: the same for every member)
+        for (uint32_t q = 0; q < cnt; ++q) { js.members.push_back(F.scan[m[q]].js); js.mask_of.push_back((int)mask_of[q]); }
+        bool pending = false;
+        std::string why;
+        *failed = m[0];
+        k = batch_kernel(t, js, &pending, &why);
+        if (!k) {
+          if (knobs().jit_verbose) fprintf(stderr, "vh: no compiled fused launch for %u members, each runs its own compiled kernel: %s\n", cnt, why.c_str());
+          dissolve = true;
+          for (uint32_t q = 0; q < cnt; ++q) { G->of[m[q]] = -1; pend[m[q]] = pending; }
+        }
+      }
+      if (dissolve) continue;
+      for (uint32_t q = 0; q < cnt; ++q) { G->of[m[q]] = (int32_t)kept; share_of[kept][q] = mask_of[q]; }
+      share_classes[kept] = classes; bk[kept] = k;
+      if (k) ++G->compiled;
+      ++kept;
+    }
+    G->n = kept;
+    for (uint32_t i = 0; i < n; ++i) if (pend[i]) F.scan[i].r->info.reserved |= VH_INFO_BUILD_PENDING;
+  }
   for (uint32_t i = 0; i < n; ++i) {      // alone after all: the single query's launch
     const VhDeferredScan& s = F.scan[i];
     if (!s.r || G->of[i] >= 0) continue;
     *failed = i;
     VhScanLaunch L;
     L.grid = s.grid; L.lds = s.lds_table; L.stream = s.x->stream();
-    vh_launch_scan_planes(s.P, s.A, s.chunks_per_seg, L, s.xcd_private);
+    if (s.pagg_jk) HIP_TRY(vh_jit_launch_planes(s.pagg_jk, s.P, s.A.D, s.chunks_per_seg, s.grid, 256, s.lds_table, L.stream));      // (scan_dispatch's launch of the single compiled query)
+    else vh_launch_scan_planes(s.P, s.A, s.chunks_per_seg, L, s.xcd_private);
     if (int rc = query_scan_tail(s.r, s.x)) return rc;
   }
   for (uint32_t g = 0; g < G->n; ++g) {
@@ -580,9 +650,8 @@ static int batch_launch_scans(VhBatchFuse& F, uint32_t n, VhBatchGroups* G, uint
     uint32_t lds = 0;
     int grid = 0;
     bool rows = false;      // any row member: the instantiation that carries the row sink
-    uint32_t mask_of[VH_BATCH_MAX], classes = cnt;
-    if (no_share) for (uint32_t k = 0; k < cnt; ++k) mask_of[k] = k;
-    else classes = vh_batch_share(sh, m, cnt, mask_of);
+    const uint32_t* mask_of = share_of[g];
+    const uint32_t classes = share_classes[g];
     for (uint32_t k = 0; k < cnt; ++k) {      // the lead's stream behind every member's clears and uploads; the members' array, staged
       const VhDeferredScan& s = F.scan[m[k]];
       if (s.x->stream() != ls) HIP_TRY(hipStreamWaitEvent(ls, s.x->ev[1], 0));
@@ -595,12 +664,17 @@ static int batch_launch_scans(VhBatchFuse& F, uint32_t n, VhBatchGroups* G, uint
     HIP_TRY(hipMemcpyAsync(lx->d_batch, lx->h_batch, cnt * sizeof(VhBatchMember), hipMemcpyHostToDevice, ls));
     HIP_TRY(hipEventRecord(lx->ev_batch[0], ls));
     char nm[160] = "";
-    VhScanLaunch L;
-    L.name = nm; L.name_cap = sizeof(nm);
-    vh_launch_scan_planes_batch(lx->d_batch, cnt, lead.A.V, lead.chunks_per_seg, L, lead.xcd_private, rows);      // (its name)
-    L = VhScanLaunch{};
-    L.grid = grid; L.lds = lds; L.stream = ls;
-    vh_launch_scan_planes_batch(lx->d_batch, cnt, lead.A.V, lead.chunks_per_seg, L, lead.xcd_private, rows);
+    if (bk[g]) {      // a compiled group: the kernel of its batch shape (the row sink's queue is static LDS of a text with a row member)
+      snprintf(nm, sizeof(nm), "%s", bk[g]->name.c_str());
+      HIP_TRY(vh_jit_launch_planes_batch(bk[g], lx->d_batch, lead.chunks_per_seg, grid, 256, lds, ls));
+    } else {
+      VhScanLaunch L;
+      L.name = nm; L.name_cap = sizeof(nm);
+      vh_launch_scan_planes_batch(lx->d_batch, cnt, lead.A.V, lead.chunks_per_seg, L, lead.xcd_private, rows);      // (its name)
+      L = VhScanLaunch{};
+      L.grid = grid; L.lds = lds; L.stream = ls;
+      vh_launch_scan_planes_batch(lx->d_batch, cnt, lead.A.V, lead.chunks_per_seg, L, lead.xcd_private, rows);
+    }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(lx->ev_batch[1], ls));
     for (uint32_t k = 0; k < cnt; ++k) {      // every member's stream behind the launch, then its own tail there
@@ -674,7 +748,7 @@ extern "C" int vh_query_agg_batch(vh_table* t, const vh_plan* const* plans, uint
         if (rc) { rs[i] = nullptr; break; }
         rs[i]->exec = xs[i];
       }
-      if (!rc) rc = batch_launch_scans(*fuse, n, &G, &failed, no_share);
+      if (!rc) rc = batch_launch_scans(t, *fuse, n, &G, &failed, no_share);
     }
     evicted = t->layout_budget != 0 && g_plan_evicted;
   }
@@ -699,6 +773,7 @@ extern "C" int vh_query_agg_batch(vh_table* t, const vh_plan* const* plans, uint
       if (G.of[i] == (int32_t)g && (out[i]->info.reserved & VH_INFO_BATCH_FUSED)) { out[i]->info.scan_kernel_ms = ms; ++bi.fused_members; }      // (a member that was planned again is a single query's result)
   }
   bi.singles = n - bi.fused_members;
+  bi.reserved = G.compiled;      // (the compiled fused launches among fused_groups)
   if (evicted) for (uint32_t i = 0; i < n; ++i) out[i]->info.reserved |= VH_INFO_EVICTED;
   if (info) *info = bi;
   return VH_OK;

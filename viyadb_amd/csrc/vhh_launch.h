@@ -239,7 +239,7 @@ int QueryBuild::plan_again(bool keep_part, bool no_hashed_part) {
 
 // No compiled kernel for a plan that asked for the COMPILED aggregate on the planes and met the rest of its rule: the same plan with
 // VH_PLAN2_PLANE_AGG in the flag's place, for the pre-built kernels — choose_plane_agg then takes it (bit 27 without bit 5). A member of a
-// batch stays the single query it is.
+// batch is then answered as the single query it is; one with its kernel at hand is a compiled candidate of the batch (launch() below).
 int QueryBuild::plan_again_prebuilt_planes() {
   vh_plan p2 = *p;
   p2.flags |= VH_PLAN_NO_JIT;
@@ -318,6 +318,7 @@ int QueryBuild::compile_plane_agg(bool* settled) {
     return plan_again_prebuilt_planes();
   }
   pagg_jk = k;
+  pagg_shape = js;
   plane_agg_take(f, v);
   return VH_OK;
 }
@@ -1112,13 +1113,15 @@ int QueryBuild::launch() {
   if (g_heavy.only && !from_tuples && g_heavy.epoch != t->sync_epoch)       // the table has moved on since the first pass: its rows are no longer the rows that pass saw
     return vh_fail(VH_E_RANGE, "second pass over heavy ranges: the table changed since the first pass");      // (heavy_pass_finish gives up; the caller re-plans the whole query)
   if (from_tuples) {
-  } else if (P.total_units && plane_agg && o.fuse && !pagg_jit) {      // (a member that asked for the compiled form is answered as the single query it is)
+  } else if (P.total_units && plane_agg && o.fuse && (!pagg_jit || pagg_jk)) {      // (a member that asked for the compiled form and has no kernel of its own is answered as the single query it is)
     // A member of a batch whose scan may share a fused launch (vh_query_agg_batch): everything up to ev[1] is enqueued; the scan and what
     // follows it are the batch's to launch, once it knows the groups. The plan goes by value: it is complete here.
     VhDeferredScan& d = o.fuse->scan[o.fuse->member];
     d.r = r; d.x = x; d.P = P; d.A = pagg_ref; d.B = pagg_filter ? planes_prog : VhBitsProg{}; d.D = pagg_desc; d.grid = grid; d.lds_table = lds_table; d.xcd_private = nxcd > 1; d.v_serial = pagg_v->serial;
     d.f_serial = (pagg_filter ? sliced_use : pagg_v)->serial; d.segrows = x->h_segrows;
     d.chunks_per_seg = (uint32_t)std::max<uint64_t>(1, (t->padded_rows + VH_SLICED_CHUNK_ROWS - 1) / VH_SLICED_CHUNK_ROWS);
+    d.pagg_jk = pagg_jk;      // (a compiled candidate: vh_batch.h)
+    if (pagg_jk) d.js = pagg_shape;
     *out = holder.release();
     done = true;
     return VH_OK;

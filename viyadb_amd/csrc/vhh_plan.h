@@ -211,6 +211,10 @@ struct VhDeferredScan {
   bool xcd_private = false; uint32_t chunks_per_seg = 0; uint64_t v_serial = 0;
   uint64_t f_serial = 0;      // the projection F the program reads (V's where there is no filter): part of the mask key (vh_batch.h)
   const uint32_t* segrows = nullptr;      // the effective rows per segment as staged (x->h_segrows[0 .. P.nseg): the context is the member's own until its result is freed)
+  // a COMPILED candidate (vh_batch.h): the member's own compiled kernel — what launches it when it stays alone or its group's batch kernel
+  // cannot be had — and the shape it was compiled for, a member shape of the group's batch shape. nullptr: a pre-built candidate
+  VhJitKernel* pagg_jk = nullptr;
+  VhJitShape js;
 };
 struct VhBatchFuse { VhDeferredScan scan[VH_BATCH_MAX]; uint32_t member = 0; };      // member: the one being planned
 // ... and how query_launch_locked is asked for a plan, beyond table, context and the plan itself: every caller names the members it sets.
@@ -338,6 +342,7 @@ struct QueryBuild {
   bool plane_agg_rule(VhPredPack** f, VhPredPack** v);
   void plane_agg_take(VhPredPack* f, VhPredPack* v);      // the rule holds and a kernel is at hand: the plan is the plane aggregate's, F and V are stamped and held
   void choose_plane_agg();
+  VhJitShape pagg_shape;                         // ... and the shape it was compiled for (a batch hands it on: VhDeferredScan::js)
   VhJitKernel* pagg_jk = nullptr;                // compile_kernel: the plane aggregate's kernel compiled for this plan's shape (jk stays null: no scan over rows is compiled)
   int compile_plane_agg(bool* settled);          // compile_kernel's first step for a plan that asked (pagg_jit)
   int plan_again_prebuilt_planes();              // ... and its way out where no compiled kernel can be had: the same plan with VH_PLAN2_PLANE_AGG in the flag's place

@@ -139,6 +139,11 @@ class AggResult:
         return bool(self.flags & capi.INFO_BATCH_FUSED)
 
     @property
+    def batch_compiled(self) -> bool:
+        """... of a kernel compiled for the batch's shape (PLAN2_PLANE_JIT members of query_agg_batch): batch_fused and plane_jit."""
+        return self.batch_fused and self.plane_jit
+
+    @property
     def sub_trimmed(self) -> bool:
         """The grouped form is sub-sorted and the scan trimmed every run to the words that can pass the sub column's leaf (bit 28; bits 20
         and 21 are set too): derived from `flags`, like plane_agg."""
@@ -508,7 +513,10 @@ class DeviceTable:
         """Up to capi.BATCH_MAX aggregates in one call (vh_query_agg_batch): results in plan order, each equal to query_agg's of the same
         plan, and how the batch was answered. Members that take the aggregate on the bit-sliced planes share fused launches
         (AggResult.batch_fused), and members of a launch with the same filter and snapshot share one evaluation of its pass mask
-        (AggResult.batch_member: launch, position, mask_of, mask_classes). All or nothing: a failing member fails the call."""
+        (AggResult.batch_member: launch, position, mask_of, mask_classes). Members that carry PLAN2_PLANE_JIT and have their own compiled
+        kernel group among themselves and are answered by one kernel compiled for the batch's shape (AggResult.batch_compiled,
+        BatchInfo.compiled_groups); while that kernel is not at hand each runs its own compiled kernel. All or nothing: a failing member
+        fails the call."""
         n = len(plans)
         built = [self._build_plan(p) for p in plans]
         ptrs = (C.POINTER(capi.Plan) * max(1, n))(*[C.pointer(b[0]) for b in built])
